@@ -9,13 +9,23 @@ profile pairs under WAG -- `--pairs` of them PER GPU (weak scaling: independent 
 nodes are farmed across ranks, no data-path collective; the only RCCL traffic is the
 one-off broadcast of the rate-model constant block).
 
-The line carries, beside the headline (the full, unbanded DP):
+A plain run times the headline (the full, unbanded DP in the --mode policy) and nothing else.  With --full the line
+carries beside it:
+  * the other fill policies on the same batch, and their lpEnd against the exact policy's;
   * `banded_mode`: the same kind of pairs inside a band-20 GuideAlignmentEnvelope - the reference's default mode and
     north_star's own target ("the banded forward DP for 2x2000-residue profile pairs") - at 512 pairs and at a
     batch large enough to fill the chip, in-envelope cells counted;
-  * for N > 1, `strong`: configs[3] as written - 512 pairs IN TOTAL dealt to the N ranks.
+  * for N > 1, `strong`: configs[3] as written - 512 pairs IN TOTAL dealt to the N ranks;
+  * for N = 1, `cpu_baseline`: the plain-C oracle timed on the host, and the device's lpEnd and best paths checked
+    against it.
 
-  python bench.py                      # 1 GPU, defaults finish in a few minutes
+--dump-outputs DIR writes what the headline path computed in its last timed step: `lp_end.npy` (every pair's Forward
+log-likelihood) and `forward_cells_sample.npy` (Forward-matrix cells, 5 states each, at a fixed, seeded sample of the
+cells where every state is finite; not written for bands below 2), all finite float64; with N > 1 every rank writes its
+own, suffixed `_rank<r>`.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
+  python bench.py                      # 1 GPU, the headline alone
+  python bench.py --full               # and the blocks above; a few minutes
   python bench.py --gpus N             # starts N rank processes itself (torch.distributed.run), one per GPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N      # the driver's form
 """
@@ -62,24 +72,30 @@ def parse():
     ap.add_argument("--pairs", type=int, default=512, help="independent pair DPs per GPU (weak scaling) or in total (strong)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --pairs pair DPs on every GPU.  strong: BASELINE configs[3] as written, --pairs pair DPs in "
-                         "total dealt to the GPUs (with N > 1 the weak line carries a `strong` block anyway)")
+                         "total dealt to the GPUs (with N > 1 and --full the weak line carries a `strong` block anyway)")
     ap.add_argument("--len", type=int, default=2000, dest="length", help="residues per sequence")
     ap.add_argument("--model", default="wag")
     ap.add_argument("--tl", type=float, default=0.2)
     ap.add_argument("--tr", type=float, default=0.3)
-    ap.add_argument("--cpu-pairs", type=int, default=10, help="pairs timed by the CPU baseline (rank 0, N=1)")
+    ap.add_argument("--cpu-pairs", type=int, default=10, help="pairs timed by the CPU baseline (rank 0, N=1, --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--band", type=int, default=-1,
                     help="guide-alignment band (maxDistanceFromGuide) of the HEADLINE workload; the guide is the pair's true "
-                         "alignment.  -1 = full envelope (the headline configuration; the banded block is added to it)")
+                         "alignment.  -1 = full envelope (the headline configuration; --full adds the banded block to it)")
     ap.add_argument("--mode", choices=list(MODES), default="trunc",
                     help="arithmetic of the headline fill.  trunc (default) = scaled probabilities with the reference's truncation; "
                          "fast = LDS-table log-sum-exp with the reference's truncation; both have best paths identical to the "
                          "reference's on all 2000 pairs of tools/sweep_trace_identity.py.  exact = the reference's table bit for "
                          "bit.  linear = scaled probabilities without the truncation (best paths may differ at near-ties).  The "
-                         "other policies are timed too")
-    ap.add_argument("--single-mode", action="store_true", help="time only --mode; no banded block, no strong block")
-    ap.add_argument("--banded-pairs", default="512,2560,4096", help="batch sizes of the banded block (band 20), comma separated; '' = none")
+                         "other policies are timed too under --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other policies, the banded block and (N > 1) the strong block, and (N = 1) run the "
+                         "CPU baseline with its checks; a plain run times the headline alone")
+    ap.add_argument("--single-mode", action="store_true", help="under --full: time only --mode; no banded block, no strong block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline path's outputs of its last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--banded-pairs", default="512,2560,4096",
+                    help="batch sizes of the banded block (band 20, --full), comma separated; '' = none")
     ap.add_argument("--traffic", type=float, default=None,
                     help="HBM bytes per launch from a PMC run (default: profiles/traffic.json entry for this workload)")
     return ap.parse_args()
@@ -96,6 +112,53 @@ def spawn_ranks(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
+
+
+DUMP_PAIRS = 16              # pairs of the batch whose Forward cells are sampled by --dump-outputs
+DUMP_CELLS = 4096            # cells sampled per pair (x 5 states x 8 bytes: 2.6 MB in all)
+
+
+def sample_cells(rng, n_rows, n_cols, triple, n):
+    """n seeded (i, j) of a pair's Forward matrix, uniform over the cells where every state holds a finite value: rows
+    1 .. n_rows-2 and columns 2 .. n_cols-2 (the first and last rows and columns hold the -inf of states that cannot be
+    reached there - IMI in column 1 among them), and under a band only cells at least two inside the envelope's edge
+    (at the edge a state's source cells lie outside it).  None when no such cell exists (bands below 2)."""
+    x, y, _, band = triple
+    rows = np.arange(1, n_rows - 1)
+    lo, hi = np.full(len(rows), 2), np.full(len(rows), n_cols - 1)
+    if band >= 0:
+        ex, ey = np.asarray(x.env_pos[:-1], np.int64), np.asarray(y.env_pos[:-1], np.int64)
+        lo = np.maximum(lo, np.searchsorted(ey, ex[rows] - (band - 2), "left"))
+        hi = np.minimum(hi, np.searchsorted(ey, ex[rows] + (band - 2), "right"))
+    width = np.maximum(hi - lo, 0)
+    if width.sum() == 0:
+        return None
+    first = np.concatenate([[0], np.cumsum(width)])
+    t = rng.integers(0, first[-1], n)
+    r = np.searchsorted(first, t, "right") - 1
+    return np.stack([rows[r], lo[r] + (t - first[r])], axis=1)
+
+
+def dump_outputs(batch, triples, lp_end, out_dir, rank=None):
+    """--dump-outputs: the outputs of the batch's last Forward pass as float64 .npy files - every pair's lpEnd, and the
+    Forward cells (all five states) at a fixed, seeded sample of (pair, i, j): pairs spread evenly over the batch, cells
+    drawn by sample_cells.  Every value written is finite; a sampled cell that is not is a wrong fill and fails here."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank is None else "_rank%d" % rank
+    rng = np.random.default_rng(20261016)
+    cells = []
+    for k in np.unique(np.linspace(0, batch.n - 1, min(DUMP_PAIRS, batch.n)).astype(int)):
+        l = batch.layout(int(k))
+        ij = sample_cells(rng, l.n_rows, l.n_cols, triples[k], DUMP_CELLS)
+        if ij is not None:
+            cells.append(batch.read_cells(int(k), ij))
+    lp_end = np.asarray(lp_end, dtype=np.float64)
+    assert np.all(np.isfinite(lp_end)), "non-finite Forward log-likelihood"
+    np.save(os.path.join(out_dir, "lp_end%s.npy" % sfx), lp_end)
+    if cells:
+        cells = np.concatenate(cells).astype(np.float64)
+        assert np.all(np.isfinite(cells)), "non-finite Forward cells inside the region where every state is reachable"
+        np.save(os.path.join(out_dir, "forward_cells_sample%s.npy" % sfx), cells)
 
 
 def _cpu_fill_worker(spec):
@@ -143,6 +206,8 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
     coll_dev = None if rehearse else dev      # where the collectives' tensors live (nccl: on the rank's GPU)
+    single = args.single_mode or not args.full                  # a plain run: the headline policy alone, no extra blocks
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
 
     from historian_amd import capi, farm, hostmodel, workload
 
@@ -175,9 +240,9 @@ def main():
                 print("built %d of %d pairs" % (k + 1, n), file=sys.stderr, flush=True)
         return triples, env
 
-    def timed(triples, mode, band, keep_traces=0):
+    def timed(triples, mode, band, keep_traces=0, dump=None):
         """W warm-up passes, then exactly K timed passes of the hot path between barrier + synchronize on both sides; the
-        time is the MAX over ranks."""
+        time is the MAX over ranks.  dump: directory for the outputs of the last timed pass (dump_outputs)."""
         # banded batches are stored band-compressed (per strip only the swept step windows): thousands of pairs fit
         batch = capi.Batch(triples, flags_of[mode] | (capi.HX_BAND_COMPRESSED if band >= 0 else 0))
         n_cells = batch.total_cells()
@@ -195,6 +260,8 @@ def main():
             dist.barrier()
         dt = farm.max_over_ranks(time.perf_counter() - t0, world, coll_dev)
         lp = batch.lp_end()
+        if dump:
+            dump_outputs(batch, triples, lp, dump, rank if world > 1 else None)
         traces = None
         if keep_traces:
             # outside the timed region: the device-side best-path traceback of every pair (hx_batch_best_trace); the first
@@ -209,15 +276,17 @@ def main():
     # strong scaling: BASELINE configs[3] as written - `--pairs` pairs IN TOTAL, dealt to the ranks; weak: per rank
     n_local, first = farm.deal(args.pairs, world, rank, strong)
     triples, env_cells_of = build(n_local, first, args.band)
-    order = [args.mode] + ([m for m in MODES if m != args.mode] if not args.single_mode else [])
-    runs = {m: timed(triples, m, args.band, keep_traces=args.cpu_pairs) for m in order}
+    order = [args.mode] + ([m for m in MODES if m != args.mode] if not single else [])
+    keep = args.cpu_pairs if args.full else 0       # (device best paths, compared with the CPU oracle's in the CPU leg)
+    runs = {m: timed(triples, m, args.band, keep_traces=keep, dump=args.dump_outputs if m == args.mode else None)
+            for m in order}
     head = runs[args.mode]
     cells = sum(env_cells_of) if args.band >= 0 else head["cells"]      # the metric counts in-envelope cells
     gcells = farm.sum_over_ranks(cells, world, coll_dev) if strong else cells * world
 
     # ---- the strong-scaling block (N > 1 under a weak headline): configs[3] as written, 512 pairs in total ----------
     strong_block = None
-    if world > 1 and not strong and not args.single_mode and args.band < 0:
+    if world > 1 and not strong and not single and args.band < 0:
         s_total = 512
         s_local, s_first = farm.deal(s_total, world, rank, True)
         # (rank 0's slice is a prefix of its weak batch; the other ranks build theirs)
@@ -230,7 +299,7 @@ def main():
 
     # ---- the banded block: band 20, the reference's default mode and north_star's own target ------------------------
     banded_block = None
-    if args.band < 0 and not args.single_mode and args.banded_pairs:
+    if args.band < 0 and not single and args.banded_pairs:
         banded_block = {"band": 20, "fill_mode": args.mode, "arithmetic": ARITH[args.mode], "kernel": KERNELS[(args.mode, True)],
                         "cells_counted": "in-envelope cells (band + envelope edges), band-compressed storage", "unit": "cells/s",
                         "scaling": "weak", "batches": []}
@@ -291,7 +360,7 @@ def main():
             out["banded_mode"] = banded_block
         if strong_block is not None:
             out["strong"] = strong_block
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_leg:
             from oracle import c_oracle           # the checker, timed as the CPU baseline ("port")
             c_oracle.load()
             n_cpu = max(1, min(args.cpu_pairs, n_local))

@@ -33,12 +33,12 @@ def test_two_ranks_on_one_gpu(scaling, pairs, port):
 def test_gpus_flag_starts_the_ranks_itself():
     # `python bench.py --gpus 2` with no launcher around it: bench.py starts two rank processes (torch.distributed.run)
     # before touching the GPU and rank 0's single line comes back, with the banded block (weak) and the strong block
-    # (configs[3] as written: 512 pairs in total dealt to the ranks)
+    # (configs[3] as written: 512 pairs in total dealt to the ranks); those blocks are --full's
     env = dict(os.environ, HX_BENCH_REHEARSE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "6",
-           "--len", "200", "--no-cpu-baseline", "--banded-pairs", "4,10"]
+           "--len", "200", "--no-cpu-baseline", "--banded-pairs", "4,10", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     lines = [l for l in out.stdout.decode().splitlines() if l.startswith("{")]
