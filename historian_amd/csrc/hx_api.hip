@@ -105,6 +105,20 @@ int fail(int code, const char* fmt, ...) {
 
 constexpr double NEG_INF = -std::numeric_limits<double>::infinity();
 
+// The arithmetic policy of a batch, decoded once at creation (hx_batch_create_on has folded HX_LSE_EXACT and the default
+// into the flags: "exact" is the absence of the fast / linear / truncating bits).
+struct Policy {
+  bool fast, linear, trunc;   // the fast table (every policy but exact); scaled-probability fills; ... with truncation
+  int band_mode;              // the banded sweep's policy (hx_band.hip): 0 linear, 1 fast, 2 exact, 3 truncating linear
+  explicit Policy(uint32_t flags = 0)
+      : fast((flags & HX_LSE_FAST) != 0), linear((flags & HX_LSE_LINEAR) == HX_LSE_LINEAR),
+        trunc((flags & HX_LSE_TRUNC) == HX_LSE_TRUNC), band_mode(linear ? (trunc ? 3 : 0) : (fast ? 1 : 2)) {}
+  // the table of the log-sum-exp fills: FastPiece table, or the exact mode's {f0, df} pairs
+  Tab16 lse_tab(const DeviceTables& D) const { return Tab16{fast ? D.fast_tab : D.pair_tab}; }
+  // the table of the banded rotating-row sweep's policy
+  Tab16 band_tab(const DeviceTables& D) const { return linear ? Tab16{D.log_tab} : lse_tab(D); }
+};
+
 // Grows a host staging image of the device arena; returns byte offsets.
 struct Arena {
   std::vector<char> host;
@@ -303,6 +317,7 @@ struct JobOff {
   size_t log_root, log_sub_l, log_sub_r, log_ins_l, log_ins_r, log_cptw_l, log_cptw_r, emis, emis_pad;
   size_t fwd_windows, bwd_windows, strip_base, yword, yword_bwd, band_rows, band_rows_bwd;
   bool compressed;
+  bool chain, leaf_like;  // both profiles are chains; ... of leaves (choose_class)
   int64_t compact_plane;
   int64_t eplane_off;     // into hx_batch::d_eplane, or -1
   bool table_emission;
@@ -366,76 +381,79 @@ std::vector<int32_t> strip_windows(const uint8_t* xf, const int32_t* xenv, const
 }
 
 
-// Rows of the banded rotating-row sweep (hx_band.hip): for every row of a leaf-like pair the anti-diagonal steps
-// k = i + j it owns - its in-envelope span of columns (reference src/forward.h:92-98), widened to whole step pairs -
-// and the base of its cells in a state plane.  Returns false when the pair does not satisfy what that kernel assumes:
+// Rows of the banded rotating-row sweeps (hx_band.hip): for every row of a leaf-like pair the anti-diagonal steps k = i + j
+// it owns - its in-envelope span of columns (reference src/forward.h:92-98), widened to whole step pairs - and the base of its
+// cells in a state plane.  The builders return false when the pair does not satisfy what that kernel assumes:
 //   * the envelope coordinates of both profiles are non-decreasing (true for leaf profiles under any guide alignment:
 //     cumulative match counts, reference src/alignpath.cpp:282-310), so a row's band is one span and spans move right;
 //   * the only always-in-envelope row is x START and the only such column the y state that feeds END (leaf profiles);
 //   * a lane that finishes row i is free before row i + 63's span opens (rows i .. i + 63 are never alive together).
 // Layout of a record: see BandRow in hx_band.hip.
-bool build_band_rows(const int32_t* xenv, const int32_t* yenv, const uint8_t* xf, const uint8_t* yf, const int32_t* xecls,
-                     bool x_empty, int R, int Cc, int band, int64_t ss, int blk, const int32_t* cwin, const int64_t* cbase,
-                     std::vector<int32_t>& out, int& n_steps) {
-  if (R < 2 || Cc < 2 || R + Cc > 60000) return false;
+
+// The envelope checks of both sweeps, then every sweep row's band of columns lo[i] .. hi[i] (two pointers over the columns:
+// the first with yenv >= xenv - band, the last with yenv <= xenv + band).  mirrored: the Backward sweep's coordinates.
+bool band_spans(const int32_t* xenv, const int32_t* yenv, const uint8_t* xf, const uint8_t* yf, int R, int Cc, int band,
+                bool mirrored, std::vector<int>& lo, std::vector<int>& hi) {
   for (int i = 1; i <= R; ++i) if (xenv[i] < xenv[i - 1]) return false;
   for (int j = 1; j <= Cc; ++j) if (yenv[j] < yenv[j - 1]) return false;
   for (int i = 0; i < R; ++i) if (((xf[i] & F_EDGE) != 0) != (i == 0)) return false;
   for (int j = 0; j < Cc; ++j) if (((yf[j] & F_EDGE) != 0) != (j == Cc - 1)) return false;
-  std::vector<int> lo(R), hi(R);
-  {
-    int a = 0, b = -1;                 // two pointers over the columns: first with yenv >= xenv - band, last with yenv <= xenv + band
-    for (int i = 0; i < R; ++i) {
-      while (a < Cc && (int64_t)yenv[a] < (int64_t)xenv[i] - band) ++a;
-      while (b + 1 < Cc && (int64_t)yenv[b + 1] <= (int64_t)xenv[i] + band) ++b;
-      if (b < a) return false;         // an empty band row: not a guide-alignment envelope
-      lo[i] = a; hi[i] = b;
-    }
+  lo.assign(R, 0); hi.assign(R, 0);
+  int a = 0, b = -1;
+  for (int i = 0; i < R; ++i) {
+    while (a < Cc && (int64_t)yenv[a] < (int64_t)xenv[i] - band) ++a;
+    while (b + 1 < Cc && (int64_t)yenv[b + 1] <= (int64_t)xenv[i] + band) ++b;
+    if (b < a) return false;           // an empty band row: not a guide-alignment envelope
+    if (mirrored) { lo[R - 1 - i] = Cc - 1 - b; hi[R - 1 - i] = Cc - 1 - a; }
+    else { lo[i] = a; hi[i] = b; }
   }
-  lo[0] = 0;
-  hi[0] = std::max(hi[0], hi[1]);      // row 1 reads row 0 up to its own last column (row 0 is in the envelope throughout)
-  for (int i = 0; i < R; ++i) if (hi[i] >= Cc - 2) hi[i] = Cc - 1;   // the cells next to the band in the always-in column
+  return true;
+}
+
+// From the sweep rows' spans to the records, for both sweeps.  The always-in-envelope column is the last one of the Forward
+// sweep and the first one of the Backward sweep (mirrored); the x state of sweep row i is i, or R-1-i (mirrored) with the
+// emission class of state R-i.  cwin / cbase: the band-compressed windows of the Forward planes, or null.
+bool encode_band_rows(const std::vector<int>& lo, const std::vector<int>& hi, bool mirrored, const uint8_t* xf,
+                      const int32_t* xecls, bool x_empty, int R, int Cc, int64_t ss, int blk, const int32_t* cwin,
+                      const int64_t* cbase, std::vector<int32_t>& out, int& n_steps) {
   const int n_strips = (R + HX_STRIP - 1) / HX_STRIP;
   out.assign(2 * (size_t)(R + 64) + (size_t)n_strips + 4, 0);
   int32_t* strip_store = &out[2 * (size_t)(R + 64)];
-  std::vector<int> os(R), oe(R), as_(R), ae_(R);
+  std::vector<int> os(R), oe(R);
   std::vector<char> have(n_strips, 0);
   n_steps = 0;
-  for (int i = 0; i < R; ++i) {
-    as_[i] = i + lo[i]; ae_[i] = i + hi[i];
-    os[i] = as_[i] & ~1; oe[i] = ae_[i] | 1;
-  }
+  for (int i = 0; i < R; ++i) { os[i] = (i + lo[i]) & ~1; oe[i] = (i + hi[i]) | 1; }
   // Whole cache lines: a step pair of a state plane holds rows 4g .. 4g + 3 of a strip in one 64-byte line, and a line that
   // the sweep writes in part costs a read-modify-write (a build that simply dropped the partly written lines at both ends of
   // a store ran a quarter faster).  So the four rows of such a group own the same steps - from the first row's first to the
-  // last row's last: the cells a row gains lie outside the envelope (the sweep computes them as zero cells and stores -inf,
-  // which is what they hold in pre-filled planes and "anything" in the others), except that nothing is gained in the
-  // always-in-envelope column: a row whose band does not reach it stops one column short (cell (1, Ny-2) there is the edge
-  // kernel's, the others are its -inf).  A group whose spread does not fit the record's three-bit pads keeps its own spans.
+  // last row's last (never past the pad cell of the last column: the plane ends there).  The cells a row gains lie outside
+  // the envelope (the sweep computes them as zero cells and stores -inf, which is what they hold in pre-filled planes and
+  // "anything" in the others) or, in the Backward sweep's first column and last row away from the band, are -inf (see
+  // build_band_rows_bwd) - except that nothing is gained in the Forward sweep's always-in-envelope column: a row whose band
+  // does not reach it stops one column short (cell (1, Ny-2) there is the edge kernel's, the others are its -inf).  A group
+  // whose spread does not fit the record's three-bit pads keeps its own spans.
   if (!getenv("HX_BAND_NO_LINE_GROUPS"))
     for (int g = 0; g < R; g += 4) {
       const int ge = std::min(g + 4, R);
       int gos = INT_MAX, goe = -1;
       for (int i = g; i < ge; ++i) { gos = std::min(gos, os[i]); goe = std::max(goe, oe[i]); }
       bool fits = true;
-      std::vector<int> no(ge - g), ne(ge - g);
+      int ne[4];
       for (int i = g; i < ge; ++i) {
-        // (never past the pad cell of the last column - the plane ends there -, and a row whose band does not reach the
-        // always-in-envelope column stops one column short of it)
         int e = std::min(goe, (i + Cc - 1) | 1);
-        if (hi[i] < Cc - 1) { int lim = i + Cc - 2; if (!(lim & 1)) --lim; e = std::min(e, std::max(lim, oe[i])); }
+        if (!mirrored && hi[i] < Cc - 1) { int lim = i + Cc - 2; if (!(lim & 1)) --lim; e = std::min(e, std::max(lim, oe[i])); }
         e = std::max(e, oe[i]);
-        no[i - g] = gos; ne[i - g] = e;
-        if (as_[i] - gos > 7 || e - ae_[i] > 7) fits = false;
+        ne[i - g] = e;
+        if (i + lo[i] - gos > 7 || e - (i + hi[i]) > 7) fits = false;
       }
       if (!fits) continue;
-      for (int i = g; i < ge; ++i) { os[i] = no[i - g]; oe[i] = ne[i - g]; }
+      for (int i = g; i < ge; ++i) { os[i] = gos; oe[i] = ne[i - g]; }
     }
   for (int i = 0; i < R; ++i) {
-    const int as = as_[i];
-    int ae = ae_[i];
-    // row 0's pad cells are inside the envelope (unless they are past the last column): the sweep computes them
-    if (i == 0) ae = std::min(oe[0], Cc - 1);
+    const int as = i + lo[i];
+    int ae = i + hi[i];
+    // the Forward sweep's row 0: its pad cells are inside the envelope (unless they are past the last column), it computes them
+    if (!mirrored && i == 0) ae = std::min(oe[0], Cc - 1);
     // where the strip's cells live: slot(i, k) = strip_store[q] + 2 (i % 64) + (k >> 1) blk + (k & 1)
     const int q = i >> 6;
     int64_t A;
@@ -454,12 +472,13 @@ bool build_band_rows(const int32_t* xenv, const int32_t* yenv, const uint8_t* xf
     if (have[q] && strip_store[q] != (int32_t)A) return false;
     have[q] = 1;
     strip_store[q] = (int32_t)A;
-    const bool ready = (xf[i] & F_READY) || x_empty;
+    const int ic = mirrored ? R - 1 - i : i;                          // the actual x state of the row
+    const bool ready = (xf[ic] & F_READY) || x_empty;
     int32_t* o = &out[2 * (size_t)i];
     if (oe[i] - os[i] > 0xFFFF || os[i] >= 0xFFFF) return false;
     o[0] = os[i] | ((oe[i] - os[i]) << 16);
     if (as - os[i] > 7 || oe[i] - ae > 7 || as < os[i] || ae > oe[i]) return false;
-    o[1] = (xecls[i] & 0xFF) | (ready ? 0 : 0x100) | ((as - os[i]) << 9) | ((oe[i] - ae) << 12);
+    o[1] = (xecls[mirrored ? ic + 1 : ic] & 0xFF) | (ready ? 0 : 0x100) | ((as - os[i]) << 9) | ((oe[i] - ae) << 12);
     n_steps = std::max(n_steps, oe[i] + 1);
   }
   // a lane must be idle for at least one whole step pair between two rows (its register window restarts from zero cells),
@@ -469,14 +488,28 @@ bool build_band_rows(const int32_t* xenv, const int32_t* yenv, const uint8_t* xf
   // the largest slot must fit the converting wave's 32-bit slot
   if ((int64_t)n_steps / 2 * blk + INT32_MAX / 2 > INT32_MAX) return false;
   for (int i = R; i < R + 64; ++i) out[2 * (size_t)i] = 0xFFFF;    // sentinels: never owned
+  return true;
+}
+
+// The Forward sweep.
+bool build_band_rows(const int32_t* xenv, const int32_t* yenv, const uint8_t* xf, const uint8_t* yf, const int32_t* xecls,
+                     bool x_empty, int R, int Cc, int band, int64_t ss, int blk, const int32_t* cwin, const int64_t* cbase,
+                     std::vector<int32_t>& out, int& n_steps) {
+  if (R < 2 || Cc < 2 || R + Cc > 60000) return false;
+  std::vector<int> lo, hi;
+  if (!band_spans(xenv, yenv, xf, yf, R, Cc, band, false, lo, hi)) return false;
+  lo[0] = 0;
+  hi[0] = std::max(hi[0], hi[1]);      // row 1 reads row 0 up to its own last column (row 0 is in the envelope throughout)
+  for (int i = 0; i < R; ++i) if (hi[i] >= Cc - 2) hi[i] = Cc - 1;   // the cells next to the band in the always-in column
+  if (!encode_band_rows(lo, hi, false, xf, xecls, x_empty, R, Cc, ss, blk, cwin, cbase, out, n_steps)) return false;
   n_steps = (n_steps + 1) & ~1;
   return true;
 }
 
-// The same for the Backward sweep of hx_band.hip, in mirrored coordinates i' = R-1-i, j' = Cc-1-j (the layout of the
-// Backward matrix).  What is always inside the envelope is now the LAST row (x START) and the FIRST column (the y state
-// feeding END): both are -inf away from the band (see below), written by the kernel's second wave; the sweep owns a row's band
-// cells, widened to column 0 where the band touches it, and on the last row from where the row above's band begins.
+// The Backward sweep of hx_band.hip, in mirrored coordinates i' = R-1-i, j' = Cc-1-j (the layout of the Backward matrix).
+// What is always inside the envelope is now the LAST row (x START) and the FIRST column (the y state feeding END): both are
+// -inf away from the band (see below), written by the kernel's second wave; the sweep owns a row's band cells, widened to
+// column 0 where the band touches it, and on the last row from where the row above's band begins.
 //   x = first owned step | (owned steps - 1) << 16;  y = class of x state i + 1 | state i not ready << 8 | pads << 9, 12 (three bits each)
 // followed by the per-strip store bases (dense planes only) and, last, one int: the first column the sweep owns on the last
 // row (0: the whole row).
@@ -486,65 +519,13 @@ bool build_band_rows_bwd(const int32_t* xenv, const int32_t* yenv, const uint8_t
   // the y state that feeds END must not be ready (it has the null transition to END): then no x-absorbing move leaves a
   // cell of its column (reference src/forward.cpp:1041-1049), and the column and the last row are -inf away from the band
   if ((yf[Cc - 1] & F_READY) || y_empty) return false;
-  for (int i = 1; i <= R; ++i) if (xenv[i] < xenv[i - 1]) return false;
-  for (int j = 1; j <= Cc; ++j) if (yenv[j] < yenv[j - 1]) return false;
-  for (int i = 0; i < R; ++i) if (((xf[i] & F_EDGE) != 0) != (i == 0)) return false;
-  for (int j = 0; j < Cc; ++j) if (((yf[j] & F_EDGE) != 0) != (j == Cc - 1)) return false;
-  std::vector<int> lo(R), hi(R);          // mirrored rows, mirrored columns
-  {
-    int a = 0, b = -1;
-    for (int i = 0; i < R; ++i) {
-      while (a < Cc && (int64_t)yenv[a] < (int64_t)xenv[i] - band) ++a;
-      while (b + 1 < Cc && (int64_t)yenv[b + 1] <= (int64_t)xenv[i] + band) ++b;
-      if (b < a) return false;
-      lo[R - 1 - i] = Cc - 1 - b; hi[R - 1 - i] = Cc - 1 - a;
-    }
-  }
+  std::vector<int> lo, hi;                                         // mirrored rows, mirrored columns
+  if (!band_spans(xenv, yenv, xf, yf, R, Cc, band, true, lo, hi)) return false;
   for (int i = 0; i < R; ++i) if (lo[i] <= 1) lo[i] = 0;            // the cells next to the band in the always-in column
   hi[R - 1] = Cc - 1;
   lo[R - 1] = std::min(lo[R - 1], lo[R - 2]);                       // the last row reads the row above from where its band begins
-  const int n_strips = (R + HX_STRIP - 1) / HX_STRIP;
-  out.assign(2 * (size_t)(R + 64) + (size_t)n_strips + 4, 0);
-  int32_t* strip_store = &out[2 * (size_t)(R + 64)];
-  std::vector<int> os(R), oe(R);
-  n_steps = 0;
-  for (int i = 0; i < R; ++i) { os[i] = (i + lo[i]) & ~1; oe[i] = (i + hi[i]) | 1; }
-  // whole cache lines, as in build_band_rows: the four rows of a 64-byte group own the same steps.  What a row gains lies
-  // outside the envelope or - first column, last row away from the band - is -inf by the argument above, which is what the
-  // sweep stores for an owned cell outside its row's span.
-  if (!getenv("HX_BAND_NO_LINE_GROUPS"))
-    for (int g = 0; g < R; g += 4) {
-      const int ge = std::min(g + 4, R);
-      int gos = INT_MAX, goe = -1;
-      for (int i = g; i < ge; ++i) { gos = std::min(gos, os[i]); goe = std::max(goe, oe[i]); }
-      bool fits = true;
-      for (int i = g; i < ge; ++i) {
-        const int e = std::max(oe[i], std::min(goe, (i + Cc - 1) | 1));
-        if (i + lo[i] - gos > 7 || e - (i + hi[i]) > 7) fits = false;
-      }
-      if (!fits) continue;
-      for (int i = g; i < ge; ++i) { oe[i] = std::max(oe[i], std::min(goe, (i + Cc - 1) | 1)); os[i] = gos; }
-    }
-  for (int i = 0; i < R; ++i) {
-    const int as = i + lo[i], ae = i + hi[i];
-    const int q = i >> 6;
-    const int64_t A = (int64_t)q * ss - (int64_t)32 * q * blk;
-    if (A < INT32_MIN / 2 || A > INT32_MAX / 2) return false;
-    strip_store[q] = (int32_t)A;
-    const int ic = R - 1 - i;                                        // the actual x state of the row
-    const bool ready = (xf[ic] & F_READY) || x_empty;
-    int32_t* o = &out[2 * (size_t)i];
-    if (oe[i] - os[i] > 0xFFFF || os[i] >= 0xFFFF) return false;
-    o[0] = os[i] | ((oe[i] - os[i]) << 16);
-    if (as - os[i] > 7 || oe[i] - ae > 7) return false;
-    o[1] = (xecls[ic + 1] & 0xFF) | (ready ? 0 : 0x100) | ((as - os[i]) << 9) | ((oe[i] - ae) << 12);
-    n_steps = std::max(n_steps, oe[i] + 1);
-  }
-  for (int i = 0; i + 63 < R; ++i) if (os[i + 63] < oe[i] + 1) return false;
-  for (int i = 0; i + 64 < R; ++i) if (os[i + 64] < oe[i] + 3) return false;
-  if ((int64_t)n_steps / 2 * blk + INT32_MAX / 2 > INT32_MAX) return false;
-  for (int i = R; i < R + 64; ++i) out[2 * (size_t)i] = 0xFFFF;
-  out[2 * (size_t)(R + 64) + n_strips] = lo[R - 1];
+  if (!encode_band_rows(lo, hi, true, xf, xecls, x_empty, R, Cc, ss, blk, nullptr, nullptr, out, n_steps)) return false;
+  out[2 * (size_t)(R + 64) + (R + HX_STRIP - 1) / HX_STRIP] = lo[R - 1];
   n_steps = (n_steps + 1) & ~1;
   return true;
 }
@@ -580,6 +561,7 @@ struct hx_batch {
   int device = 0;
   int n_jobs = 0;
   uint32_t flags = 0;
+  Policy pol;                       // the arithmetic policy of `flags`
   std::vector<DevJob> jobs;         // host copies in the caller's job order (device pointers inside)
   std::vector<hx_layout> layouts;
   std::vector<int> order;           // class-ordered table position -> caller's job index
@@ -614,7 +596,6 @@ struct hx_batch {
   void* h_trace = nullptr;
   int64_t trace_cap = 0;
   bool trace_ties_valid = false;     // the near-tie flags of the last hx_batch_best_trace are in d_trace_n's third block
-  bool ev_valid[2] = {false, false};
 };
 
 namespace {
@@ -630,6 +611,24 @@ int publish_jobs(hx_batch* b) {
 int use_device(const hx_batch* b) {
   if (hipSetDevice(b->device) != hipSuccess) return fail(HX_ERR_HIP, "hipSetDevice(%d) failed", b->device);
   return HX_OK;
+}
+// The checks a batch reader starts with, in this order: its arguments (`args_ok`: the reader's own tests of its pointers,
+// sizes and `which`), the job index (`job`: null for a reader that takes none; every value of a reader's own job argument
+// is range-checked), and the fills it reads (`need`, with the message when one of them has not been launched).
+enum : unsigned { NEED_NONE = 0, NEED_FORWARD = 1, NEED_BACKWARD = 2 };
+int check_reader(const hx_batch* b, bool args_ok, const int32_t* job, unsigned need = NEED_NONE, const char* not_done = nullptr) {
+  if (!b || !args_ok) return fail(HX_ERR_INVALID_ARG, "bad arguments");
+  if (job && (*job < 0 || *job >= b->n_jobs)) return fail(HX_ERR_RANGE, "job %d out of range", *job);
+  if (((need & NEED_FORWARD) && !b->forward_done) || ((need & NEED_BACKWARD) && !b->backward_done))
+    return fail(HX_ERR_STATE, "%s", not_done);
+  return HX_OK;
+}
+// the fill a reader's `which` names (0 Forward, 1 Backward)
+unsigned need_fill(int32_t which) { return which == 0 ? NEED_FORWARD : NEED_BACKWARD; }
+// ... and then the batch's device, for a reader that goes to it right away
+int open_reader(const hx_batch* b, bool args_ok, const int32_t* job, unsigned need = NEED_NONE, const char* not_done = nullptr) {
+  const int rc = check_reader(b, args_ok, job, need, not_done);
+  return rc != HX_OK ? rc : use_device(b);
 }
 }  // namespace
 
@@ -720,347 +719,318 @@ int hx_shutdown(void) {
   return HX_OK;
 }
 
-static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs, uint32_t flags, hx_batch** out) {
-  if (!out) return fail(HX_ERR_INVALID_ARG, "out is null");
-  *out = nullptr;
-  if (device < 0 || device >= HX_MAX_DEVICES || !g_dev[device].ready)
-    return fail(HX_ERR_NOT_INITIALIZED, "hx_init has not been called for device %d", device);
-  if (!jobs || n_jobs <= 0) return fail(HX_ERR_INVALID_ARG, "need at least one job");
-  HIP_TRY(hipSetDevice(device));
-  const bool timing = getenv("HX_TIMING_CREATE") != nullptr;
-  const auto tick = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tc0 = tick();
+}  // extern "C"
 
-  hx_batch* b = new (std::nothrow) hx_batch;
-  if (!b) return fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed");
-  b->device = device;
-  b->n_jobs = n_jobs;
-  b->flags = flags;
-  b->jobs.resize(n_jobs);
-  b->layouts.resize(n_jobs);
+namespace {
+// ---- the steps of hx_batch_create ----
 
-  Arena ar;
-  std::vector<JobOff> offs(n_jobs);
-  std::vector<int64_t> mat_off(n_jobs);
-  std::vector<int> kclass(n_jobs);
-  int64_t eplane_total = 0;
-  int rc = HX_OK;
+// Validates job k and puts its profiles and model into the staging image.
+int flatten_job(const hx_pair_job& pj, int k, Arena& ar, JobOff& jo) {
+  const hx_hmm* h = pj.hmm;
+  if (!h || !pj.x || !pj.y) return fail(HX_ERR_INVALID_ARG, "job %d has null members", k);
+  const int A = h->alph_size, C = h->components, CA = A * C;
+  if (A <= 0 || C <= 0) return fail(HX_ERR_INVALID_ARG, "job %d: bad alphabet/components", k);
+  if (!h->log_root || !h->log_sub_l || !h->log_sub_r || !h->log_ins_l || !h->log_ins_r || !h->log_cptw_l || !h->log_cptw_r)
+    return fail(HX_ERR_INVALID_ARG, "job %d: null hmm arrays", k);
+  const bool need_env = pj.max_distance >= 0;
+  int rc;
+  if ((rc = flatten_profile(pj.x, CA, need_env, false, ar, jo.x)) != HX_OK) return rc;
+  if ((rc = flatten_profile(pj.y, CA, need_env, true, ar, jo.y)) != HX_OK) return rc;
+  jo.log_root = ar.put(h->log_root, sizeof(double) * CA);
+  jo.log_sub_l = ar.put(h->log_sub_l, sizeof(double) * CA * A);
+  jo.log_sub_r = ar.put(h->log_sub_r, sizeof(double) * CA * A);
+  jo.log_ins_l = ar.put(h->log_ins_l, sizeof(double) * CA);
+  jo.log_ins_r = ar.put(h->log_ins_r, sizeof(double) * CA);
+  jo.log_cptw_l = ar.put(h->log_cptw_l, sizeof(double) * C);
+  jo.log_cptw_r = ar.put(h->log_cptw_r, sizeof(double) * C);
+  const int64_t pairs = (int64_t)jo.x.n_cls * jo.y.n_cls;
+  jo.table_emission = pairs > 0 && pairs <= (1 << 16);
+  jo.emis = jo.table_emission ? ar.reserve(sizeof(double) * pairs) : 0;
+  jo.emis_pad = jo.table_emission ? ar.reserve(sizeof(double) * (jo.x.n_cls + 1) * (jo.y.n_cls + 1)) : 0;
+  jo.fwd_windows = jo.bwd_windows = jo.strip_base = jo.yword = jo.yword_bwd = jo.band_rows = jo.band_rows_bwd = 0;
+  jo.compressed = false;
+  jo.compact_plane = 0;
+  return HX_OK;
+}
+
+// The kernel class of a flattened job, before plan_band_sweep may move it to KC_LEAF_ROT_BANDED.
+int choose_class(JobOff& jo, bool need_env, uint32_t flags) {
   static const bool force_dag = getenv("HX_FORCE_DAG") != nullptr;   // tuning hook: the general pipeline for chain profiles too
-  const bool band_old = getenv("HX_BAND_OLD") != nullptr;             // tuning / test hook: banded leaf pairs on the strip pipelines
-  const bool linear = (flags & HX_LSE_LINEAR) == HX_LSE_LINEAR;
-  for (int k = 0; k < n_jobs && rc == HX_OK; ++k) {
-    const hx_pair_job& pj = jobs[k];
-    const hx_hmm* h = pj.hmm;
-    if (!h || !pj.x || !pj.y) { rc = fail(HX_ERR_INVALID_ARG, "job %d has null members", k); break; }
-    const int A = h->alph_size, C = h->components, CA = A * C;
-    if (A <= 0 || C <= 0) { rc = fail(HX_ERR_INVALID_ARG, "job %d: bad alphabet/components", k); break; }
-    if (!h->log_root || !h->log_sub_l || !h->log_sub_r || !h->log_ins_l || !h->log_ins_r || !h->log_cptw_l || !h->log_cptw_r) {
-      rc = fail(HX_ERR_INVALID_ARG, "job %d: null hmm arrays", k);
-      break;
-    }
-    const bool need_env = pj.max_distance >= 0;
-    JobOff& jo = offs[k];
-    if ((rc = flatten_profile(pj.x, CA, need_env, false, ar, jo.x)) != HX_OK) break;
-    if ((rc = flatten_profile(pj.y, CA, need_env, true, ar, jo.y)) != HX_OK) break;
-    jo.log_root = ar.put(h->log_root, sizeof(double) * CA);
-    jo.log_sub_l = ar.put(h->log_sub_l, sizeof(double) * CA * A);
-    jo.log_sub_r = ar.put(h->log_sub_r, sizeof(double) * CA * A);
-    jo.log_ins_l = ar.put(h->log_ins_l, sizeof(double) * CA);
-    jo.log_ins_r = ar.put(h->log_ins_r, sizeof(double) * CA);
-    jo.log_cptw_l = ar.put(h->log_cptw_l, sizeof(double) * C);
-    jo.log_cptw_r = ar.put(h->log_cptw_r, sizeof(double) * C);
-    const int64_t pairs = (int64_t)jo.x.n_cls * jo.y.n_cls;
-    jo.table_emission = pairs > 0 && pairs <= (1 << 16);
-    jo.emis = jo.table_emission ? ar.reserve(sizeof(double) * pairs) : 0;
-    jo.emis_pad = jo.table_emission ? ar.reserve(sizeof(double) * (jo.x.n_cls + 1) * (jo.y.n_cls + 1)) : 0;
-    jo.fwd_windows = jo.bwd_windows = jo.strip_base = jo.yword = jo.yword_bwd = jo.band_rows = jo.band_rows_bwd = 0;
-    jo.compressed = false;
-    jo.compact_plane = 0;
+  jo.chain = jo.x.chain && jo.y.chain;
+  jo.leaf_like = jo.chain && jo.x.interior_emit && jo.y.interior_emit && jo.table_emission;
+  // y side small enough for LDS (hx_chain.hip HX_YL_*, hx_linear.hip) and all its transitions have lpTrans 0
+  const bool ylds = jo.leaf_like && jo.y.lp_zero && jo.y.n <= 6144 && jo.y.n_cls + 1 <= 64 && jo.x.n_cls < 255 &&
+                    (int64_t)(jo.x.n_cls + 1) * (jo.y.n_cls + 1) <= 1024;
+  if (flags & HX_FORCE_GENERIC) return KC_GENERIC;
+  if (force_dag || !jo.chain) return need_env ? KC_DAG_BANDED : KC_DAG;
+  if (ylds) return need_env ? KC_LEAF_LDS_BANDED : KC_LEAF_LDS;
+  if (jo.leaf_like) return need_env ? KC_LEAF_BANDED : KC_LEAF;
+  return need_env ? KC_CHAIN_BANDED : KC_CHAIN;
+}
 
-    // ---- kernel class of the job ----
-    const bool chain = jo.x.chain && jo.y.chain;
-    const bool leaf_like = chain && jo.x.interior_emit && jo.y.interior_emit && jo.table_emission;
-    // y side small enough for LDS (hx_chain.hip HX_YL_*, hx_linear.hip) and all its transitions have lpTrans 0
-    const bool ylds = leaf_like && jo.y.lp_zero && jo.y.n <= 6144 && jo.y.n_cls + 1 <= 64 && jo.x.n_cls < 255 &&
-                      (int64_t)(jo.x.n_cls + 1) * (jo.y.n_cls + 1) <= 1024;
-    int kc;
-    if (flags & HX_FORCE_GENERIC) kc = KC_GENERIC;
-    else if (force_dag || !chain) kc = need_env ? KC_DAG_BANDED : KC_DAG;
-    else if (ylds) kc = need_env ? KC_LEAF_LDS_BANDED : KC_LEAF_LDS;
-    else if (leaf_like) kc = need_env ? KC_LEAF_BANDED : KC_LEAF;
-    else kc = need_env ? KC_CHAIN_BANDED : KC_CHAIN;
-    kclass[k] = kc;
-    if ((flags & HX_BAND_COMPRESSED) && (kc >= KC_DAG || (flags & HX_KEEP_BACKWARD))) {
-      rc = fail(HX_ERR_INVALID_ARG, "HX_BAND_COMPRESSED is implemented by the Forward fills of chain (leaf) profiles only: "
-                                    "no general profiles (job %d), no HX_KEEP_BACKWARD / HX_FORCE_GENERIC", k);
-      break;
-    }
+// (copies of staged host data: put() may reallocate the staging image the pointers would point into)
+std::vector<uint8_t> staged_flags(const Arena& ar, const ProfOff& o) {
+  return std::vector<uint8_t>(ar.host.data() + o.flags, ar.host.data() + o.flags + o.n);
+}
+std::vector<int32_t> staged_ecls(const Arena& ar, const ProfOff& o) {
+  const int32_t* p = reinterpret_cast<const int32_t*>(ar.host.data() + o.ecls);
+  return std::vector<int32_t>(p, p + o.n);
+}
 
-    if (linear && (kc == KC_LEAF_LDS || kc == KC_LEAF_LDS_BANDED) && jo.y.n >= 2) {
-      // per-column words of the banded scaled-probability fill (hx_linear.hip): {emission class : 8, not ready : 1,
-      // always in envelope : 1, envelope coordinate : 22}, with 64 words of padding on either side (the edge columns').
-      const int Cc = jo.y.n - 1;
-      const std::vector<uint8_t> yf(ar.host.data() + jo.y.flags, ar.host.data() + jo.y.flags + jo.y.n);
-      const std::vector<int32_t> ecls(reinterpret_cast<const int32_t*>(ar.host.data() + jo.y.ecls),
-                                      reinterpret_cast<const int32_t*>(ar.host.data() + jo.y.ecls) + jo.y.n);
-      std::vector<uint32_t> yw((size_t)Cc + 328);     // (the kernel refills its word ring 64 words at a time, up to 256 ahead)
-      for (int jp = 0; jp < Cc + 328; ++jp) {
-        const int j = jp < 64 ? 0 : (jp - 64 >= Cc ? Cc - 1 : jp - 64);
-        const bool ready = (yf[j] & F_READY) || jo.y.empty;
-        const uint32_t env = (need_env && pj.y->env_pos) ? (uint32_t)pj.y->env_pos[j] : 0u;
-        yw[jp] = (uint32_t)ecls[j] | (ready ? 0u : 0x100u) | ((yf[j] & F_EDGE) ? 0x200u : 0u) | (env << 10);
-      }
-      jo.yword = ar.put(yw.data(), sizeof(uint32_t) * yw.size());
-      // Backward: sweep column j is y state jc = Cc-1-j; its own readiness, edge flag and envelope coordinate, and the
-      // emission class of state jc+1
-      for (int jp = 0; jp < Cc + 328; ++jp) {
-        const int j = jp < 64 ? 0 : (jp - 64 >= Cc ? Cc - 1 : jp - 64), jc = Cc - 1 - j;
-        const bool ready = (yf[jc] & F_READY) || jo.y.empty;
-        const uint32_t env = (need_env && pj.y->env_pos) ? (uint32_t)pj.y->env_pos[jc] : 0u;
-        yw[jp] = (uint32_t)ecls[jc + 1] | (ready ? 0u : 0x100u) | ((yf[jc] & F_EDGE) ? 0x200u : 0u) | (env << 10);
-      }
-      jo.yword_bwd = ar.put(yw.data(), sizeof(uint32_t) * yw.size());
-    }
-    std::vector<int32_t> cwin_keep;
-    std::vector<int64_t> cbase_keep;
-    if (need_env) {
-      const int R = jo.x.n - 1, Cc = jo.y.n - 1;
-      // (copies: put() may reallocate the staging image the pointers would point into)
-      const std::vector<uint8_t> xf(ar.host.data() + jo.x.flags, ar.host.data() + jo.x.flags + jo.x.n);
-      const std::vector<uint8_t> yf(ar.host.data() + jo.y.flags, ar.host.data() + jo.y.flags + jo.y.n);
-      const std::vector<int32_t> wf = strip_windows(xf.data(), pj.x->env_pos, yf.data(), pj.y->env_pos, R, Cc, pj.max_distance, false);
-      const std::vector<int32_t> wb = strip_windows(xf.data(), pj.x->env_pos, yf.data(), pj.y->env_pos, R, Cc, pj.max_distance, true);
-      jo.bwd_windows = ar.put(wb.data(), sizeof(int32_t) * wb.size());
-      if (flags & HX_BAND_COMPRESSED) {
-        // Band-compressed storage: a strip keeps only the step windows it sweeps.  The windows are put into the
-        // form the fill uses them in (whole step pairs, clipped, merged when they touch - k_fill_leaf_linear),
-        // which that kernel's own widening leaves unchanged, and every window gets its offset in the state plane.
-        std::vector<int32_t> we(wf);
-        const int n_strips = (R + HX_STRIP - 1) / HX_STRIP, nsteps = (Cc + HX_STRIP) & ~1;
-        std::vector<int64_t> sb(2 * (size_t)n_strips, 0);
-        int64_t off = 0;
-        for (int s = 0; s < n_strips; ++s) {
-          int32_t* o = &we[4 * (size_t)s];
-          int lo[2], hi[2];
-          for (int w = 0; w < 2; ++w) {
-            lo[w] = o[2 * w] & ~1;
-            const int hh = (o[2 * w + 1] + 1) & ~1;
-            hi[w] = hh < nsteps ? hh : nsteps;
-            if (hi[w] < lo[w]) hi[w] = lo[w];
-          }
-          if (hi[1] > lo[1] && lo[1] <= hi[0]) { hi[0] = std::max(hi[0], hi[1]); lo[1] = hi[1] = 0; }
-          for (int w = 0; w < 2; ++w) {
-            o[2 * w] = lo[w]; o[2 * w + 1] = hi[w];
-            sb[2 * (size_t)s + w] = off;
-            off += (int64_t)((hi[w] - lo[w]) >> 1) * (2 * HX_STRIP);
-          }
-        }
-        jo.fwd_windows = ar.put(we.data(), sizeof(int32_t) * we.size());
-        jo.strip_base = ar.put(sb.data(), sizeof(int64_t) * sb.size());
-        cwin_keep = we; cbase_keep = sb;
-        jo.compressed = true;
-        jo.compact_plane = (off + 1) & ~(int64_t)1;
-      } else {
-        jo.fwd_windows = ar.put(wf.data(), sizeof(int32_t) * wf.size());
-      }
-    }
-
-    DevJob& J = b->jobs[k];
-    memset(&J, 0, sizeof(J));
-    for (int s = 0; s < 5; ++s)
-      for (int d = 0; d < 6; ++d) J.T[s][d] = h->lp_trans[s][d];
-    J.A = A; J.C = C; J.CA = CA;
-    J.max_dist = pj.max_distance;
-    J.n_rows = jo.x.n - 1;
-    J.n_cols = jo.y.n - 1;
-    J.n_strips = (J.n_rows + HX_STRIP - 1) / HX_STRIP;
-    J.strip_stride = strip_stride_for(J.n_cols);
-    J.plane = jo.compressed ? jo.compact_plane : J.n_strips * J.strip_stride;
-    J.chain = chain;
-    J.leaf_like = leaf_like;
-    hx_layout& L = b->layouts[k];
-    L.n_rows = J.n_rows; L.n_cols = J.n_cols; L.strip_rows = HX_STRIP; L.n_strips = J.n_strips;
-    J.blk = 2 * HX_STRIP; J.matrix_doubles = 5 * J.plane;
-    // Unbanded leaf pairs of the scaled-probability fills keep the five states of a step pair adjacent: a wavefront then
-    // writes 5 KiB contiguous per iteration instead of 1 KiB into each of five planes (hx_linear.hip; same total size).
-    // Only those kernels and the layout-aware readers ever see such a job.
-    if (linear && kc == KC_LEAF_LDS && !getenv("HX_PLANAR_LAYOUT")) {
-      J.strip_stride *= 5; J.plane = 2 * HX_STRIP; J.blk = 10 * HX_STRIP;
-    }
-    if (kc == KC_LEAF_LDS_BANDED && jo.x.lp_zero && !band_old) {
-      // the banded rotating-row sweep (hx_band.hip), when the pair satisfies its assumptions and its sides fit LDS
-      const int pol = linear ? ((flags & HX_LSE_TRUNC) == HX_LSE_TRUNC ? 3 : 0) : ((flags & HX_LSE_FAST) ? 1 : 2);
-      std::vector<int32_t> rows;
-      int n_steps = 0;
-      const std::vector<uint8_t> xf(ar.host.data() + jo.x.flags, ar.host.data() + jo.x.flags + jo.x.n);
-      const std::vector<uint8_t> yf(ar.host.data() + jo.y.flags, ar.host.data() + jo.y.flags + jo.y.n);
-      const std::vector<int32_t> xecls(reinterpret_cast<const int32_t*>(ar.host.data() + jo.x.ecls),
-                                       reinterpret_cast<const int32_t*>(ar.host.data() + jo.x.ecls) + jo.x.n);
-      // Band-compressed planes of such a pair need not hold the always-in-envelope column (the y state feeding END) away
-      // from the band: below row 1 those cells are -inf (no x-absorbing move enters that column from a cell that is not
-      // itself in it, and the column's only finite cell off the band is (1, Ny-2): see hx_band.hip), and a cell that is not
-      // stored reads as -inf (hx_batch_read_cells, the traceback, lpEnd).  A strip's second window is that column whenever
-      // it is apart from the band's window, which also says that no row of the strip has a band that reaches it.  Without
-      // those windows a pair's planes are about half the size, and the fill no longer writes 5 x 8 bytes of -inf into a
-      // cache line of its own for every row (a fifth of the sweep's time at 4096 pairs).
-      std::vector<int32_t> twin;
-      std::vector<int64_t> tbase;
-      int64_t tplane = 0;
-      if (jo.compressed) {
-        twin = cwin_keep;
-        const int n_strips = (J.n_rows + HX_STRIP - 1) / HX_STRIP;
-        tbase.assign(2 * (size_t)n_strips, 0);
-        int64_t off = 0;
-        for (int q = 0; q < n_strips; ++q) {
-          int32_t* o = &twin[4 * (size_t)q];
-          if (q >= 1 && o[3] > o[2]) o[2] = o[3] = 0;
-          for (int w = 0; w < 2; ++w) {
-            tbase[2 * (size_t)q + w] = off;
-            off += (int64_t)((o[2 * w + 1] - o[2 * w]) >> 1) * (2 * HX_STRIP);
-          }
-        }
-        tplane = (off + 1) & ~(int64_t)1;
-      }
-      const bool fits = band_kernel_fits(pol, J.n_rows, J.n_cols, std::max(jo.x.n_cls, jo.y.n_cls));
-      bool trimmed = fits && jo.compressed && !getenv("HX_BAND_KEEP_EDGE_COLUMN") &&
-                     build_band_rows(pj.x->env_pos, pj.y->env_pos, xf.data(), yf.data(), xecls.data(), jo.x.empty != 0, J.n_rows, J.n_cols,
-                                     pj.max_distance, J.strip_stride, J.blk, twin.data(), tbase.data(), rows, n_steps);
-      if (trimmed) {
-        jo.fwd_windows = ar.put(twin.data(), sizeof(int32_t) * twin.size());
-        jo.strip_base = ar.put(tbase.data(), sizeof(int64_t) * tbase.size());
-        jo.compact_plane = tplane;
-        J.plane = tplane;
-        J.matrix_doubles = 5 * J.plane;
-      }
-      if (trimmed ||
-          (fits &&
-          build_band_rows(pj.x->env_pos, pj.y->env_pos, xf.data(), yf.data(), xecls.data(), jo.x.empty != 0, J.n_rows, J.n_cols,
-                          pj.max_distance, J.strip_stride, J.blk, jo.compressed ? cwin_keep.data() : nullptr,
-                          jo.compressed ? cbase_keep.data() : nullptr, rows, n_steps))) {
-        // the Backward sweep of the same kernel (dense planes: band-compressed batches have no Backward).  A pair the
-        // Backward sweep cannot take (fewer than three rows or columns) stays out of the class altogether, so that the
-        // class never falls back to the strip pipeline because of one such pair.
-        std::vector<int32_t> rows_b;
-        int n_steps_b = 0;
-        const bool bwd_ok = jo.compressed ||
-            build_band_rows_bwd(pj.x->env_pos, pj.y->env_pos, xf.data(), yf.data(), xecls.data(), jo.x.empty != 0, jo.y.empty != 0, J.n_rows, J.n_cols,
-                                pj.max_distance, J.strip_stride, J.blk, rows_b, n_steps_b);
-        if (bwd_ok) {
-          jo.band_rows = ar.put(rows.data(), sizeof(int32_t) * rows.size());
-          J.band_steps = n_steps;
-          kc = kclass[k] = KC_LEAF_ROT_BANDED;
-          // two pairs per wavefront (hx_band2.hip): a lane is a row modulo 32 there, so rows i and i + 31 must never be alive
-          // together and a lane must be idle for a whole step pair between rows i and i + 32 - the conditions build_band_rows
-          // checks for 63 / 64, on both sweeps' records
-          auto ring32 = [&](const std::vector<int32_t>& rec) {
-            auto first = [&](int i) { return rec[2 * (size_t)i] & 0xFFFF; };
-            auto last = [&](int i) { return (rec[2 * (size_t)i] & 0xFFFF) + ((rec[2 * (size_t)i] >> 16) & 0xFFFF); };
-            for (int i = 0; i + 31 < J.n_rows; ++i) if (first(i + 31) < last(i) + 1) return false;
-            for (int i = 0; i + 32 < J.n_rows; ++i) if (first(i + 32) < last(i) + 3) return false;
-            return true;
-          };
-          J.band_w32 = (J.blk == 2 * HX_STRIP && ring32(rows) && (jo.compressed || ring32(rows_b)) &&
-                        band2_kernel_fits(J.n_rows, J.n_cols, std::max(jo.x.n_cls, jo.y.n_cls))) ? 1 : 0;
-          J.band_steps_bwd = 0;
-          if (!jo.compressed) {
-            jo.band_rows_bwd = ar.put(rows_b.data(), sizeof(int32_t) * rows_b.size());
-            J.band_steps_bwd = n_steps_b;
-          }
-        }
-      }
-    }
-    L.strip_stride = J.strip_stride; L.plane_stride = J.plane;
-    L.block_stride = J.blk; L.matrix_doubles = J.matrix_doubles;
-    L.mirrored = 0; L.compressed = jo.compressed ? 1 : 0;
-    b->any_compressed = b->any_compressed || jo.compressed;
-    jo.eplane_off = -1;
-    if (!jo.table_emission) {   // (also for a profile without emitting states: the pipeline's loads are unconditional)
-      jo.eplane_off = eplane_total;
-      eplane_total += J.plane;
-      if (J.plane > b->max_eplane) b->max_eplane = J.plane;
-    }
-    b->total_cells += (int64_t)J.n_rows * J.n_cols;
-    if (jo.x.n > b->max_states) b->max_states = jo.x.n;
-    if (jo.y.n > b->max_states) b->max_states = jo.y.n;
-    if (jo.x.n_cls > b->max_cls) b->max_cls = jo.x.n_cls;
-    if (jo.y.n_cls > b->max_cls) b->max_cls = jo.y.n_cls;
-    if (CA > b->max_ca) b->max_ca = CA;
-    if (jo.table_emission && pairs > b->max_cls_pairs) b->max_cls_pairs = (int)pairs;
-    ClassRange& cr = b->cls[kc];
-    cr.n++;
-    if (kc == KC_LEAF_ROT_BANDED && J.band_w32) cr.n_w32++;
-    if (J.n_rows > cr.max_rows) cr.max_rows = J.n_rows;
-    if (J.n_cols > cr.max_cols) cr.max_cols = J.n_cols;
-    if (jo.x.n_cls > cr.max_cls) cr.max_cls = jo.x.n_cls;
-    if (jo.y.n_cls > cr.max_cls) cr.max_cls = jo.y.n_cls;
-    if (((jo.y.n + 3) & ~3) > cr.yl_cols) cr.yl_cols = (jo.y.n + 3) & ~3;
-    const int ep = ((jo.x.n_cls + 1) * (jo.y.n_cls + 1) + 1) & ~1;
-    if (ep > cr.yl_emis) cr.yl_emis = ep;
+// Per-column words of the banded scaled-probability fill (hx_linear.hip): {emission class : 8, not ready : 1, always in
+// envelope : 1, envelope coordinate : 22}, with 64 words of padding on either side (the edge columns').
+void put_ywords(Arena& ar, JobOff& jo, const hx_pair_job& pj) {
+  const bool need_env = pj.max_distance >= 0;
+  const int Cc = jo.y.n - 1;
+  const std::vector<uint8_t> yf = staged_flags(ar, jo.y);
+  const std::vector<int32_t> ecls = staged_ecls(ar, jo.y);
+  std::vector<uint32_t> yw((size_t)Cc + 328);     // (the kernel refills its word ring 64 words at a time, up to 256 ahead)
+  for (int jp = 0; jp < Cc + 328; ++jp) {
+    const int j = jp < 64 ? 0 : (jp - 64 >= Cc ? Cc - 1 : jp - 64);
+    const bool ready = (yf[j] & F_READY) || jo.y.empty;
+    const uint32_t env = (need_env && pj.y->env_pos) ? (uint32_t)pj.y->env_pos[j] : 0u;
+    yw[jp] = (uint32_t)ecls[j] | (ready ? 0u : 0x100u) | ((yf[j] & F_EDGE) ? 0x200u : 0u) | (env << 10);
   }
-  if (rc != HX_OK) { delete b; return rc; }
+  jo.yword = ar.put(yw.data(), sizeof(uint32_t) * yw.size());
+  // Backward: sweep column j is y state jc = Cc-1-j; its own readiness, edge flag and envelope coordinate, and the
+  // emission class of state jc+1
+  for (int jp = 0; jp < Cc + 328; ++jp) {
+    const int j = jp < 64 ? 0 : (jp - 64 >= Cc ? Cc - 1 : jp - 64), jc = Cc - 1 - j;
+    const bool ready = (yf[jc] & F_READY) || jo.y.empty;
+    const uint32_t env = (need_env && pj.y->env_pos) ? (uint32_t)pj.y->env_pos[jc] : 0u;
+    yw[jp] = (uint32_t)ecls[jc + 1] | (ready ? 0u : 0x100u) | ((yf[jc] & F_EDGE) ? 0x200u : 0u) | (env << 10);
+  }
+  jo.yword_bwd = ar.put(yw.data(), sizeof(uint32_t) * yw.size());
+}
 
-  // class-ordered job table and matrix allocation (stable within a class)
-  // The general-profile classes need scratch planes next to the matrices: the five outgoing sums of every cell
-  // (hx_dag.hip), or - HX_LSE_LINEAR, when every such job's planes fit 32-bit byte offsets - the cells in the
-  // scaled-probability fill's own format (hx_daglin.hip).
-  // (General profiles under the truncating policy run as HX_LSE_FAST, which truncates as the reference does.  The scaled-
-  // probability pipeline of hx_daglin.hip with truncating sums was built and withdrawn in round 3: it sums a state's fourth and
-  // further in-transitions out of the reference's order, and with truncation the order of a sum matters at the 4.5e-5 level -
-  // cells downstream of such a state moved by up to 6e-5 where the leaf kernels hold 1e-7.)
-  b->dag_linear = (flags & HX_LSE_LINEAR) == HX_LSE_LINEAR && (flags & HX_LSE_TRUNC) != HX_LSE_TRUNC && !(flags & HX_FORCE_GENERIC);
+// The step windows of a banded job's strips (strip_windows), Forward and Backward.  Band-compressed storage: a strip keeps
+// only the step windows it sweeps.  The windows are put into the form the fill uses them in (whole step pairs, clipped,
+// merged when they touch - k_fill_leaf_linear), which that kernel's own widening leaves unchanged, and every window gets
+// its offset in the state plane; cwin / cbase receive them.
+void put_windows(Arena& ar, JobOff& jo, const hx_pair_job& pj, uint32_t flags, std::vector<int32_t>& cwin,
+                 std::vector<int64_t>& cbase) {
+  const int R = jo.x.n - 1, Cc = jo.y.n - 1;
+  const std::vector<uint8_t> xf = staged_flags(ar, jo.x), yf = staged_flags(ar, jo.y);
+  const std::vector<int32_t> wf = strip_windows(xf.data(), pj.x->env_pos, yf.data(), pj.y->env_pos, R, Cc, pj.max_distance, false);
+  const std::vector<int32_t> wb = strip_windows(xf.data(), pj.x->env_pos, yf.data(), pj.y->env_pos, R, Cc, pj.max_distance, true);
+  jo.bwd_windows = ar.put(wb.data(), sizeof(int32_t) * wb.size());
+  if (!(flags & HX_BAND_COMPRESSED)) {
+    jo.fwd_windows = ar.put(wf.data(), sizeof(int32_t) * wf.size());
+    return;
+  }
+  std::vector<int32_t> we(wf);
+  const int n_strips = (R + HX_STRIP - 1) / HX_STRIP, nsteps = (Cc + HX_STRIP) & ~1;
+  std::vector<int64_t> sb(2 * (size_t)n_strips, 0);
+  int64_t off = 0;
+  for (int s = 0; s < n_strips; ++s) {
+    int32_t* o = &we[4 * (size_t)s];
+    int lo[2], hi[2];
+    for (int w = 0; w < 2; ++w) {
+      lo[w] = o[2 * w] & ~1;
+      const int hh = (o[2 * w + 1] + 1) & ~1;
+      hi[w] = hh < nsteps ? hh : nsteps;
+      if (hi[w] < lo[w]) hi[w] = lo[w];
+    }
+    if (hi[1] > lo[1] && lo[1] <= hi[0]) { hi[0] = std::max(hi[0], hi[1]); lo[1] = hi[1] = 0; }
+    for (int w = 0; w < 2; ++w) {
+      o[2 * w] = lo[w]; o[2 * w + 1] = hi[w];
+      sb[2 * (size_t)s + w] = off;
+      off += (int64_t)((hi[w] - lo[w]) >> 1) * (2 * HX_STRIP);
+    }
+  }
+  jo.fwd_windows = ar.put(we.data(), sizeof(int32_t) * we.size());
+  jo.strip_base = ar.put(sb.data(), sizeof(int64_t) * sb.size());
+  cwin = we; cbase = sb;
+  jo.compressed = true;
+  jo.compact_plane = (off + 1) & ~(int64_t)1;
+}
+
+// The device record and the caller's layout of a job.  interleaved: the five states of a step pair adjacent.
+void init_job(DevJob& J, hx_layout& L, const JobOff& jo, const hx_pair_job& pj, bool interleaved) {
+  const hx_hmm* h = pj.hmm;
+  memset(&J, 0, sizeof(J));
+  for (int s = 0; s < 5; ++s)
+    for (int d = 0; d < 6; ++d) J.T[s][d] = h->lp_trans[s][d];
+  J.A = h->alph_size; J.C = h->components; J.CA = J.A * J.C;
+  J.max_dist = pj.max_distance;
+  J.n_rows = jo.x.n - 1;
+  J.n_cols = jo.y.n - 1;
+  J.n_strips = (J.n_rows + HX_STRIP - 1) / HX_STRIP;
+  J.strip_stride = strip_stride_for(J.n_cols);
+  J.plane = jo.compressed ? jo.compact_plane : J.n_strips * J.strip_stride;
+  J.chain = jo.chain;
+  J.leaf_like = jo.leaf_like;
+  L.n_rows = J.n_rows; L.n_cols = J.n_cols; L.strip_rows = HX_STRIP; L.n_strips = J.n_strips;
+  J.blk = 2 * HX_STRIP; J.matrix_doubles = 5 * J.plane;
+  if (interleaved) { J.strip_stride *= 5; J.plane = 2 * HX_STRIP; J.blk = 10 * HX_STRIP; }
+}
+
+// Two pairs per wavefront (hx_band2.hip): a lane is a row modulo 32 there, so rows i and i + 31 must never be alive together
+// and a lane must be idle for a whole step pair between rows i and i + 32 - the conditions build_band_rows checks for 63 / 64
+bool ring32(const std::vector<int32_t>& rec, int n_rows) {
+  auto first = [&](int i) { return rec[2 * (size_t)i] & 0xFFFF; };
+  auto last = [&](int i) { return (rec[2 * (size_t)i] & 0xFFFF) + ((rec[2 * (size_t)i] >> 16) & 0xFFFF); };
+  for (int i = 0; i + 31 < n_rows; ++i) if (first(i + 31) < last(i) + 1) return false;
+  for (int i = 0; i + 32 < n_rows; ++i) if (first(i + 32) < last(i) + 3) return false;
+  return true;
+}
+
+// The banded rotating-row sweep (hx_band.hip) for a KC_LEAF_LDS_BANDED job, when the pair satisfies its assumptions and its
+// sides fit LDS: the row records of both sweeps.  Returns whether the job moves to KC_LEAF_ROT_BANDED.
+bool plan_band_sweep(Arena& ar, JobOff& jo, DevJob& J, const hx_pair_job& pj, int band_mode, const std::vector<int32_t>& cwin,
+                     const std::vector<int64_t>& cbase) {
+  std::vector<int32_t> rows;
+  int n_steps = 0;
+  const std::vector<uint8_t> xf = staged_flags(ar, jo.x), yf = staged_flags(ar, jo.y);
+  const std::vector<int32_t> xecls = staged_ecls(ar, jo.x);
+  auto forward_rows = [&](const int32_t* win, const int64_t* base) {
+    return build_band_rows(pj.x->env_pos, pj.y->env_pos, xf.data(), yf.data(), xecls.data(), jo.x.empty != 0, J.n_rows, J.n_cols,
+                           pj.max_distance, J.strip_stride, J.blk, win, base, rows, n_steps);
+  };
+  // Band-compressed planes of a pair that the banded sweep takes need not hold the always-in-envelope column (the y state
+  // feeding END) away from the band: below row 1 those cells are -inf (no x-absorbing move enters that column from a cell that
+  // is not itself in it, and the column's only finite cell off the band is (1, Ny-2): see hx_band.hip), and a cell that is not
+  // stored reads as -inf (hx_batch_read_cells, the traceback, lpEnd).  A strip's second window is that column whenever it is
+  // apart from the band's window, which also says that no row of the strip has a band that reaches it.  Without those windows
+  // a pair's planes are about half the size, and the fill no longer writes 5 x 8 bytes of -inf into a cache line of its own
+  // for every row (a fifth of the sweep's time at 4096 pairs).
+  std::vector<int32_t> twin(cwin);
+  std::vector<int64_t> tbase;
+  int64_t tplane = 0;
+  if (jo.compressed) {
+    tbase.assign(2 * (size_t)J.n_strips, 0);
+    for (int q = 0; q < J.n_strips; ++q) {
+      int32_t* o = &twin[4 * (size_t)q];
+      if (q >= 1 && o[3] > o[2]) o[2] = o[3] = 0;
+      for (int w = 0; w < 2; ++w) {
+        tbase[2 * (size_t)q + w] = tplane;
+        tplane += (int64_t)((o[2 * w + 1] - o[2 * w]) >> 1) * (2 * HX_STRIP);
+      }
+    }
+    tplane = (tplane + 1) & ~(int64_t)1;
+  }
+  const bool fits = band_kernel_fits(band_mode, J.n_rows, J.n_cols, std::max(jo.x.n_cls, jo.y.n_cls));
+  const bool trimmed = fits && jo.compressed && forward_rows(twin.data(), tbase.data());
+  if (trimmed) {
+    jo.fwd_windows = ar.put(twin.data(), sizeof(int32_t) * twin.size());
+    jo.strip_base = ar.put(tbase.data(), sizeof(int64_t) * tbase.size());
+    jo.compact_plane = tplane;
+    J.plane = tplane;
+    J.matrix_doubles = 5 * J.plane;
+  }
+  if (!trimmed && !(fits && forward_rows(jo.compressed ? cwin.data() : nullptr, jo.compressed ? cbase.data() : nullptr)))
+    return false;
+  // the Backward sweep of the same kernel (dense planes: band-compressed batches have no Backward).  A pair the Backward
+  // sweep cannot take (fewer than three rows or columns) stays out of the class altogether, so that the class never falls
+  // back to the strip pipeline because of one such pair.
+  std::vector<int32_t> rows_b;
+  int n_steps_b = 0;
+  const bool bwd_ok = jo.compressed ||
+      build_band_rows_bwd(pj.x->env_pos, pj.y->env_pos, xf.data(), yf.data(), xecls.data(), jo.x.empty != 0, jo.y.empty != 0, J.n_rows, J.n_cols,
+                          pj.max_distance, J.strip_stride, J.blk, rows_b, n_steps_b);
+  if (!bwd_ok) return false;
+  jo.band_rows = ar.put(rows.data(), sizeof(int32_t) * rows.size());
+  J.band_steps = n_steps;
+  J.band_w32 = (J.blk == 2 * HX_STRIP && ring32(rows, J.n_rows) && (jo.compressed || ring32(rows_b, J.n_rows)) &&
+                band2_kernel_fits(J.n_rows, J.n_cols, std::max(jo.x.n_cls, jo.y.n_cls))) ? 1 : 0;
+  J.band_steps_bwd = 0;
+  if (!jo.compressed) {
+    jo.band_rows_bwd = ar.put(rows_b.data(), sizeof(int32_t) * rows_b.size());
+    J.band_steps_bwd = n_steps_b;
+  }
+  return true;
+}
+
+// A job's share of the batch's and its class's sizes; its emission plane, when it has no class-pair table.
+void tally_job(hx_batch* b, int kc, JobOff& jo, const DevJob& J, int64_t& eplane_total) {
+  b->any_compressed = b->any_compressed || jo.compressed;
+  jo.eplane_off = -1;
+  if (!jo.table_emission) {   // (also for a profile without emitting states: the pipeline's loads are unconditional)
+    jo.eplane_off = eplane_total;
+    eplane_total += J.plane;
+    if (J.plane > b->max_eplane) b->max_eplane = J.plane;
+  }
+  b->total_cells += (int64_t)J.n_rows * J.n_cols;
+  if (jo.x.n > b->max_states) b->max_states = jo.x.n;
+  if (jo.y.n > b->max_states) b->max_states = jo.y.n;
+  if (jo.x.n_cls > b->max_cls) b->max_cls = jo.x.n_cls;
+  if (jo.y.n_cls > b->max_cls) b->max_cls = jo.y.n_cls;
+  if (J.CA > b->max_ca) b->max_ca = J.CA;
+  const int64_t pairs = (int64_t)jo.x.n_cls * jo.y.n_cls;
+  if (jo.table_emission && pairs > b->max_cls_pairs) b->max_cls_pairs = (int)pairs;
+  ClassRange& cr = b->cls[kc];
+  cr.n++;
+  if (kc == KC_LEAF_ROT_BANDED && J.band_w32) cr.n_w32++;
+  if (J.n_rows > cr.max_rows) cr.max_rows = J.n_rows;
+  if (J.n_cols > cr.max_cols) cr.max_cols = J.n_cols;
+  if (jo.x.n_cls > cr.max_cls) cr.max_cls = jo.x.n_cls;
+  if (jo.y.n_cls > cr.max_cls) cr.max_cls = jo.y.n_cls;
+  if (((jo.y.n + 3) & ~3) > cr.yl_cols) cr.yl_cols = (jo.y.n + 3) & ~3;
+  const int ep = ((jo.x.n_cls + 1) * (jo.y.n_cls + 1) + 1) & ~1;
+  if (ep > cr.yl_emis) cr.yl_emis = ep;
+}
+
+// Class-ordered job table and matrix allocation (stable within a class).  The general-profile classes need scratch planes
+// next to the matrices: the five outgoing sums of every cell (hx_dag.hip), or - HX_LSE_LINEAR, when every such job's planes
+// fit 32-bit byte offsets - the cells in the scaled-probability fill's own format (hx_daglin.hip).
+// (General profiles under the truncating policy run as HX_LSE_FAST, which truncates as the reference does.  The scaled-
+// probability pipeline of hx_daglin.hip with truncating sums was built and withdrawn in round 3: it sums a state's fourth and
+// further in-transitions out of the reference's order, and with truncation the order of a sum matters at the 4.5e-5 level -
+// cells downstream of such a state moved by up to 6e-5 where the leaf kernels hold 1e-7.)
+void order_classes(hx_batch* b, const hx_pair_job* jobs, const std::vector<JobOff>& offs, const std::vector<int>& kclass,
+                   std::vector<int64_t>& mat_off, std::vector<int64_t>& agg_off, int64_t& mat_total, int64_t& agg_total) {
+  const int n_jobs = b->n_jobs;
+  b->dag_linear = b->pol.linear && !b->pol.trunc && !(b->flags & HX_FORCE_GENERIC);
   for (int k = 0; k < n_jobs && b->dag_linear; ++k)
     if ((kclass[k] == KC_DAG || kclass[k] == KC_DAG_BANDED) && !dag_linear_fits(b->jobs[k].plane)) b->dag_linear = false;
-  int64_t mat_total = 0, agg_total = 0;
-  std::vector<int64_t> agg_off(n_jobs, -1);
-  {
-    int pos = 0;
-    b->order.resize(n_jobs);
-    for (int c = 0; c < KC_COUNT; ++c) {
-      ClassRange& cr = b->cls[c];
-      cr.begin = pos;
-      cr.mat_begin = mat_total;
-      cr.agg_begin = agg_total;
-      for (int k = 0; k < n_jobs; ++k)
-        if (kclass[k] == c) {
-          b->order[pos++] = k;
-          mat_off[k] = mat_total;
-          mat_total += b->jobs[k].matrix_doubles;
-          if (c == KC_DAG || c == KC_DAG_BANDED) {
-            agg_off[k] = agg_total;
-            agg_total += b->dag_linear ? dag_linear_scratch_doubles(b->jobs[k].plane, offs[k].x.n, offs[k].y.n, jobs[k].x->in_off[jobs[k].x->n_states], jobs[k].y->in_off[jobs[k].y->n_states]) : b->jobs[k].matrix_doubles;
-          }
+  mat_total = agg_total = 0;
+  int pos = 0;
+  b->order.resize(n_jobs);
+  for (int c = 0; c < KC_COUNT; ++c) {
+    ClassRange& cr = b->cls[c];
+    cr.begin = pos;
+    cr.mat_begin = mat_total;
+    cr.agg_begin = agg_total;
+    for (int k = 0; k < n_jobs; ++k)
+      if (kclass[k] == c) {
+        b->order[pos++] = k;
+        mat_off[k] = mat_total;
+        mat_total += b->jobs[k].matrix_doubles;
+        if (c == KC_DAG || c == KC_DAG_BANDED) {
+          agg_off[k] = agg_total;
+          agg_total += b->dag_linear ? dag_linear_scratch_doubles(b->jobs[k].plane, offs[k].x.n, offs[k].y.n, jobs[k].x->in_off[jobs[k].x->n_states], jobs[k].y->in_off[jobs[k].y->n_states]) : b->jobs[k].matrix_doubles;
         }
-      cr.mat_doubles = mat_total - cr.mat_begin;
-      cr.agg_doubles = agg_total - cr.agg_begin;
-    }
+      }
+    cr.mat_doubles = mat_total - cr.mat_begin;
+    cr.agg_doubles = agg_total - cr.agg_begin;
   }
-  // lpEnd / lpStart of all jobs, contiguous (caller's order): one copy back per read
-  b->lp_end_off = ar.reserve(sizeof(double) * n_jobs);
-  b->lp_start_off = ar.reserve(sizeof(double) * n_jobs);
+}
 
-  auto cleanup = [&](int code) { hx_batch_destroy(b); return code; };
-  const double tc1 = tick();
+// hipMalloc of n doubles, with the error the ABI reports for it
+int alloc_doubles(double** p, int64_t n, const char* what) {
+  if (hipMalloc(reinterpret_cast<void**>(p), sizeof(double) * (size_t)n) == hipSuccess) return HX_OK;
+  return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld %s bytes failed", (long long)(n * 8), what);
+}
+
+// Device memory of the batch: the staging image, the matrices and scratch planes; the device pointers of every job.
+int allocate_and_bind(hx_batch* b, const Arena& ar, const std::vector<JobOff>& offs, const std::vector<int64_t>& mat_off,
+                      const std::vector<int64_t>& agg_off, int64_t mat_total, int64_t eplane_total, int64_t agg_total) {
   if (hipMalloc(reinterpret_cast<void**>(&b->d_arena), ar.host.size() + 256) != hipSuccess)
-    return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %zu input bytes failed", ar.host.size()));
+    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %zu input bytes failed", ar.host.size());
   if (hipMemcpy(b->d_arena, ar.host.data(), ar.host.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(HX_ERR_HIP, "input upload failed"));
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_fwd), sizeof(double) * (size_t)mat_total) != hipSuccess)
-    return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld Forward-matrix bytes failed", (long long)(mat_total * 8)));
+    return fail(HX_ERR_HIP, "input upload failed");
+  int rc;
+  if ((rc = alloc_doubles(&b->d_fwd, mat_total, "Forward-matrix")) != HX_OK) return rc;
   b->fwd_total = mat_total;
-  if (eplane_total > 0)
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_eplane), sizeof(double) * (size_t)eplane_total) != hipSuccess)
-      return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld emission-plane bytes failed", (long long)(eplane_total * 8)));
-  if (agg_total > 0)
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_agg), sizeof(double) * (size_t)agg_total) != hipSuccess)
-      return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld scratch bytes failed", (long long)(agg_total * 8)));
-  if (flags & HX_KEEP_BACKWARD)
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_bwd), sizeof(double) * (size_t)mat_total) != hipSuccess)
-      return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld Backward-matrix bytes failed", (long long)(mat_total * 8)));
+  if (eplane_total > 0 && (rc = alloc_doubles(&b->d_eplane, eplane_total, "emission-plane")) != HX_OK) return rc;
+  if (agg_total > 0 && (rc = alloc_doubles(&b->d_agg, agg_total, "scratch")) != HX_OK) return rc;
+  if ((b->flags & HX_KEEP_BACKWARD) && (rc = alloc_doubles(&b->d_bwd, mat_total, "Backward-matrix")) != HX_OK) return rc;
 
-  b->cls[KC_LEAF_ROT_BANDED].bwd_band = b->cls[KC_LEAF_ROT_BANDED].n > 0 && !getenv("HX_BAND_BWD_OLD");
-  for (int k = 0; k < n_jobs; ++k)
-    if (kclass[k] == KC_LEAF_ROT_BANDED && !offs[k].band_rows_bwd) b->cls[KC_LEAF_ROT_BANDED].bwd_band = false;
-  for (int k = 0; k < n_jobs; ++k) {
+  ClassRange& rot = b->cls[KC_LEAF_ROT_BANDED];
+  rot.bwd_band = rot.n > 0 && !getenv("HX_BAND_BWD_OLD");
+  for (int p = rot.begin; p < rot.begin + rot.n; ++p)
+    if (!offs[b->order[p]].band_rows_bwd) rot.bwd_band = false;
+  for (int k = 0; k < b->n_jobs; ++k) {
     DevJob& J = b->jobs[k];
     const JobOff& jo = offs[k];
     char* base = b->d_arena;
@@ -1089,9 +1059,81 @@ static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs
     J.fwd = b->d_fwd + mat_off[k];
     J.bwd = b->d_bwd ? b->d_bwd + mat_off[k] : nullptr;
   }
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_jobs), sizeof(DevJob) * n_jobs) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&b->d_jobs_cls), sizeof(DevJob) * n_jobs) != hipSuccess)
-    return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of job table failed"));
+  if (hipMalloc(reinterpret_cast<void**>(&b->d_jobs), sizeof(DevJob) * b->n_jobs) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void**>(&b->d_jobs_cls), sizeof(DevJob) * b->n_jobs) != hipSuccess)
+    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of job table failed");
+  return HX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs, uint32_t flags, hx_batch** out) {
+  if (!out) return fail(HX_ERR_INVALID_ARG, "out is null");
+  *out = nullptr;
+  if (device < 0 || device >= HX_MAX_DEVICES || !g_dev[device].ready)
+    return fail(HX_ERR_NOT_INITIALIZED, "hx_init has not been called for device %d", device);
+  if (!jobs || n_jobs <= 0) return fail(HX_ERR_INVALID_ARG, "need at least one job");
+  HIP_TRY(hipSetDevice(device));
+  const bool timing = getenv("HX_TIMING_CREATE") != nullptr;
+  const auto tick = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double tc0 = tick();
+
+  hx_batch* b = new (std::nothrow) hx_batch;
+  if (!b) return fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed");
+  b->device = device;
+  b->n_jobs = n_jobs;
+  b->flags = flags;
+  b->pol = Policy(flags);
+  b->jobs.resize(n_jobs);
+  b->layouts.resize(n_jobs);
+
+  Arena ar;
+  std::vector<JobOff> offs(n_jobs);
+  std::vector<int> kclass(n_jobs);
+  int64_t eplane_total = 0;
+  int rc = HX_OK;
+  for (int k = 0; k < n_jobs; ++k) {
+    const hx_pair_job& pj = jobs[k];
+    JobOff& jo = offs[k];
+    if ((rc = flatten_job(pj, k, ar, jo)) != HX_OK) break;
+    const bool need_env = pj.max_distance >= 0;
+    int kc = choose_class(jo, need_env, flags);
+    if ((flags & HX_BAND_COMPRESSED) && (kc >= KC_DAG || (flags & HX_KEEP_BACKWARD))) {
+      rc = fail(HX_ERR_INVALID_ARG, "HX_BAND_COMPRESSED is implemented by the Forward fills of chain (leaf) profiles only: "
+                                    "no general profiles (job %d), no HX_KEEP_BACKWARD / HX_FORCE_GENERIC", k);
+      break;
+    }
+    if (b->pol.linear && (kc == KC_LEAF_LDS || kc == KC_LEAF_LDS_BANDED) && jo.y.n >= 2) put_ywords(ar, jo, pj);
+    std::vector<int32_t> cwin;
+    std::vector<int64_t> cbase;
+    if (need_env) put_windows(ar, jo, pj, flags, cwin, cbase);
+    DevJob& J = b->jobs[k];
+    hx_layout& L = b->layouts[k];
+    // Unbanded leaf pairs of the scaled-probability fills keep the five states of a step pair adjacent: a wavefront then
+    // writes 5 KiB contiguous per iteration instead of 1 KiB into each of five planes (hx_linear.hip; same total size).
+    // Only those kernels and the layout-aware readers ever see such a job.
+    init_job(J, L, jo, pj, b->pol.linear && kc == KC_LEAF_LDS);
+    if (kc == KC_LEAF_LDS_BANDED && jo.x.lp_zero && plan_band_sweep(ar, jo, J, pj, b->pol.band_mode, cwin, cbase))
+      kc = KC_LEAF_ROT_BANDED;
+    kclass[k] = kc;
+    L.strip_stride = J.strip_stride; L.plane_stride = J.plane;
+    L.block_stride = J.blk; L.matrix_doubles = J.matrix_doubles;
+    L.mirrored = 0; L.compressed = jo.compressed ? 1 : 0;
+    tally_job(b, kc, jo, J, eplane_total);
+  }
+  if (rc != HX_OK) { delete b; return rc; }
+
+  int64_t mat_total = 0, agg_total = 0;
+  std::vector<int64_t> mat_off(n_jobs), agg_off(n_jobs, -1);
+  order_classes(b, jobs, offs, kclass, mat_off, agg_off, mat_total, agg_total);
+  // lpEnd / lpStart of all jobs, contiguous (caller's order): one copy back per read
+  b->lp_end_off = ar.reserve(sizeof(double) * n_jobs);
+  b->lp_start_off = ar.reserve(sizeof(double) * n_jobs);
+
+  auto cleanup = [&](int code) { hx_batch_destroy(b); return code; };
+  const double tc1 = tick();
+  if ((rc = allocate_and_bind(b, ar, offs, mat_off, agg_off, mat_total, eplane_total, agg_total)) != HX_OK) return cleanup(rc);
   const double tc2 = tick();
   if ((rc = publish_jobs(b)) != HX_OK) return cleanup(rc);
   if (timing)
@@ -1197,15 +1239,117 @@ static void ensure_state_records(hx_batch* b, hipStream_t st) {
   b->records_valid = true;
 }
 
+// ---- what the Forward and the Backward fill share ----
+
+static bool banded_class(int c) {
+  return c == KC_LEAF_LDS_BANDED || c == KC_LEAF_ROT_BANDED || c == KC_LEAF_BANDED || c == KC_CHAIN_BANDED || c == KC_DAG_BANDED;
+}
+
+// A banded class's fills only visit in-envelope windows; everything else of its matrices is -inf beforehand.  The leaf and
+// chain classes (`sparse_ok`) skip that under HX_SPARSE_ENVELOPE, whose callers never read outside the envelope, and in
+// band-compressed planes, which hold nothing but the swept windows (the fill writes them completely; such a batch has no
+// Backward fill).  The general-profile classes are pre-filled under every flag.
+static void prefill_neg_inf(const hx_batch* b, double* mat, const ClassRange& cr, bool sparse_ok, hipStream_t st) {
+  if (sparse_ok && (b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED))) return;
+  launch_fill_neg_inf(mat + cr.mat_begin, cr.mat_doubles, st);
+}
+
+// The progress counters of the launches that deal a pair to several workgroups (hx_chain.hip, hx_linear.hip, hx_dag.hip
+// and hx_daglin.hip MULTI): allocated on first use; the Forward fill (dir 0) uses the first half of the buffer, the Backward
+// fill the second (a caller may run the two fills on two streams).  The first `ints` of the fill's half are zeroed on st.
+static int zeroed_counters(hx_batch* b, int dir, size_t ints, hipStream_t st, int** counters) {
+  if (!b->d_multi && hipMalloc(reinterpret_cast<void**>(&b->d_multi), 2 * HX_MULTI_COUNTER_PAIRS * 256 * sizeof(int)) != hipSuccess)
+    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of the progress counters failed");
+  *counters = b->d_multi + (size_t)dir * HX_MULTI_COUNTER_PAIRS * 256;
+  HIP_TRY(hipMemsetAsync(*counters, 0, ints * sizeof(int), st));
+  return HX_OK;
+}
+
+// The banded rotating-row sweep of a KC_LEAF_ROT_BANDED class (hx_band.hip), or two pairs per wavefront (hx_band2.hip)
+// with its edge kernel on the side stream.
+static int fill_band_sweep(hx_batch* b, const ClassRange& cr, int dir, hipStream_t st) {
+  const DeviceTables& D = g_dev[b->device];
+  const DevJob* jobs = b->d_jobs_cls + cr.begin;
+  const bool sparse = (b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED)) != 0;
+  if (band2_wanted(b->pol.linear, cr.n, cr.n_w32)) {
+    const hipStream_t side = side_fork(b, st);
+    LAUNCH_TRY((dir ? launch_backward_band2 : launch_forward_band2)(jobs, cr.n, b->pol.trunc, cr.max_rows, cr.max_cols, cr.max_cls,
+                                                                    Tab8{D.tab}, Tab16{D.log_tab}, sparse, st, side));
+    int rc;
+    if ((rc = side_join(b, st, side)) != HX_OK) return rc;
+    launch_band2_result(jobs, cr.n, dir, Tab8{D.tab}, st);
+    return HX_OK;
+  }
+  LAUNCH_TRY((dir ? launch_backward_band : launch_forward_band)(jobs, cr.n, b->pol.band_mode, cr.max_rows, cr.max_cols, cr.max_cls,
+                                                                Tab8{D.tab}, b->pol.band_tab(D), sparse, st));
+  return HX_OK;
+}
+
+// The strip pipelines of leaf and chain classes: scaled probabilities (hx_linear.hip) for leaf pairs whose y side fits LDS
+// under HX_LSE_LINEAR, else table log-sum-exps (hx_chain.hip).  A small batch of unbanded such pairs (one rank's share of a
+// strong-scaling run) is dealt to several workgroups per pair.
+static int fill_strips(hx_batch* b, int c, int dir, hipStream_t st) {
+  const DeviceTables& D = g_dev[b->device];
+  const ClassRange& cr = b->cls[c];
+  const DevJob* jobs = b->d_jobs_cls + cr.begin;
+  const bool banded = banded_class(c);
+  const int leaf = (c == KC_LEAF_LDS || c == KC_LEAF_LDS_BANDED || c == KC_LEAF_ROT_BANDED) ? 2 : ((c == KC_LEAF || c == KC_LEAF_BANDED) ? 1 : 0);
+  const int multi = (leaf == 2 && !banded && cr.n <= HX_MULTI_COUNTER_PAIRS && !b->no_multi) ? chain_multi_groups(cr.n, cr.max_rows, b->pol.linear ? 64 : 128) : 1;
+  int* counters = nullptr;
+  if (multi > 1) {
+    b->used_multi[dir] = true;
+    int rc;
+    if ((rc = zeroed_counters(b, dir, (size_t)cr.n * 256, st, &counters)) != HX_OK) return rc;
+  }
+  if (b->pol.linear && leaf == 2)
+    LAUNCH_TRY((dir ? launch_backward_leaf_linear : launch_forward_leaf_linear)(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab},
+                                                                                cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi, counters, b->pol.trunc, st));
+  else
+    LAUNCH_TRY((dir ? launch_backward_chain : launch_forward_chain)(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, leaf, banded,
+                                                                    cr.yl_cols, cr.yl_emis, multi, counters, st));
+  return HX_OK;
+}
+
+// A lone pair (or two) of more than sixteen strips in a general-profile class: its strips dealt to several workgroups
+// (hx_dag.hip, hx_daglin.hip).  Sets *groups (workgroups per pair, 1: the ordinary launch) and *waves (per workgroup), and
+// zeroes the progress counters of such a launch.  What differs between the two directions:
+//   * the Forward fill deals out whenever the pair qualifies; the Backward fill only in the state-record formulation
+//     (`records`: the general-profile classes, whose scratch planes hold the counters; chain classes run without records);
+//   * waves per workgroup: Forward 2 or 4, or 8 with the scaled-probability fill (the table policies' kernel is built for at
+//     most four waves in this launch: 512 registers per lane); Backward 2, 4 or 8 (built for at most eight: 256 registers);
+//   * workgroups per pair: at most 32 and HX_MULTI_MAX_GROUPS in all; Backward also at most 256 / waves (its progress
+//     counters: 256 per pair);
+//   * the counters: Forward, HX_MULTI_MAX_PAIRS * 256 ints at the start of the Forward half of hx_batch::d_multi (zeroed
+//     whenever the pair qualifies); Backward, the last 256 ints of each pair's scratch planes (zeroed when dealt out).
+static int plan_dag_multi(hx_batch* b, const ClassRange& cr, int dir, bool records, hipStream_t st, int* groups, int* waves,
+                          int** counters) {
+  *groups = 1; *waves = 4; *counters = nullptr;
+  const char* min_strips = getenv("HX_DAG_MULTI_MIN_STRIPS");       // tuning hook
+  if (!records || cr.n > HX_MULTI_MAX_PAIRS || cr.max_rows <= (min_strips ? atoi(min_strips) : 16) * HX_STRIP ||
+      getenv(dir ? "HX_DAG_BWD_SINGLE" : "HX_DAG_FWD_SINGLE") || b->no_multi)
+    return HX_OK;
+  b->used_multi[dir] = true;
+  const int strips = (cr.max_rows + HX_STRIP - 1) / HX_STRIP;
+  // tuning hook: waves per workgroup (default 4: measured 1.24 / 1.13 / 1.02 / 1.01 s for the Backward fill at one
+  // workgroup / 16 / 8 / 4 waves)
+  if (const char* e = getenv("HX_DAG_MULTI_WAVES")) *waves = atoi(e);
+  if ((*waves != 8 || (dir == 0 && !b->dag_linear)) && *waves != 2) *waves = 4;
+  *groups = std::min(std::min(32, HX_MULTI_MAX_GROUPS / cr.n), (strips + *waves - 1) / *waves);
+  if (dir) *groups = std::min(*groups, 256 / *waves);
+  if (dir == 0) return zeroed_counters(b, 0, HX_MULTI_MAX_PAIRS * 256, st, counters);
+  for (int q = 0; q < cr.n && *groups > 1; ++q) {
+    const DevJob& Jh = b->jobs[b->order[cr.begin + q]];
+    HIP_TRY(hipMemsetAsync(reinterpret_cast<int*>(Jh.agg + 5 * Jh.plane) - 256, 0, 256 * sizeof(int), st));
+  }
+  return HX_OK;
+}
+
 int hx_batch_forward(hx_batch* b, void* stream) {
   if (!b) return fail(HX_ERR_INVALID_ARG, "batch is null");
   int rc;
   if ((rc = use_device(b)) != HX_OK) return rc;
   const DeviceTables& D = g_dev[b->device];
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool fast = (b->flags & HX_LSE_FAST) != 0, linear = (b->flags & HX_LSE_LINEAR) == HX_LSE_LINEAR;
-  const bool trunc = (b->flags & HX_LSE_TRUNC) == HX_LSE_TRUNC;
-  const Tab16 lse_tab{fast ? D.fast_tab : D.pair_tab};    // FastPiece table, or the exact mode's {f0, df} pairs
   // the state records: with the preparation when a general-profile class will read them in the fill, else when a traceback or
   // counting kernel first asks (ensure_state_records)
   const bool records_now = b->cls[KC_DAG].n > 0 || b->cls[KC_DAG_BANDED].n > 0 || b->cls[KC_GENERIC].n > 0 || b->records_valid ||
@@ -1216,83 +1360,42 @@ int hx_batch_forward(hx_batch* b, void* stream) {
   HIP_TRY(hipEventRecord(b->ev[0][0], st));
   // per-cell emission terms of the jobs without a class-pair table (general profiles).  Part of the fill:
   // the reference evaluates them inside its fill loop, so the launch is inside the timed region.
-  if (!(b->flags & HX_FORCE_GENERIC)) launch_emission_plane(b->d_jobs, b->n_jobs, b->max_eplane, Tab8{D.tab}, Tab16{D.fast_tab}, fast && !getenv("HX_EXACT_EMISSION"), st);
+  if (!(b->flags & HX_FORCE_GENERIC)) launch_emission_plane(b->d_jobs, b->n_jobs, b->max_eplane, Tab8{D.tab}, Tab16{D.fast_tab}, b->pol.fast && !getenv("HX_EXACT_EMISSION"), st);
   for (int c = 0; c < KC_COUNT; ++c) {
     const ClassRange& cr = b->cls[c];
     if (cr.n == 0) continue;
     const DevJob* jobs = b->d_jobs_cls + cr.begin;
-    const bool banded = c == KC_LEAF_LDS_BANDED || c == KC_LEAF_BANDED || c == KC_CHAIN_BANDED || c == KC_DAG_BANDED;
+    const bool banded = banded_class(c);
     switch (c) {
       case KC_LEAF_ROT_BANDED:
-        if (!(b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED))) launch_fill_neg_inf(b->d_fwd + cr.mat_begin, cr.mat_doubles, st);
-        if (band2_wanted(linear, cr.n, cr.n_w32)) {
-          const hipStream_t side = side_fork(b, st);
-          LAUNCH_TRY(launch_forward_band2(jobs, cr.n, trunc, cr.max_rows, cr.max_cols, cr.max_cls, Tab8{D.tab}, Tab16{D.log_tab},
-                                          (b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED)) != 0, st, side));
-          if ((rc = side_join(b, st, side)) != HX_OK) return rc;
-          launch_band2_result(jobs, cr.n, 0, Tab8{D.tab}, st);
-        } else
-        LAUNCH_TRY(launch_forward_band(jobs, cr.n, linear ? (trunc ? 3 : 0) : (fast ? 1 : 2), cr.max_rows, cr.max_cols, cr.max_cls, Tab8{D.tab},
-                                       linear ? Tab16{D.log_tab} : lse_tab, (b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED)) != 0, st));
+        prefill_neg_inf(b, b->d_fwd, cr, true, st);
+        if ((rc = fill_band_sweep(b, cr, 0, st)) != HX_OK) return rc;
         break;
-      case KC_LEAF_LDS: case KC_LEAF_LDS_BANDED: case KC_LEAF: case KC_LEAF_BANDED: case KC_CHAIN: case KC_CHAIN_BANDED: {
-        // with a band the strip pipelines only visit in-envelope windows; everything else is -inf
-        // (band-compressed matrices hold nothing but the swept windows, which the fill writes completely)
-        if (banded && !(b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED)))
-          launch_fill_neg_inf(b->d_fwd + cr.mat_begin, cr.mat_doubles, st);
-        const int leaf = (c == KC_LEAF_LDS || c == KC_LEAF_LDS_BANDED) ? 2 : ((c == KC_LEAF || c == KC_LEAF_BANDED) ? 1 : 0);
-        // HX_LSE_LINEAR on leaf pairs whose y side fits LDS: the recursion runs on scaled probabilities instead of
-        // table log-sum-exps (hx_linear.hip)
-        // a small batch of unbanded leaf pairs (one rank's share of a strong-scaling run): several workgroups per pair
-        int multi = (leaf == 2 && !banded && cr.n <= HX_MULTI_COUNTER_PAIRS && !b->no_multi) ? chain_multi_groups(cr.n, cr.max_rows, linear ? 64 : 128) : 1;
-        if (multi > 1) {
-          b->used_multi[0] = true;
-          if (!b->d_multi && hipMalloc(reinterpret_cast<void**>(&b->d_multi), 2 * HX_MULTI_COUNTER_PAIRS * 256 * sizeof(int)) != hipSuccess)
-            return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of the progress counters failed");
-          HIP_TRY(hipMemsetAsync(b->d_multi, 0, (size_t)cr.n * 256 * sizeof(int), st));
-        }
-        if (linear && leaf == 2)
-          LAUNCH_TRY(launch_forward_leaf_linear(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab}, cr.yl_cols, cr.yl_emis, cr.max_cls + 1,
-                                                multi, b->d_multi, trunc, st));
-        else
-          LAUNCH_TRY(launch_forward_chain(jobs, cr.n, cr.max_rows, Tab8{D.tab}, lse_tab, fast, leaf, banded, cr.yl_cols, cr.yl_emis, multi, b->d_multi, st));
+      case KC_LEAF_LDS: case KC_LEAF_LDS_BANDED: case KC_LEAF: case KC_LEAF_BANDED: case KC_CHAIN: case KC_CHAIN_BANDED:
+        if (banded) prefill_neg_inf(b, b->d_fwd, cr, true, st);
+        if ((rc = fill_strips(b, c, 0, st)) != HX_OK) return rc;
         break;
-      }
-      case KC_DAG: case KC_DAG_BANDED:
+      case KC_DAG: case KC_DAG_BANDED: {
         // general profiles: the strip pipeline; with a band it only visits in-envelope windows, the rest is -inf
         if (banded) {
-          launch_fill_neg_inf(b->d_fwd + cr.mat_begin, cr.mat_doubles, st);
+          prefill_neg_inf(b, b->d_fwd, cr, false, st);
           if (b->dag_linear) launch_dag_linear_clear(jobs, cr.n, st);
           else launch_fill_neg_inf(b->d_agg + cr.agg_begin, cr.agg_doubles, st);
         }
-        {
-          // a lone pair (or two) of more than sixteen strips: dealt to several workgroups, as the Backward fill is (below)
-          int multi = 1, multi_waves = 4;
-          const char* min_strips = getenv("HX_DAG_MULTI_MIN_STRIPS");
-          if (cr.n <= HX_MULTI_MAX_PAIRS && cr.max_rows > (min_strips ? atoi(min_strips) : 16) * HX_STRIP && !getenv("HX_DAG_FWD_SINGLE") && !b->no_multi) {
-            b->used_multi[0] = true;
-            const int strips = (cr.max_rows + HX_STRIP - 1) / HX_STRIP;
-            if (const char* e = getenv("HX_DAG_MULTI_WAVES")) multi_waves = atoi(e);
-            // (the table policies' kernel is built for at most four waves per workgroup in this launch: 512 registers per lane)
-            if ((multi_waves != 8 || !b->dag_linear) && multi_waves != 2) multi_waves = 4;
-            multi = std::min(std::min(32, HX_MULTI_MAX_GROUPS / cr.n), (strips + multi_waves - 1) / multi_waves);
-            if (!b->d_multi && hipMalloc(reinterpret_cast<void**>(&b->d_multi), 2 * HX_MULTI_COUNTER_PAIRS * 256 * sizeof(int)) != hipSuccess)
-              return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of the progress counters failed");
-            HIP_TRY(hipMemsetAsync(b->d_multi, 0, HX_MULTI_MAX_PAIRS * 256 * sizeof(int), st));
-          }
-          if (b->dag_linear)
-            LAUNCH_TRY(launch_forward_dag_linear(jobs, cr.n, cr.max_rows, Tab8{D.tab}, Tab16{D.log_tab}, multi, multi_waves, b->d_multi, st));
-          else
-            LAUNCH_TRY(launch_forward_dag_pipe(jobs, cr.n, cr.max_rows, Tab8{D.tab}, lse_tab, fast, multi, multi_waves, b->d_multi, st));
-        }
+        int multi, waves, *counters;
+        if ((rc = plan_dag_multi(b, cr, 0, true, st, &multi, &waves, &counters)) != HX_OK) return rc;
+        if (b->dag_linear)
+          LAUNCH_TRY(launch_forward_dag_linear(jobs, cr.n, cr.max_rows, Tab8{D.tab}, Tab16{D.log_tab}, multi, waves, counters, st));
+        else
+          LAUNCH_TRY(launch_forward_dag_pipe(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, multi, waves, counters, st));
         break;
+      }
       default:
         LAUNCH_TRY(launch_forward_dag(jobs, cr.n, cr.max_rows, Tab8{D.tab}, st));
     }
   }
   HIP_TRY(hipEventRecord(b->ev[0][1], st));
   HIP_TRY(hipGetLastError());
-  b->ev_valid[0] = true;
   b->forward_done = true;
   b->last_stream = st;
   return HX_OK;
@@ -1306,15 +1409,11 @@ int hx_batch_backward(hx_batch* b, void* stream) {
   if ((rc = use_device(b)) != HX_OK) return rc;
   const DeviceTables& D = g_dev[b->device];
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool fast = (b->flags & HX_LSE_FAST) != 0, linear = (b->flags & HX_LSE_LINEAR) == HX_LSE_LINEAR;
-  const bool trunc = (b->flags & HX_LSE_TRUNC) == HX_LSE_TRUNC;
-  const Tab16 lse_tab{fast ? D.fast_tab : D.pair_tab};
   ensure_state_records(b, st);                    // (the Backward fill of chain profiles runs the general pipeline, which reads them)
   if (!b->d_bwd) {
     // not pre-allocated with HX_KEEP_BACKWARD: allocate the Backward matrices now and re-publish the job tables
     HIP_TRY(hipStreamSynchronize(b->last_stream));
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_bwd), sizeof(double) * (size_t)b->fwd_total) != hipSuccess)
-      return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld Backward-matrix bytes failed", (long long)(b->fwd_total * 8));
+    if ((rc = alloc_doubles(&b->d_bwd, b->fwd_total, "Backward-matrix")) != HX_OK) return rc;
     for (int k = 0; k < b->n_jobs; ++k) b->jobs[k].bwd = b->d_bwd + (b->jobs[k].fwd - b->d_fwd);
     if ((rc = publish_jobs(b)) != HX_OK) return rc;
   } else if (st != b->last_stream) {
@@ -1327,72 +1426,31 @@ int hx_batch_backward(hx_batch* b, void* stream) {
     const ClassRange& cr = b->cls[c];
     if (cr.n == 0) continue;
     const DevJob* jobs = b->d_jobs_cls + cr.begin;
-    const bool banded = c == KC_LEAF_LDS_BANDED || c == KC_LEAF_ROT_BANDED || c == KC_LEAF_BANDED || c == KC_CHAIN_BANDED || c == KC_DAG_BANDED;
+    const bool banded = banded_class(c);
     switch (c) {
-      case KC_LEAF_LDS: case KC_LEAF_LDS_BANDED: case KC_LEAF_ROT_BANDED: case KC_LEAF: case KC_LEAF_BANDED: {
-        if (banded && !(b->flags & HX_SPARSE_ENVELOPE)) launch_fill_neg_inf(b->d_bwd + cr.mat_begin, cr.mat_doubles, st);
-        const int leaf = (c == KC_LEAF_LDS || c == KC_LEAF_LDS_BANDED || c == KC_LEAF_ROT_BANDED) ? 2 : 1;
-        if (c == KC_LEAF_ROT_BANDED && cr.bwd_band && band2_wanted(linear, cr.n, cr.n_w32)) {
-          const hipStream_t side = side_fork(b, st);
-          LAUNCH_TRY(launch_backward_band2(jobs, cr.n, trunc, cr.max_rows, cr.max_cols, cr.max_cls, Tab8{D.tab}, Tab16{D.log_tab},
-                                           (b->flags & HX_SPARSE_ENVELOPE) != 0, st, side));
-          if ((rc = side_join(b, st, side)) != HX_OK) return rc;
-          launch_band2_result(jobs, cr.n, 1, Tab8{D.tab}, st);
-        } else if (c == KC_LEAF_ROT_BANDED && cr.bwd_band)
-          // the rotating-row sweep in mirrored coordinates (hx_band.hip)
-          LAUNCH_TRY(launch_backward_band(jobs, cr.n, linear ? (trunc ? 3 : 0) : (fast ? 1 : 2), cr.max_rows, cr.max_cols, cr.max_cls, Tab8{D.tab},
-                                          linear ? Tab16{D.log_tab} : lse_tab, (b->flags & HX_SPARSE_ENVELOPE) != 0, st));
-        else {
-          int multi = (leaf == 2 && !banded && cr.n <= HX_MULTI_COUNTER_PAIRS && !b->no_multi) ? chain_multi_groups(cr.n, cr.max_rows, linear ? 64 : 128) : 1;
-          int* counters = nullptr;
-          if (multi > 1) {
-            b->used_multi[1] = true;
-            if (!b->d_multi && hipMalloc(reinterpret_cast<void**>(&b->d_multi), 2 * HX_MULTI_COUNTER_PAIRS * 256 * sizeof(int)) != hipSuccess)
-              return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of the progress counters failed");
-            counters = b->d_multi + HX_MULTI_COUNTER_PAIRS * 256;
-            HIP_TRY(hipMemsetAsync(counters, 0, (size_t)cr.n * 256 * sizeof(int), st));
-          }
-          if (linear && leaf == 2)
-            LAUNCH_TRY(launch_backward_leaf_linear(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab}, cr.yl_cols, cr.yl_emis, cr.max_cls + 1,
-                                                   multi, counters, trunc, st));
-          else
-            LAUNCH_TRY(launch_backward_chain(jobs, cr.n, cr.max_rows, Tab8{D.tab}, lse_tab, fast, leaf, banded, cr.yl_cols, cr.yl_emis, multi, counters, st));
-        }
+      case KC_LEAF_LDS: case KC_LEAF_LDS_BANDED: case KC_LEAF_ROT_BANDED: case KC_LEAF: case KC_LEAF_BANDED:
+        if (banded) prefill_neg_inf(b, b->d_bwd, cr, true, st);
+        // the rotating-row sweep in mirrored coordinates (hx_band.hip), when every pair of the class has its records
+        rc = (c == KC_LEAF_ROT_BANDED && cr.bwd_band) ? fill_band_sweep(b, cr, 1, st) : fill_strips(b, c, 1, st);
+        if (rc != HX_OK) return rc;
+        break;
+      case KC_CHAIN: case KC_CHAIN_BANDED: case KC_DAG: case KC_DAG_BANDED: {
+        if (banded) prefill_neg_inf(b, b->d_bwd, cr, false, st);
+        // the state-record formulation needs the pair's scratch planes (general-profile classes have them: five planes
+        // per pair - twelve in the scaled-probability mode - of no use once the Forward fill is done: a later Forward
+        // launch rebuilds its per-state packs (k_lin_pack) and, with a band, clears the planes again (k_lin_clear))
+        const bool records = c == KC_DAG || c == KC_DAG_BANDED;
+        int multi, waves, *counters;
+        if ((rc = plan_dag_multi(b, cr, 1, records, st, &multi, &waves, &counters)) != HX_OK) return rc;
+        LAUNCH_TRY(launch_backward_dag_pipe(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, records, multi, waves, st));
         break;
       }
-      case KC_CHAIN: case KC_CHAIN_BANDED: case KC_DAG: case KC_DAG_BANDED:
-        if (banded) launch_fill_neg_inf(b->d_bwd + cr.mat_begin, cr.mat_doubles, st);
-        {
-          // the state-record formulation needs the pair's scratch planes (general-profile classes have them: five planes
-          // per pair - twelve in the scaled-probability mode - of no use once the Forward fill is done: a later Forward
-          // launch rebuilds its per-state packs (k_lin_pack) and, with a band, clears the planes again (k_lin_clear))
-          const bool records = (c == KC_DAG || c == KC_DAG_BANDED) && !getenv("HX_DAG_BWD_OLD");
-          // a lone pair (or two) of more than sixteen strips: its strips dealt to two to four workgroups (hx_dag.hip
-          // k_backward_dag_multi); their progress counters - the last 256 ints of each pair's scratch planes - start at zero
-          int multi = 1, multi_waves = 4;
-          const char* min_strips = getenv("HX_DAG_MULTI_MIN_STRIPS");      // tuning hook
-          if (records && cr.n <= HX_MULTI_MAX_PAIRS && cr.max_rows > (min_strips ? atoi(min_strips) : 16) * HX_STRIP && !getenv("HX_DAG_BWD_SINGLE") && !b->no_multi) {
-            b->used_multi[1] = true;
-            const int strips = (cr.max_rows + HX_STRIP - 1) / HX_STRIP;
-            if (const char* e = getenv("HX_DAG_MULTI_WAVES")) multi_waves = atoi(e);      // tuning hook: waves per workgroup (default 4: measured 1.24 / 1.13 / 1.02 / 1.01 s at one workgroup / 16 / 8 / 4 waves)
-            if (multi_waves != 8 && multi_waves != 2) multi_waves = 4;      // (the kernel is built for at most eight: 256 registers per lane)
-            multi = std::min(256 / multi_waves, (strips + multi_waves - 1) / multi_waves);   // (progress counters: 256 per pair)
-            multi = std::min(multi, std::min(32, HX_MULTI_MAX_GROUPS / cr.n));
-            for (int q = 0; q < cr.n && multi > 1; ++q) {
-              const DevJob& Jh = b->jobs[b->order[cr.begin + q]];
-              HIP_TRY(hipMemsetAsync(reinterpret_cast<int*>(Jh.agg + 5 * Jh.plane) - 256, 0, 256 * sizeof(int), st));
-            }
-          }
-          LAUNCH_TRY(launch_backward_dag_pipe(jobs, cr.n, cr.max_rows, Tab8{D.tab}, lse_tab, fast, records, multi, multi_waves, st));
-        }
-        break;
       default:
         LAUNCH_TRY(launch_backward_dag(jobs, cr.n, cr.max_rows, Tab8{D.tab}, st));
     }
   }
   HIP_TRY(hipEventRecord(b->ev[1][1], st));
   HIP_TRY(hipGetLastError());
-  b->ev_valid[1] = true;
   b->backward_done = true;
   b->last_stream = st;
   return HX_OK;
@@ -1406,19 +1464,14 @@ int hx_batch_sync(hx_batch* b) {
 }
 
 int hx_batch_last_kernel_ms(hx_batch* b, int32_t which, float* ms) {
-  if (!b || !ms || which < 0 || which > 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (!b->ev_valid[which]) return fail(HX_ERR_STATE, "no such fill has been launched");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, ms && which >= 0 && which <= 1, nullptr, need_fill(which), "no such fill has been launched")) return rc;
   HIP_TRY(hipEventSynchronize(b->ev[which][1]));
   HIP_TRY(hipEventElapsedTime(ms, b->ev[which][0], b->ev[which][1]));
   return HX_OK;
 }
 
 static int read_scalars(hx_batch* b, double* out, int which) {
-  if (!b || !out) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (which == 0 ? !b->forward_done : !b->backward_done) return fail(HX_ERR_STATE, "fill has not been launched");
-  int rc;
-  if ((rc = use_device(b)) != HX_OK) return rc;
+  if (const int rc = open_reader(b, out != nullptr, nullptr, need_fill(which), "fill has not been launched")) return rc;
   HIP_TRY(hipStreamSynchronize(b->last_stream));
   HIP_TRY(hipMemcpy(out, b->d_arena + (which == 0 ? b->lp_end_off : b->lp_start_off), sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost));
   return HX_OK;
@@ -1441,47 +1494,38 @@ static int relaunch_single(hx_batch* b, bool backward_too) {
   if (rc == HX_OK && backward_too) rc = hx_batch_backward(b, b->last_stream);
   return rc;
 }
-int hx_batch_lp_end(hx_batch* b, double* out) {
-  int rc = read_scalars(b, out, 0);
+// lpEnd (which 0) or lpStart (1) of every job, relaunching the fills once for NaN (above)
+static int read_lp(hx_batch* b, double* out, int which) {
+  int rc = read_scalars(b, out, which);
   if (rc != HX_OK) return rc;
+  const char* fill = which == 0 ? "Forward" : "Backward";
   int k = first_nan(b, out);
-  if (k >= 0 && b->used_multi[0] && !b->no_multi) {
-    if ((rc = relaunch_single(b, b->backward_done)) != HX_OK) return fail(HX_ERR_HIP, "the Forward fill of pair %d did not complete (workgroups lost one another) and could not be launched again", k);
-    if ((rc = read_scalars(b, out, 0)) != HX_OK) return rc;
+  if (k >= 0 && b->used_multi[which] && !b->no_multi) {
+    if ((rc = relaunch_single(b, which == 1 || b->backward_done)) != HX_OK)
+      return fail(HX_ERR_HIP, "the %s fill of pair %d did not complete (workgroups lost one another) and could not be launched again", fill, k);
+    if ((rc = read_scalars(b, out, which)) != HX_OK) return rc;
     k = first_nan(b, out);
   }
-  if (k >= 0) return fail(HX_ERR_HIP, "the Forward fill of pair %d did not complete (workgroups lost one another)", k);
+  if (k >= 0) return fail(HX_ERR_HIP, "the %s fill of pair %d did not complete (workgroups lost one another)", fill, k);
   return HX_OK;
 }
-int hx_batch_lp_start(hx_batch* b, double* out) {
-  int rc = read_scalars(b, out, 1);
-  if (rc != HX_OK) return rc;
-  int k = first_nan(b, out);
-  if (k >= 0 && b->used_multi[1] && !b->no_multi) {
-    if ((rc = relaunch_single(b, true)) != HX_OK) return fail(HX_ERR_HIP, "the Backward fill of pair %d did not complete (workgroups lost one another) and could not be launched again", k);
-    if ((rc = read_scalars(b, out, 1)) != HX_OK) return rc;
-    k = first_nan(b, out);
-  }
-  if (k >= 0) return fail(HX_ERR_HIP, "the Backward fill of pair %d did not complete (workgroups lost one another)", k);
-  return HX_OK;
-}
+int hx_batch_lp_end(hx_batch* b, double* out) { return read_lp(b, out, 0); }
+int hx_batch_lp_start(hx_batch* b, double* out) { return read_lp(b, out, 1); }
 
 int hx_batch_relaunches(const hx_batch* b) {
-  if (!b) return fail(HX_ERR_INVALID_ARG, "bad arguments");
+  if (const int rc = check_reader(b, true, nullptr)) return rc;
   return b->relaunches;
 }
 
 int hx_batch_layout(const hx_batch* b, int32_t job, int32_t which, hx_layout* out) {
-  if (!b || !out || which < 0 || which > 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
+  if (const int rc = check_reader(b, out && which >= 0 && which <= 1, &job)) return rc;
   *out = b->layouts[job];
   out->mirrored = which;      // the Backward matrix is stored in mirrored coordinates
   return HX_OK;
 }
 
 int hx_batch_strip_windows(const hx_batch* b, int32_t job, int32_t* windows, int64_t* bases) {
-  if (!b || !windows || !bases) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
+  if (const int rc = check_reader(b, windows && bases, &job)) return rc;
   const DevJob& J = b->jobs[job];
   if (!J.strip_base) return fail(HX_ERR_STATE, "job %d is not stored band-compressed", job);
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
@@ -1493,8 +1537,7 @@ int hx_batch_strip_windows(const hx_batch* b, int32_t job, int32_t* windows, int
 int64_t hx_batch_total_cells(const hx_batch* b) { return b ? b->total_cells : 0; }
 
 int hx_batch_job_kernel(const hx_batch* b, int32_t job, int32_t* forward_class, int32_t* backward_sweep) {
-  if (!b) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
+  if (const int rc = check_reader(b, true, &job)) return rc;
   for (int c = 0; c < KC_COUNT; ++c) {
     const ClassRange& cr = b->cls[c];
     for (int p = cr.begin; p < cr.begin + cr.n; ++p)
@@ -1508,9 +1551,9 @@ int hx_batch_job_kernel(const hx_batch* b, int32_t job, int32_t* forward_class, 
 }
 
 int hx_batch_shared_wavefront_pairs(const hx_batch* b) {
-  if (!b) return fail(HX_ERR_INVALID_ARG, "bad arguments");
+  if (const int rc = check_reader(b, true, nullptr)) return rc;
   const ClassRange& cr = b->cls[KC_LEAF_ROT_BANDED];
-  return band2_wanted((b->flags & HX_LSE_LINEAR) == HX_LSE_LINEAR, cr.n, cr.n_w32) ? cr.n : 0;
+  return band2_wanted(b->pol.linear, cr.n, cr.n_w32) ? cr.n : 0;
 }
 
 static const double* matrix_of(hx_batch* b, int job, int which) {
@@ -1518,20 +1561,14 @@ static const double* matrix_of(hx_batch* b, int job, int which) {
 }
 
 int hx_batch_read_matrix(hx_batch* b, int32_t job, int32_t which, double* out) {
-  if (!b || !out || which < 0 || which > 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (which == 0 ? !b->forward_done : !b->backward_done) return fail(HX_ERR_STATE, "fill has not been launched");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, out && which >= 0 && which <= 1, &job, need_fill(which), "fill has not been launched")) return rc;
   HIP_TRY(hipStreamSynchronize(b->last_stream));
   HIP_TRY(hipMemcpy(out, matrix_of(b, job, which), sizeof(double) * (size_t)b->jobs[job].matrix_doubles, hipMemcpyDeviceToHost));
   return HX_OK;
 }
 
 int hx_batch_read_matrix_async(hx_batch* b, int32_t job, int32_t which, double* out) {
-  if (!b || !out || which < 0 || which > 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (which == 0 ? !b->forward_done : !b->backward_done) return fail(HX_ERR_STATE, "fill has not been launched");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, out && which >= 0 && which <= 1, &job, need_fill(which), "fill has not been launched")) return rc;
   HIP_TRY(hipStreamSynchronize(b->last_stream));
   if (!b->copy_stream) {
     DeviceTables& D = g_dev[b->device];
@@ -1548,8 +1585,7 @@ int hx_batch_read_matrix_async(hx_batch* b, int32_t job, int32_t which, double* 
 }
 
 int hx_batch_wait_read(hx_batch* b, int32_t job, int32_t which) {
-  if (!b || which < 0 || which > 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
+  if (const int rc = check_reader(b, which >= 0 && which <= 1, &job)) return rc;
   if (b->copied[which].empty() || !b->copied[which][job]) return fail(HX_ERR_STATE, "no asynchronous read of job %d was started", job);
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
   HIP_TRY(hipEventSynchronize(b->copied[which][job]));
@@ -1627,13 +1663,11 @@ static int quick_create_impl(int device, const hx_quick_job* jobs, int32_t n_job
     memset(&J, 0, sizeof(J));
     J.xlen = q.x_len; J.ylen = q.y_len; J.alph = q.alph_size;
     J.n_strips = (q.x_len + HX_STRIP - 1) / HX_STRIP;
-    // the three states of a step pair adjacent (a wavefront writes 3 KiB contiguous per iteration), unless
-    // HX_PLANAR_LAYOUT asks for separate state planes
-    const bool planar = getenv("HX_PLANAR_LAYOUT") != nullptr;
-    J.strip_stride = strip_stride_for(q.y_len) * (planar ? 1 : 3);
-    J.plane = planar ? J.n_strips * J.strip_stride : 2 * HX_STRIP;
-    J.blk = planar ? 2 * HX_STRIP : 6 * HX_STRIP;
-    const int64_t matrix_doubles = (planar ? 3 : 1) * (int64_t)J.n_strips * J.strip_stride;
+    // the three states of a step pair adjacent (a wavefront writes 3 KiB contiguous per iteration)
+    J.strip_stride = strip_stride_for(q.y_len) * 3;
+    J.plane = 2 * HX_STRIP;
+    J.blk = 6 * HX_STRIP;
+    const int64_t matrix_doubles = (int64_t)J.n_strips * J.strip_stride;
     for (int s = 0; s < 11; ++s) J.sc[s] = q.scores[s];
     hx_layout& L = b->layouts[k];
     L.n_rows = q.x_len; L.n_cols = q.y_len; L.strip_rows = HX_STRIP; L.n_strips = J.n_strips;
@@ -1784,9 +1818,8 @@ int hx_host_free(void* p) {
 }
 
 int hx_batch_read_cells(hx_batch* b, int32_t job, int32_t which, const int32_t* ij, int64_t n, double* out) {
-  if (!b || !out || !ij || n < 0 || which < 0 || which > 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (which == 0 ? !b->forward_done : !b->backward_done) return fail(HX_ERR_STATE, "fill has not been launched");
+  if (const int rc = check_reader(b, out && ij && n >= 0 && which >= 0 && which <= 1, &job, need_fill(which), "fill has not been launched"))
+    return rc;
   if (n == 0) return HX_OK;
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
   int32_t* d_ij = nullptr;
@@ -1811,9 +1844,8 @@ int hx_batch_read_cells(hx_batch* b, int32_t job, int32_t which, const int32_t* 
 
 // Device-side ForwardMatrix::bestTrace for every job of the batch (hx_trace.hip).
 int hx_batch_best_trace(hx_batch* b, hx_trace_cell* cells, int64_t cap, int32_t* n_cells) {
-  if (!b || !cells || !n_cells || cap < 1) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (!b->forward_done) return fail(HX_ERR_STATE, "hx_batch_best_trace needs a previous hx_batch_forward");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, cells && n_cells && cap >= 1, nullptr, NEED_FORWARD, "hx_batch_best_trace needs a previous hx_batch_forward"))
+    return rc;
   const int n = b->n_jobs;
   // device buffers and the page-locked staging buffer are kept with the batch (a host mirror asks once per fill batch,
   // a benchmark many times)
@@ -1863,7 +1895,7 @@ int hx_batch_best_trace(hx_batch* b, hx_trace_cell* cells, int64_t cap, int32_t*
 }
 
 int hx_batch_best_trace_ties(hx_batch* b, int32_t* near_tie) {
-  if (!b || !near_tie) return fail(HX_ERR_INVALID_ARG, "bad arguments");
+  if (const int rc = check_reader(b, near_tie != nullptr, nullptr)) return rc;
   if (!b->trace_ties_valid) return fail(HX_ERR_STATE, "hx_batch_best_trace_ties needs a previous hx_batch_best_trace");
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
   HIP_TRY(hipMemcpy(near_tie, reinterpret_cast<const int32_t*>(b->d_trace_n + 2 * (size_t)b->n_jobs), sizeof(int32_t) * b->n_jobs, hipMemcpyDeviceToHost));
@@ -1872,11 +1904,9 @@ int hx_batch_best_trace_ties(hx_batch* b, int32_t* near_tie) {
 
 int hx_batch_sample_traces(hx_batch* b, int32_t job, int32_t n_walks, const double* uniforms, int64_t n_uniforms,
                            hx_trace_cell* cells, int64_t cap, int32_t* n_cells, int64_t* draws_used) {
-  if (!b || !uniforms || !cells || !n_cells || !draws_used || n_walks < 1 || n_uniforms < 0 || cap < 1)
-    return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (!b->forward_done) return fail(HX_ERR_STATE, "hx_batch_sample_traces needs a previous hx_batch_forward");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, uniforms && cells && n_cells && draws_used && n_walks >= 1 && n_uniforms >= 0 && cap >= 1, &job,
+                                  NEED_FORWARD, "hx_batch_sample_traces needs a previous hx_batch_forward"))
+    return rc;
   struct Dev {                                       // released on every way out
     void* p = nullptr;
     ~Dev() { if (p) (void)hipFree(p); }
@@ -1914,10 +1944,9 @@ int hx_batch_sample_traces(hx_batch* b, int32_t job, int32_t n_walks, const doub
 }
 
 int hx_batch_indel_counts(hx_batch* b, int32_t job, const double* branch_times, double* out) {
-  if (!b || !branch_times || !out) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (!b->forward_done || !b->backward_done) return fail(HX_ERR_STATE, "hx_batch_indel_counts needs the Forward and the Backward fill");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, branch_times && out, &job, NEED_FORWARD | NEED_BACKWARD,
+                                  "hx_batch_indel_counts needs the Forward and the Backward fill"))
+    return rc;
   hipStream_t st = b->last_stream;
   double* d = nullptr;
   if (hipMalloc(reinterpret_cast<void**>(&d), 12 * sizeof(double)) != hipSuccess) return fail(HX_ERR_OUT_OF_MEMORY, "device allocation failed");
@@ -1940,9 +1969,7 @@ int hx_batch_indel_counts(hx_batch* b, int32_t job, const double* branch_times, 
 int hx_batch_read_prepared(hx_batch* b, int32_t job, double* subx, double* suby, double* insx, double* rootsubx,
                            double* insy, double* rootsuby) {
   if (!b) return fail(HX_ERR_INVALID_ARG, "batch is null");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (!b->forward_done) return fail(HX_ERR_STATE, "hx_batch_forward has not been launched");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, true, &job, NEED_FORWARD, "hx_batch_forward has not been launched")) return rc;
   if ((subx || suby) && !b->sub_scattered) {
     // the fills use per-class tables; the per-state leftMultiply rows are produced when somebody asks for them
     launch_scatter_sub(b->d_jobs, b->n_jobs, b->max_states, b->last_stream);
@@ -1961,10 +1988,9 @@ int hx_batch_read_prepared(hx_batch* b, int32_t job, double* subx, double* suby,
 }
 
 int hx_batch_posterior_scan(hx_batch* b, int32_t job, double min_post_prob, hx_cell* out, int64_t cap, int64_t* n_out) {
-  if (!b || !n_out || cap < 0 || (cap > 0 && !out)) return fail(HX_ERR_INVALID_ARG, "bad arguments");
-  if (job < 0 || job >= b->n_jobs) return fail(HX_ERR_RANGE, "job %d out of range", job);
-  if (!b->forward_done || !b->backward_done) return fail(HX_ERR_STATE, "posterior scan needs Forward and Backward fills");
-  { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
+  if (const int rc = open_reader(b, n_out && cap >= 0 && (cap == 0 || out), &job, NEED_FORWARD | NEED_BACKWARD,
+                                  "posterior scan needs Forward and Backward fills"))
+    return rc;
   static_assert(sizeof(PostCell) == sizeof(hx_cell), "hx_cell layout");
   const double thr = std::log(min_post_prob);   // host libm, as reference src/forward.cpp:1304
   PostCell* d_out = nullptr;

@@ -2,8 +2,8 @@
 // state i has the single in-transition i-1 -> i): reference src/forward.cpp:68-223
 // specialised to in-degree 1, with the ready/wait/null flags and the envelope kept.
 //
-// One workgroup per pair.  The matrix is swept in row passes of THREADS*RPT rows; every
-// lane owns RPT consecutive rows and at step d computes its cells on anti-diagonal d.
+// One workgroup per pair.  The matrix is swept in row passes of THREADS rows; every
+// lane owns one row and at step d computes its cell on anti-diagonal d.
 // The three predecessor cells of a cell are
 //   left  (i, j-1)   : the lane's own value from step d-1           (registers)
 //   up    (i-1, j)   : the row above, step d-1  (registers, or lane-1 via DPP wave_shr)
@@ -11,7 +11,7 @@
 // so no DP cell is re-read from memory, except the one boundary row between two row
 // passes (block-loaded 64 columns at a time).  The only cross-wave traffic is lane 63's
 // last row -> next wave's lane 0 through a double-buffered LDS slot, one s_barrier per
-// anti-diagonal.  Each step a wave stores RPT*64 consecutive doubles per state plane
+// anti-diagonal.  Each step a wave stores 64 consecutive doubles per state plane
 // (strip-skewed layout, hx_device.h): fully coalesced, write-once 40 B/cell.
 //
 // Two log-sum-exp policies:
@@ -132,7 +132,7 @@ __device__ __forceinline__ C5 chain_cell(const DevJob& J, const LSE& L, const XR
   return r;
 }
 
-// Strip pipeline.  A workgroup of W waves owns one pair; 64*RPT-row strips are dealt to
+// Strip pipeline.  A workgroup of W waves owns one pair; 64-row strips are dealt to
 // its waves round-robin and every wave sweeps its strip left to right on its own clock
 // (no workgroup barrier in the loop).  A strip's only input from the strip above is that
 // strip's last row, which the wave above has already written to the matrix: the consumer
@@ -157,14 +157,14 @@ __device__ __forceinline__ C5 chain_cell(const DevJob& J, const LSE& L, const XR
 // and are written / polled with `sc1` accesses behind the storing wave's own s_waitcnt - the hand-off of hx_dag.hip's
 // lone-pair launches.  A poll gives up after HX_CHAIN_PATIENCE rounds and the pair's lpEnd / lpStart becomes NaN.
 #define HX_CHAIN_PATIENCE (1 << 22)
-template <int DIR, int RPT, int W, class LSE, bool FAST, bool LEAF, bool YL, bool BANDED, int MINW = 1, int PPW = 1, bool MULTI = false>
+template <int DIR, int W, class LSE, bool FAST, bool LEAF, bool YL, bool BANDED, int MINW = 1, int PPW = 1, bool MULTI = false>
 __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob* __restrict__ jobs,
                                                                       const double* __restrict__ exact_tab,
                                                                       const double* __restrict__ fast_tab, const int n_jobs, const int yl_emis,
                                                                       const int groups = 1, int* const counters = nullptr) {
-  static_assert(!MULTI || (PPW == 1 && !BANDED && RPT == 1), "several workgroups per pair: unbanded pairs, one pair per workgroup");
+  static_assert(!MULTI || (PPW == 1 && !BANDED), "several workgroups per pair: unbanded pairs, one pair per workgroup");
   constexpr int THREADS = W * PPW * 64;
-  constexpr int SR = 64 * RPT;                      // rows per strip
+  constexpr int SR = 64;                           // rows per strip
   static_assert(PPW == 1 || !YL, "the LDS-resident y side belongs to one pair");
   __shared__ volatile int prog[W * PPW];
   // FAST: the 4096-piece table.  Exact, one pair per workgroup: the head of the reference's table (differences
@@ -266,53 +266,49 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
 
   for (int s = gw; s < n_strips; s += WT) {
     const int row0 = s * SR;
-    const int i0 = row0 + lane * RPT;              // first row of this lane
-    XRow X[RPT];
-    XLeaf XL[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) {
-      const int i = i0 + k;                      // row in sweep coordinates (mirrored for Backward)
-      X[k].valid = i < R;
-      const int ic = X[k].valid ? (DIR ? R - 1 - i : i) : 0;   // actual x state
+    const int i0 = row0 + lane;                    // the lane's row in sweep coordinates (mirrored for Backward)
+    XRow X;
+    XLeaf XL;
+    {
+      X.valid = i0 < R;
+      const int ic = X.valid ? (DIR ? R - 1 - i0 : i0) : 0;   // actual x state
       if (LEAF) {
         const d4v p = xpack[ic];
         if (DIR == 0) {
-          XL[k].lp = p.x; XL[k].rootsub = p.y; XL[k].ins = p.z; XL[k].pen = p.w;
-          XL[k].eoff = (unsigned)J.x.ecls[ic] * (unsigned)(J.y.n_cls + 1);
+          XL.lp = p.x; XL.rootsub = p.y; XL.ins = p.z; XL.pen = p.w;
+          XL.eoff = (unsigned)J.x.ecls[ic] * (unsigned)(J.y.n_cls + 1);
         } else {
           const d4v q = xpack[ic + 1];             // the state the absorbing transition leads to
-          XL[k].lp = q.x; XL[k].rootsub = q.y; XL[k].ins = q.z; XL[k].pen = p.w;
-          XL[k].eoff = (unsigned)J.x.ecls[ic + 1] * (unsigned)(J.y.n_cls + 1);
+          XL.lp = q.x; XL.rootsub = q.y; XL.ins = q.z; XL.pen = p.w;
+          XL.eoff = (unsigned)J.x.ecls[ic + 1] * (unsigned)(J.y.n_cls + 1);
         }
-        XL[k].valid = X[k].valid;
+        XL.valid = X.valid;
       }
-      X[k].flags = J.x.flags[ic];
-      X[k].lp = ic > 0 ? J.x.in_lp[ic - 1] : 0.0;      // (chain_cell path, Forward only)
-      X[k].rootsub = J.x.rootsub[ic];
-      X[k].ins = J.x.ins[ic];
-      X[k].env = (J.max_dist >= 0) ? J.x.env[ic] : 0;
+      X.flags = J.x.flags[ic];
+      X.lp = ic > 0 ? J.x.in_lp[ic - 1] : 0.0;      // (chain_cell path, Forward only)
+      X.rootsub = J.x.rootsub[ic];
+      X.ins = J.x.ins[ic];
+      X.env = (J.max_dist >= 0) ? J.x.env[ic] : 0;
       const int cx = J.x.cls[ic];
-      X[k].emis_off = cx < 0 ? -1 : cx * J.y.n_cls;
+      X.emis_off = cx < 0 ? -1 : cx * J.y.n_cls;
     }
     // Register window, ping-ponged between two sets so that no value is ever copied: at an even step
-    // the lane's previous cells are in cb[] (and those of two steps ago in ca[], which the new cells
-    // overwrite); the previous lane's last row of one / two steps ago is in ua / ub, and the new
+    // the lane's previous cell is in cb (and that of two steps ago in ca, which the new cell
+    // overwrites); the previous lane's row of one / two steps ago is in ua / ub, and the new
     // shifted-in row overwrites ub.  The next (odd) step swaps the roles.
-    C5 ca[RPT], cb[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; ++k) { ca[k] = c5_neg_inf(); cb[k] = c5_neg_inf(); }
+    C5 ca = c5_neg_inf(), cb = c5_neg_inf();
     C5 ua = c5_neg_inf(), ub = c5_neg_inf();
     C5 bnd = c5_neg_inf();                         // 64 columns of the strip above's last row
     const bool has_above = s > 0;
     const int above_base = ((s - 1) / WT) * Cc;    // columns the producer wave published in earlier strips
     const int my_base = (s / WT) * Cc;
-    // strip-skewed store base (hx_device.h cell_slot): a lane's rows are adjacent pairs
+    // strip-skewed store base (hx_device.h cell_slot): a row's cells are adjacent pairs
     const int strip64 = i0 >> 6;
     const int64_t store_base2 = (int64_t)strip64 * ss + ((i0 & 63) << 1);
     const int t_off = row0 - (strip64 << 6) + 0;   // t64 = j + (i & 63) = step + t_off  (see below)
     const bool store_rows = i0 < ((R + 63) & ~63);
     // band-compressed planes (HX_BAND_COMPRESSED, Forward): a window's cells are stored from the window's own offset
-    const int64_t* sbase = (BANDED && RPT == 1 && DIR == 0) ? J.strip_base : nullptr;
+    const int64_t* sbase = (BANDED && DIR == 0) ? J.strip_base : nullptr;
     int64_t cstore_base = 0;
     int cstore_t0 = 0;
 
@@ -320,7 +316,7 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
     // With a band, a strip only sweeps the step windows that hold its in-envelope cells (computed on
     // the host, hx_api.hip strip_windows; the matrix is pre-filled with -inf).  Windows are widened to
     // even bounds: a row's two cells of steps 2m, 2m+1 are stored together.
-    constexpr bool WIN = BANDED && RPT == 1;       // (without it everything below folds to one full sweep)
+    constexpr bool WIN = BANDED;                   // (without it everything below folds to one full sweep)
     int wlo[2] = {0, 0}, whi[2] = {nsteps, 0};
     if (WIN) {
       const HX_GLOBAL int32_t* win = as_global(DIR ? J.bwd_windows : J.fwd_windows);
@@ -344,9 +340,8 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
       dd = dd < 0 ? -dd : dd;
       return dd <= J.max_dist;
     };
-    // one anti-diagonal step of the strip; the lane's RPT new cells are returned in out[]
-    auto step = [&](const int t, const C5 (&left)[RPT], C5 (&out)[RPT], C5& u1, C5& u2, const d4v (&Yp)[RPT],
-                    const double (&ep)[RPT]) {
+    // one anti-diagonal step of the strip; the lane's new cell is returned in out
+    auto step = [&](const int t, const C5& left, C5& out, C5& u1, C5& u2, const d4v& Yp, const double& ep) {
       if (has_above) {
         if (((t & 63) == 0 || (WIN && t == wstart)) && t < Cc) {
           // wait until the strip above has finished (and drained) the 64-column block that holds column t
@@ -377,50 +372,40 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
         if (t >= Cc) a = c5_neg_inf();
         if (lane == 0) u1 = a;                     // (row0-1, t); u2 already holds (row0-1, t-1)
       }
-      // rows in descending order: row k reads row k-1's old values, so each row's window can
-      // be rotated as soon as its new cell is known
-      C5 last = c5_neg_inf();
-#pragma unroll
-      for (int k = RPT - 1; k >= 0; --k) {
-        const int i = i0 + k;
-        const int j = t - (lane * RPT + k);
-        const bool valid = X[k].valid && j >= 0 && j < Cc;
-        const int jm = j < 0 ? 0 : (j >= Cc ? Cc - 1 : j);
-        const int jc = DIR ? Cc - 1 - jm : jm;       // actual y state
-        const C5& up = (k == 0) ? u1 : left[k - 1];
-        const C5& dg = (k == 0) ? u2 : out[k - 1];   // still the value of two steps ago: rows go in descending order
-        C5 nw;
-        if (LEAF) {
-          bool ok = valid;
-          if (BANDED || !LEAF) if (J.max_dist >= 0) {
-            const uint8_t ef = X[k].flags | yflags[jc];
-            int dd = X[k].env - yenv[jc];
-            dd = dd < 0 ? -dd : dd;
-            ok = ok && ((ef & F_EDGE) || dd <= J.max_dist);
-          }
-          const double pj = ok ? 0.0 : HX_NEG_INF;
-          if (DIR == 0) {
-            nw = leaf_cell(Tk, L, XL[k], Yp[k], ep[k], pj, up, left[k], dg);
-            if (s == 0 && t == 0 && k == 0) {        // wave-uniform: only the very first step of strip 0
-              if (lane == 0) nw.imm = 0.0;           // cell (0,0): lpStart() = 0 (reference src/forward.cpp:73)
-            }
-          } else {
-            nw = leaf_cell_bwd(Tk, L, XL[k], Yp[k], ep[k], pj, up, left[k], dg);
-            if (s == 0 && t == 0 && k == 0 && lane == 0) {
-              // the cell feeding END is initialised by assignment (reference src/forward.cpp:981-995)
-              const double lpe = J.x.pack[4 * (size_t)R] + J.y.pack[4 * (size_t)Cc];
-              nw = C5{lpe + J.T[0][5], lpe + J.T[1][5], lpe + J.T[2][5], lpe + J.T[3][5], lpe + J.T[4][5]};
-            }
+      const int j = t - lane;
+      const bool valid = X.valid && j >= 0 && j < Cc;
+      const int jm = j < 0 ? 0 : (j >= Cc ? Cc - 1 : j);
+      const int jc = DIR ? Cc - 1 - jm : jm;         // actual y state
+      C5 nw;
+      if (LEAF) {
+        bool ok = valid;
+        if (BANDED || !LEAF) if (J.max_dist >= 0) {
+          const uint8_t ef = X.flags | yflags[jc];
+          int dd = X.env - yenv[jc];
+          dd = dd < 0 ? -dd : dd;
+          ok = ok && ((ef & F_EDGE) || dd <= J.max_dist);
+        }
+        const double pj = ok ? 0.0 : HX_NEG_INF;
+        if (DIR == 0) {
+          nw = leaf_cell(Tk, L, XL, Yp, ep, pj, u1, left, u2);
+          if (s == 0 && t == 0) {                    // wave-uniform: only the very first step of strip 0
+            if (lane == 0) nw.imm = 0.0;             // cell (0,0): lpStart() = 0 (reference src/forward.cpp:73)
           }
         } else {
-          nw = chain_cell(J, L, X[k], X[k].valid ? i : 0, jc, valid, up, left[k], dg);
+          nw = leaf_cell_bwd(Tk, L, XL, Yp, ep, pj, u1, left, u2);
+          if (s == 0 && t == 0 && lane == 0) {
+            // the cell feeding END is initialised by assignment (reference src/forward.cpp:981-995)
+            const double lpe = J.x.pack[4 * (size_t)R] + J.y.pack[4 * (size_t)Cc];
+            nw = C5{lpe + J.T[0][5], lpe + J.T[1][5], lpe + J.T[2][5], lpe + J.T[3][5], lpe + J.T[4][5]};
+          }
         }
-        if (k == RPT - 1) last = nw;
-        out[k] = nw;
+      } else {
+        nw = chain_cell(J, L, X, X.valid ? i0 : 0, jc, valid, u1, left, u2);
       }
-      // the previous lane's new last row lands in the u2 slot, which becomes next step's u1
+      out = nw;
+      // the previous lane's new cell lands in the u2 slot, which becomes next step's u1
       // (lane 0 keeps the old content; it is re-filled from the boundary block when there is a strip above)
-      u2 = wave_shr1_keep0(u2, last);
+      u2 = wave_shr1_keep0(u2, nw);
     };
 
     // y-side constants and emission terms of step t, fetched ahead of use: vector-memory
@@ -428,58 +413,51 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
     // would wait for those stores to reach memory; issued before them it does not.
     // YL: per-row column word of the next step (and, for Backward, the word of the column the previous
     // step visited: in mirrored order that is actual column j+1, whose class the absorbing move needs)
-    unsigned wnext[RPT], wprev1[RPT];
+    unsigned wnext = 0u, wprev1 = 0u;
     auto init_words = [&](const int t0) {
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int j0 = t0 - (lane * RPT + k);
-        const int jm0 = j0 < 0 ? 0 : (j0 >= Cc ? Cc - 1 : j0);
-        wnext[k] = YL ? ycol[DIR ? Cc - 1 - jm0 : jm0] : 0u;
-        // Backward: the word of the column visited one step earlier (actual column j+1)
-        wprev1[k] = YL ? ycol[DIR ? Cc - jm0 : 0] : 0u;
-      }
+      const int j0 = t0 - lane;
+      const int jm0 = j0 < 0 ? 0 : (j0 >= Cc ? Cc - 1 : j0);
+      wnext = YL ? ycol[DIR ? Cc - 1 - jm0 : jm0] : 0u;
+      // Backward: the word of the column visited one step earlier (actual column j+1)
+      wprev1 = YL ? ycol[DIR ? Cc - jm0 : 0] : 0u;
     };
-    auto prefetch = [&](const int t, d4v (&Yp)[RPT], double (&ep)[RPT]) {
+    auto prefetch = [&](const int t, d4v& Yp, double& ep) {
       if (!LEAF) return;
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int j = t - (lane * RPT + k);
-        const int jm = j < 0 ? 0 : (j >= Cc ? Cc - 1 : j);
-        const int jc = DIR ? Cc - 1 - jm : jm;       // actual y state
-        if (YL) {
-          // the column word was fetched one step ahead (wnext); fetch the next one now
-          const unsigned w = wnext[k];
-          {
-            const int jn = j + 1;
-            const int jnm = jn < 0 ? 0 : (jn >= Cc ? Cc - 1 : jn);
-            wnext[k] = ycol[DIR ? Cc - 1 - jnm : jnm];
-          }
-          const unsigned c = (DIR ? wprev1[k] : w) & 0xFFFFu;
-          if (DIR && j >= 0) wprev1[k] = w;    // (before the row starts, the clamped column is not a visit)
-          const double2 rc = reinterpret_cast<const double2*>(yclass)[c];
-          Yp[k] = d4v{0.0, rc.x, rc.y, __hiloint2double((w & 0x10000u) ? (int)0xFFF00000 : 0, 0)};
-          ep[k] = elds[XL[k].eoff + c];
-          continue;
+      const int j = t - lane;
+      const int jm = j < 0 ? 0 : (j >= Cc ? Cc - 1 : j);
+      const int jc = DIR ? Cc - 1 - jm : jm;         // actual y state
+      if (YL) {
+        // the column word was fetched one step ahead (wnext); fetch the next one now
+        const unsigned w = wnext;
+        {
+          const int jn = j + 1;
+          const int jnm = jn < 0 ? 0 : (jn >= Cc ? Cc - 1 : jn);
+          wnext = ycol[DIR ? Cc - 1 - jnm : jnm];
         }
-        if (DIR) {
-          const d4v y0 = ypack[(unsigned)jc], y1 = ypack[(unsigned)jc + 1];
-          Yp[k] = d4v{y1.x, y1.y, y1.z, y0.w};
-          ep[k] = epad[XL[k].eoff + (unsigned)yecls[(unsigned)jc + 1]];
-          continue;
-        }
-        Yp[k] = ypack[(unsigned)jc];
-        ep[k] = epad[XL[k].eoff + (unsigned)yecls[(unsigned)jc]];
+        const unsigned c = (DIR ? wprev1 : w) & 0xFFFFu;
+        if (DIR && j >= 0) wprev1 = w;             // (before the row starts, the clamped column is not a visit)
+        const double2 rc = reinterpret_cast<const double2*>(yclass)[c];
+        Yp = d4v{0.0, rc.x, rc.y, __hiloint2double((w & 0x10000u) ? (int)0xFFF00000 : 0, 0)};
+        ep = elds[XL.eoff + c];
+        return;
       }
+      if (DIR) {
+        const d4v y0 = ypack[(unsigned)jc], y1 = ypack[(unsigned)jc + 1];
+        Yp = d4v{y1.x, y1.y, y1.z, y0.w};
+        ep = epad[XL.eoff + (unsigned)yecls[(unsigned)jc + 1]];
+        return;
+      }
+      Yp = ypack[(unsigned)jc];
+      ep = epad[XL.eoff + (unsigned)yecls[(unsigned)jc]];
     };
-    d4v Ya[RPT], Yb[RPT];
-    double ea[RPT], eb[RPT];
+    d4v Ya, Yb;
+    double ea, eb;
     for (int w = 0; w < (WIN ? 2 : 1); ++w) {
     if (WIN && whi[w] <= wlo[w]) continue;
     wstart = WIN ? wlo[w] : 0;
     if (WIN && w > 0) {
       // cells left of a window are outside the envelope: the register window restarts from -inf
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) { ca[k] = c5_neg_inf(); cb[k] = c5_neg_inf(); }
+      ca = c5_neg_inf(); cb = c5_neg_inf();
       ua = c5_neg_inf(); ub = c5_neg_inf(); bnd = c5_neg_inf();
     }
     if (WIN && has_above && wstart > 0 && wstart <= Cc) {
@@ -506,12 +484,10 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
     }
 
     // Two steps per iteration: in the strip-skewed layout the two cells a row produces on
-    // consecutive anti-diagonals are adjacent, so a lane stores RPT*16 contiguous bytes per
-    // state plane every second step (a wave: RPT KiB, fully coalesced).
+    // consecutive anti-diagonals are adjacent, so a lane stores 16 contiguous bytes per
+    // state plane every second step (a wave: 1 KiB, fully coalesced).
     const int wend = WIN ? whi[w] : nsteps;
     for (int t = wstart; t < wend; t += 2) {
-      C5 (&oa)[RPT] = ca;
-      C5 (&ob)[RPT] = cb;
       if (YL) prefetch(t, Ya, ea);
       step(t, cb, ca, ua, ub, Ya, ea);
       if (t + 1 < wend) {
@@ -528,33 +504,30 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
         const int64_t sl = sbase ? cstore_base + ((int64_t)((t - cstore_t0) >> 1) << 7) : store_base2 + ((int64_t)(t64 >> 1) << 7);
         HX_GLOBAL d2v* M2 = (HX_GLOBAL d2v*)(M + sl);
         const int64_t plane2 = plane >> 1;
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-          if (MULTI) {
-            // the strip below may run on another XCD: write-through stores (never `nt`, which stays in this XCD's L2)
-            const d2v v0{oa[k].imm, ob[k].imm}, v1{oa[k].imd, ob[k].imd}, v2{oa[k].idm, ob[k].idm}, v3{oa[k].imi, ob[k].imi}, v4{oa[k].iiw, ob[k].iiw};
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[k]), "v"(v0) : "memory");
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[plane2 + k]), "v"(v1) : "memory");
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[2 * plane2 + k]), "v"(v2) : "memory");
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[3 * plane2 + k]), "v"(v3) : "memory");
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[4 * plane2 + k]), "v"(v4) : "memory");
-            continue;
-          }
+        if (MULTI) {
+          // the strip below may run on another XCD: write-through stores (never `nt`, which stays in this XCD's L2)
+          const d2v v0{ca.imm, cb.imm}, v1{ca.imd, cb.imd}, v2{ca.idm, cb.idm}, v3{ca.imi, cb.imi}, v4{ca.iiw, cb.iiw};
+          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[0]), "v"(v0) : "memory");
+          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[plane2]), "v"(v1) : "memory");
+          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[2 * plane2]), "v"(v2) : "memory");
+          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[3 * plane2]), "v"(v3) : "memory");
+          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[4 * plane2]), "v"(v4) : "memory");
+        } else {
           // write-once data: non-temporal stores (the 1/64 of it that the strip below reads back comes from L2 or memory)
-          __builtin_nontemporal_store(d2v{oa[k].imm, ob[k].imm}, &M2[k]);
-          __builtin_nontemporal_store(d2v{oa[k].imd, ob[k].imd}, &M2[plane2 + k]);
-          __builtin_nontemporal_store(d2v{oa[k].idm, ob[k].idm}, &M2[2 * plane2 + k]);
-          __builtin_nontemporal_store(d2v{oa[k].imi, ob[k].imi}, &M2[3 * plane2 + k]);
-          __builtin_nontemporal_store(d2v{oa[k].iiw, ob[k].iiw}, &M2[4 * plane2 + k]);
+          __builtin_nontemporal_store(d2v{ca.imm, cb.imm}, &M2[0]);
+          __builtin_nontemporal_store(d2v{ca.imd, cb.imd}, &M2[plane2]);
+          __builtin_nontemporal_store(d2v{ca.idm, cb.idm}, &M2[2 * plane2]);
+          __builtin_nontemporal_store(d2v{ca.imi, cb.imi}, &M2[3 * plane2]);
+          __builtin_nontemporal_store(d2v{ca.iiw, cb.iiw}, &M2[4 * plane2]);
         }
       }
       // publish progress.  The strip's last row has finished column (t + 1) - (SR - 1); a
       // column counts as published once its stores have left the wave.  Vector-memory
       // operations retire in issue order and every iteration (two steps) issues at least its
-      // 5 * RPT stores (the LDS-resident-y path issues nothing else), so everything stored
+      // 5 stores (the LDS-resident-y path issues nothing else), so everything stored
       // HX_PUBLISH_LAG steps = HX_PUBLISH_LAG / 2 iterations ago is older than the wave's
       // PUBLISH_WAIT youngest operations.
-      constexpr int STORES_PER_ITER = 5 * RPT;
+      constexpr int STORES_PER_ITER = 5;
       constexpr int PUBLISH_WAIT = STORES_PER_ITER * (HX_PUBLISH_LAG / 2) < 63 ? STORES_PER_ITER * (HX_PUBLISH_LAG / 2) : 63;
       static_assert(PUBLISH_WAIT <= STORES_PER_ITER * (HX_PUBLISH_LAG / 2) && PUBLISH_WAIT <= 63 && HX_PUBLISH_LAG % 2 == 0,
                     "the wait count must not exceed the operations issued since the published column's stores");
@@ -608,7 +581,7 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
   }
 }
 
-template <int DIR, int RPT, int W, int MINW = 1>
+template <int DIR, int W, int MINW = 1>
 static int launch_variant(const DevJob* d_jobs, int n_jobs, const double* tab, const double* fast_tab, bool fast,
                            int leaf, bool banded, int yl_cols, int yl_emis, hipStream_t st) {
   const dim3 g(n_jobs), b(W * 64);
@@ -617,8 +590,8 @@ static int launch_variant(const DevJob* d_jobs, int n_jobs, const double* tab, c
   if (leaf == 2 && (yl_cols > HX_YL_MAX_COLS || yl_emis > HX_YL_MAX_EMIS + 2))
     return launch_fail("LDS-resident y side of %d columns / %d class pairs exceeds the chain kernel's tables", yl_cols, yl_emis);
 #define HX_LAUNCH(LSE_, FAST_, LEAF_, YL_, BANDED_) do { \
-  HX_CHECK_LDS((k_fill_chain<DIR, RPT, W, LSE_, FAST_, LEAF_, YL_, BANDED_, MINW>), dyn, "k_fill_chain"); \
-  hipLaunchKernelGGL((k_fill_chain<DIR, RPT, W, LSE_, FAST_, LEAF_, YL_, BANDED_, MINW>), g, b, dyn, st, d_jobs, tab, fast_tab, n_jobs, yl_emis); } while (0)
+  HX_CHECK_LDS((k_fill_chain<DIR, W, LSE_, FAST_, LEAF_, YL_, BANDED_, MINW>), dyn, "k_fill_chain"); \
+  hipLaunchKernelGGL((k_fill_chain<DIR, W, LSE_, FAST_, LEAF_, YL_, BANDED_, MINW>), g, b, dyn, st, d_jobs, tab, fast_tab, n_jobs, yl_emis); } while (0)
   if (leaf == 2 && !banded) {             // the headline configuration: unbanded leaf pairs, y side in LDS
     if (fast) HX_LAUNCH(FastLse, true, true, true, false); else HX_LAUNCH(ExactLse3, false, true, true, false);
   } else if (leaf == 2) {
@@ -627,9 +600,9 @@ static int launch_variant(const DevJob* d_jobs, int n_jobs, const double* tab, c
     if (fast) HX_LAUNCH(FastLse, true, true, false, true); else HX_LAUNCH(ExactLse3, false, true, false, true);
   } else if (DIR == 0) {
     if (fast)
-      hipLaunchKernelGGL((k_fill_chain<0, RPT, W, FastLse, true, false, false, true, MINW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
+      hipLaunchKernelGGL((k_fill_chain<0, W, FastLse, true, false, false, true, MINW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
     else
-      hipLaunchKernelGGL((k_fill_chain<0, RPT, W, ExactLse3, false, false, false, true, MINW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
+      hipLaunchKernelGGL((k_fill_chain<0, W, ExactLse3, false, false, false, true, MINW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
   } else {
     return launch_fail("the Backward strip pipeline exists for leaf-like profiles only");
   }
@@ -644,9 +617,9 @@ static void launch_banded_leaf_ppw(const DevJob* d_jobs, int n_jobs, const doubl
                                    hipStream_t st) {
   const dim3 g((n_jobs + PPW - 1) / PPW), b(PPW * 64);
   if (fast)
-    hipLaunchKernelGGL((k_fill_chain<DIR, 1, 1, FastLse, true, true, false, true, 1, PPW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
+    hipLaunchKernelGGL((k_fill_chain<DIR, 1, FastLse, true, true, false, true, 1, PPW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
   else
-    hipLaunchKernelGGL((k_fill_chain<DIR, 1, 1, ExactLse3, false, true, false, true, 1, PPW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
+    hipLaunchKernelGGL((k_fill_chain<DIR, 1, ExactLse3, false, true, false, true, 1, PPW>), g, b, 0, st, d_jobs, tab, fast_tab, n_jobs, 0);
 }
 template <int DIR>
 static void launch_banded_leaf(const DevJob* d_jobs, int n_jobs, const double* tab, const double* fast_tab, bool fast,
@@ -665,11 +638,11 @@ static int launch_chain_multi(const DevJob* d_jobs, int n_jobs, const double* ta
   if (yl_cols > HX_YL_MAX_COLS || yl_emis > HX_YL_MAX_EMIS + 2)
     return launch_fail("LDS-resident y side of %d columns / %d class pairs exceeds the chain kernel's tables", yl_cols, yl_emis);
   if (fast) {
-    HX_CHECK_LDS((k_fill_chain<DIR, 1, W, FastLse, true, true, true, false, 1, 1, true>), dyn, "k_fill_chain<multi>");
-    hipLaunchKernelGGL((k_fill_chain<DIR, 1, W, FastLse, true, true, true, false, 1, 1, true>), g, b, dyn, st, d_jobs, tab, fast_tab, n_jobs, yl_emis, multi, counters);
+    HX_CHECK_LDS((k_fill_chain<DIR, W, FastLse, true, true, true, false, 1, 1, true>), dyn, "k_fill_chain<multi>");
+    hipLaunchKernelGGL((k_fill_chain<DIR, W, FastLse, true, true, true, false, 1, 1, true>), g, b, dyn, st, d_jobs, tab, fast_tab, n_jobs, yl_emis, multi, counters);
   } else {
-    HX_CHECK_LDS((k_fill_chain<DIR, 1, W, ExactLse3, false, true, true, false, 1, 1, true>), dyn, "k_fill_chain<multi>");
-    hipLaunchKernelGGL((k_fill_chain<DIR, 1, W, ExactLse3, false, true, true, false, 1, 1, true>), g, b, dyn, st, d_jobs, tab, fast_tab, n_jobs, yl_emis, multi, counters);
+    HX_CHECK_LDS((k_fill_chain<DIR, W, ExactLse3, false, true, true, false, 1, 1, true>), dyn, "k_fill_chain<multi>");
+    hipLaunchKernelGGL((k_fill_chain<DIR, W, ExactLse3, false, true, true, false, 1, 1, true>), g, b, dyn, st, d_jobs, tab, fast_tab, n_jobs, yl_emis, multi, counters);
   }
   return 0;
 }
@@ -679,23 +652,19 @@ static int launch_chain(const DevJob* d_jobs, int n_jobs, int max_rows, const do
                          bool fast, int leaf, bool banded, int yl_cols, int yl_emis, int multi, int* counters, hipStream_t st) {
   if (multi > 1 && leaf == 2 && !banded)
     return launch_chain_multi<DIR>(d_jobs, n_jobs, tab, fast_tab, fast, yl_cols, yl_emis, multi, counters, st);
-  const char* v = getenv("HX_CHAIN_VARIANT");   // tuning hook: override for long profiles
-  const int vi = v ? atoi(v) : 0;
-  if (banded && leaf >= 1 && vi == 0 && n_jobs >= 64) {
+  if (banded && leaf >= 1 && n_jobs >= 64) {
     launch_banded_leaf<DIR>(d_jobs, n_jobs, tab, fast_tab, fast, st);
     return 0;
   }
   if (max_rows <= 64)
-    return launch_variant<DIR, 1, 1>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
+    return launch_variant<DIR, 1>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
   if (max_rows <= 128)
-    return launch_variant<DIR, 1, 2>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
+    return launch_variant<DIR, 2>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
   if (max_rows <= 256)
-    return launch_variant<DIR, 1, 4>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
-  if (vi == 2 || (vi == 0 && max_rows <= 512))
-    return launch_variant<DIR, 1, 8>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
-  if (vi == 4)
-    return launch_variant<DIR, 2, 4>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
-  return launch_variant<DIR, 1, 16>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);   // measured fastest on 2x2000
+    return launch_variant<DIR, 4>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
+  if (max_rows <= 512)
+    return launch_variant<DIR, 8>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);
+  return launch_variant<DIR, 16>(d_jobs, n_jobs, tab, fast_tab, fast, leaf, banded, yl_cols, yl_emis, st);   // measured fastest on 2x2000
 }
 
 // Workgroups per pair for a batch of n_jobs unbanded leaf pairs (y side in LDS) of up to max_rows rows: 1 = the ordinary launch.

@@ -1,6 +1,8 @@
 """Parity tests proper: the HIP path, called through the C ABI, against the oracle on
 the same seeded inputs.  Exact fill mode: every cell, lpEnd/lpStart and every prepared
 vector bit-identical (fp64 compared as uint64)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -264,6 +266,22 @@ def test_error_codes():
     with pytest.raises(capi.HxError) as e:
         b.job_kernel(1)                          # no such pair
     assert e.value.code == -8                    # HX_ERR_RANGE
+    b.close()
+    # every job index a reader is given is range-checked, the most negative int32 included (nothing is read for it)
+    b = capi.Batch([(x, y, hmm, md)], capi.HX_KEEP_BACKWARD)
+    b.forward()
+    b.backward()
+    lib, h, buf = capi.load(), b._h, np.zeros(1 << 16)
+    ptr = buf.ctypes.data_as(capi._f64p)
+    for job in (-(1 << 31), -1, 1, (1 << 31) - 1):
+        lay = capi.HxLayout()
+        assert lib.hx_batch_layout(h, job, 0, C.byref(lay)) == -8
+        assert lib.hx_batch_job_kernel(h, job, None, None) == -8
+        assert lib.hx_batch_read_matrix(h, job, 0, ptr) == -8
+        assert lib.hx_batch_read_matrix_async(h, job, 1, buf.ctypes.data) == -8
+        assert lib.hx_batch_wait_read(h, job, 0) == -8
+        assert lib.hx_batch_read_prepared(h, job, None, None, None, None, None, None) == -8
+        assert lib.hx_last_error().decode() == "job %d out of range" % job
     b.close()
     # non-toposorted transition
     bad = capi.ProfileImage(x.trans_src.copy(), x.trans_dst.copy(), x.trans_lp,
