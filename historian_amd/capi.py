@@ -87,7 +87,7 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_host_free", "hx_quick_batch_create", "hx_quick_batch_destroy", "hx_quick_batch_run",
            "hx_quick_batch_results", "hx_quick_batch_layout", "hx_quick_batch_read_matrix",
            "hx_quick_batch_total_cells", "hx_quick_batch_last_kernel_ms", "hx_sumprod_columns", "hx_sumprod_last_kernel_ms",
-           "hx_batch_read_matrix_async", "hx_batch_wait_read", "hx_batch_indel_counts", "hx_batch_shared_wavefront_pairs", "hx_batch_relaunches",
+           "hx_batch_read_matrix_async", "hx_batch_wait_read", "hx_batch_indel_counts", "hx_batch_event_counts", "hx_batch_shared_wavefront_pairs", "hx_batch_relaunches",
            "hx_branch_batch_create", "hx_branch_batch_destroy", "hx_branch_batch_run", "hx_branch_batch_results",
            "hx_branch_batch_read_matrix", "hx_branch_batch_total_cells", "hx_branch_batch_last_kernel_ms"]
 
@@ -161,6 +161,7 @@ def load():
     lib.hx_batch_read_matrix_async.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
     lib.hx_batch_indel_counts.argtypes = [vp, C.c_int32, _f64p, _f64p]
+    lib.hx_batch_event_counts.argtypes = [vp, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]
     _lib = lib
     return lib
 
@@ -375,6 +376,20 @@ class Batch:
         out = np.zeros(6)
         _check(load().hx_batch_indel_counts(self._h, job, _p(tm, _f64p), _p(out, _f64p)))
         return dict(zip(("ins", "del", "insExt", "delExt", "insTime", "delTime"), out.tolist()))
+
+    def event_counts(self, job, branch_times, x_counts=None, y_counts=None):
+        """hx_batch_event_counts: the indel counts of indel_counts plus the counts carried by the profiles' transitions
+        (x_counts / y_counts: [n_trans][6] by transition index, or None) -> (dict of the six counts, x_post [n_trans],
+        y_post [n_trans]): the posterior probability of each profile transition"""
+        nx, ny = (len(self._keep[job][0].trans_src), len(self._keep[job][1].trans_src)) if 0 <= job < self.n else (0, 0)
+        tm = np.ascontiguousarray(branch_times, dtype=np.float64)
+        xc = None if x_counts is None else np.ascontiguousarray(x_counts, dtype=np.float64).reshape(nx, 6)
+        yc = None if y_counts is None else np.ascontiguousarray(y_counts, dtype=np.float64).reshape(ny, 6)
+        out = np.zeros(6)
+        x_post, y_post = np.zeros(nx), np.zeros(ny)
+        _check(load().hx_batch_event_counts(self._h, job, _p(xc, _f64p), _p(yc, _f64p), _p(tm, _f64p), _p(out, _f64p),
+                                            _p(x_post, _f64p), _p(y_post, _f64p)))
+        return dict(zip(("ins", "del", "insExt", "delExt", "insTime", "delTime"), out.tolist())), x_post, y_post
 
     def strip_windows(self, job):
         l = self.layout(job)

@@ -17,8 +17,10 @@
 //   src/profile.h                          ProfileTransition, ProfileState, Profile
 //   src/pairhmm.h                          PairHMM
 //   src/forward.h                          DPMatrix, ForwardMatrix, BackwardMatrix
-// Out of scope: event/eigen counts -- the CountSubstEvents /
-// CountIndelEvents strategy bits are accepted and ignored, SumProduct* must be NULL.
+// Counts: the indel half is built -- CountIndelEvents makes profile transitions carry IndelCounts,
+// BackwardMatrix::getCounts returns the root's IndelCounts (device entry hx_batch_event_counts), and the Reconstructor
+// counts and fits indel rates (count / fit with fixed substitution rates).  The substitution half is not: the
+// CountSubstEvents bit is accepted and ignored, and SumProduct* must be NULL.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -220,6 +222,7 @@ struct RateModel : AlphabetOwner {
 struct ProbModel : AlphabetOwner {
   double t;                                  // branch length, and what the rates come to over it
   double ins, del, insExt, delExt;
+  double insWait, delWait;                   // IndelCounts::decayWaitTime of the two rates over t (src/model.cpp:381-382)
   vguard<Mat> subMat;
   vguard<Vec> insVec;
   vguard<double> cptWeight;
@@ -234,6 +237,22 @@ struct LogProbModel {
   int components() const { return static_cast<int>(logCptWeight.size()); }
 };
 
+// ---- src/model.h:165-178: expected indel events and waiting times -------------------------------
+struct IndelCounts {
+  double ins, del, insExt, delExt, insTime, delTime;
+  LogProb lp;
+  IndelCounts(double pseudocount = 0, double pseudotime = 0);
+  IndelCounts operator+(const IndelCounts& c) const;
+  IndelCounts operator*(double w) const;
+  IndelCounts& operator+=(const IndelCounts& c);
+  IndelCounts& operator*=(double w);
+  // the gamma / beta log-densities of the model's indel rates under these counts (EventCounts::logPrior, src/model.cpp:1060-1067)
+  double logPrior(const RateModel& model) const;
+  // the M-step for the indel rates (EventCounts::optimize, src/model.cpp:1053-1058)
+  void optimize(RateModel& model) const;
+  static double decayWaitTime(double decayRate, double timeInterval);   // src/model.cpp:1106-1108
+};
+
 // ---- src/profile.h --------------------------------------------------------------------------
 using ProfileStateIndex = size_t;
 using ProfileTransitionIndex = size_t;
@@ -242,6 +261,7 @@ struct ProfileTransition {
   ProfileStateIndex src, dest;
   AlignPath alignPath;               // the alignment columns the transition steps over
   LogProb lpTrans;
+  IndelCounts counts;                // CountIndelEvents: the expected events of the paths the transition sums
   ProfileTransition();
 };
 
@@ -475,6 +495,7 @@ public:
   struct EffectiveTransition {
     AlignPath bestAlignPath;
     LogProb lpBestAlignPath, lpPath;
+    IndelCounts counts;
     EffectiveTransition();
   };
 
@@ -533,6 +554,7 @@ private:
   AlignPath traceAlignPath(const Path& cells) const;
   ProfileState::SeqCoords cellSeqCoords(const CellCoords& at) const;
   LogProb eliminatedLogProbInsert(const CellCoords& at) const;
+  IndelCounts transitionIndelCounts(const CellCoords& from, const CellCoords& to) const;   // src/forward.cpp:579-652, indel part
   friend class BackwardMatrix;
 
 private:
@@ -553,6 +575,9 @@ public:
   explicit BackwardMatrix(ForwardMatrix& forward);
 
   double transPostProb(const CellCoords& from, const CellCoords& to) const;
+  // the IndelCounts of BackwardMatrix::getCounts (src/forward.cpp:1183-1214), the profiles' carried counts included, on the
+  // device (hx_batch_event_counts); lp = lpEnd.  (The reference returns EigenCounts; the substitution half is not built.)
+  IndelCounts getCounts();
   double cellPostProb(const CellCoords& at) const;
   Path bestTrace(const CellCoords& from);
   std::priority_queue<CellPostProb> cellsAbovePostProbThreshold(double minPostProb) const;
@@ -607,6 +632,14 @@ struct Reconstructor {
   // are independent; tracebacks and sampling still run in node order, so the results are unchanged).
   bool batchReadyNodes;                  // default true
   double maxBatchLatticeCells;           // upper bound on the lattice cells of one batch (device memory); default 4e8
+  // count / fit with the substitution rates fixed (src/recon.cpp:1373-1410): profiles carry indel counts, the root is
+  // filled Forward and Backward and counted (no root traceback when reconstructRoot is false)
+  bool accumulateIndelCounts;            // default false
+  bool useLaplacePseudocounts;           // default true: priorCounts = IndelCounts(1, 1)
+  size_t maxEMIterations;                // default 100
+  double minEMImprovement;               // default .001
+  IndelCounts priorCounts, dataCounts, dataPlusPriorCounts;
+  vguard<LogProb> emLogLikelihood;       // fit: the log-likelihood (with the log-prior) of every EM iteration
 
   struct Dataset {
     ReconTree tree;
@@ -615,6 +648,7 @@ struct Reconstructor {
     AlignPath guide, path;               // guide: rows = leaf node indices, empty = no band; path: the result (root alignment)
     LogProb lpFinalFwd, lpFinalTrace;
     map<TreeNodeIndex, int> bandUsed;
+    IndelCounts indelCounts;             // accumulateIndelCounts: the root's expected indel events, lp = lpFinalFwd
     void prepareRecon();
     vguard<FastSeq> gappedRecon() const; // Alignment(ungapped, path).gapped()
   };
@@ -630,6 +664,8 @@ struct Reconstructor {
   void reconstruct(Dataset& family);
   void seedGenerator();
   void reconstructAll(vguard<Dataset*>& datasets);   // reference src/recon.cpp:1368-1372: every family
+  void countAll(vguard<Dataset*>& datasets);         // src/recon.cpp:1373-1383: reconstruct every family, sum dataCounts
+  void fit(vguard<Dataset*>& datasets);              // src/recon.cpp:1385-1410: EM over the indel rates of `model`
   static double familyCost(const Dataset& dataset);   // estimated lattice cells of a family's pair DPs
 };
 

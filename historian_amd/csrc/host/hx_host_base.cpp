@@ -455,8 +455,52 @@ vguard<Mat> RateModel::getSubProbMatrix(double t) const {
 
 ProbModel::ProbModel(const RateModel& model, double t)
     : AlphabetOwner(model), t(t), ins(1 - exp(-model.insRate * t)), del(1 - exp(-model.delRate * t)),
-      insExt(model.insExtProb), delExt(model.delExtProb), subMat(model.getSubProbMatrix(t)), insVec(model.insProb),
+      insExt(model.insExtProb), delExt(model.delExtProb), insWait(IndelCounts::decayWaitTime(model.insRate, t)),
+      delWait(IndelCounts::decayWaitTime(model.delRate, t)), subMat(model.getSubProbMatrix(t)), insVec(model.insProb),
       cptWeight(model.cptWeight) {}
+
+// ---- IndelCounts (reference src/model.cpp:702-744, 1053-1067, 1106-1108) ---------------------------------------------
+IndelCounts::IndelCounts(double pseudocount, double pseudotime)
+    : ins(pseudocount), del(pseudocount), insExt(pseudocount), delExt(pseudocount), insTime(pseudotime), delTime(pseudotime), lp(0) {}
+
+IndelCounts& IndelCounts::operator+=(const IndelCounts& c) {
+  ins += c.ins; del += c.del; insExt += c.insExt; delExt += c.delExt; insTime += c.insTime; delTime += c.delTime; lp += c.lp;
+  return *this;
+}
+
+IndelCounts& IndelCounts::operator*=(double w) {
+  ins *= w; del *= w; insExt *= w; delExt *= w; insTime *= w; delTime *= w; lp *= w;
+  return *this;
+}
+
+IndelCounts IndelCounts::operator+(const IndelCounts& c) const { IndelCounts r(*this); r += c; return r; }
+IndelCounts IndelCounts::operator*(double w) const { IndelCounts r(*this); r *= w; return r; }
+
+double IndelCounts::decayWaitTime(double decayRate, double timeInterval) {
+  return 1 / decayRate - timeInterval / (exp(decayRate * timeInterval) - 1);
+}
+
+// log gsl_ran_gamma_pdf(rate, events + 1, 1 / waitTime) and log gsl_ran_beta_pdf(prob, yes + 1, no + 1) (src/logsumexp.cpp:101-107)
+static double logGammaPdf(double rate, double events, double waitTime) {
+  const double a = events + 1;
+  return (a - 1) * log(rate) - rate * waitTime - lgamma(a) + a * log(waitTime);
+}
+static double logBetaPdf(double prob, double yes, double no) {
+  const double a = yes + 1, b = no + 1;
+  return lgamma(a + b) - lgamma(a) - lgamma(b) + (a - 1) * log(prob) + (b - 1) * log(1 - prob);
+}
+
+double IndelCounts::logPrior(const RateModel& model) const {
+  return logGammaPdf(model.insRate, ins, insTime) + logGammaPdf(model.delRate, del, delTime) + logBetaPdf(model.insExtProb, insExt, ins) +
+         logBetaPdf(model.delExtProb, delExt, del);
+}
+
+void IndelCounts::optimize(RateModel& model) const {
+  model.insRate = ins / insTime;
+  model.delRate = del / delTime;
+  model.insExtProb = insExt / (insExt + ins);
+  model.delExtProb = delExt / (delExt + del);
+}
 
 LogProbModel::LogProbModel(const ProbModel& pm) : logInsProb(pm.components()), logCptWeight(pm.components()) {
   for (int c = 0; c < pm.components(); ++c) {

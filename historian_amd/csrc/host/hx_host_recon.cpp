@@ -34,7 +34,8 @@ void ReconTree::finish() {
 Reconstructor::Reconstructor()
     : maxDistanceFromGuide(20), profileSamples(10), profileMaxStates(0), includeBestTraceInProfile(true), keepGapsOpen(false),
       usePosteriorsForProfile(false), reconstructRoot(true), minPostProb(.01), rndSeed(std::mt19937::default_seed),
-      batchReadyNodes(true), maxBatchLatticeCells(4e8) {}
+      batchReadyNodes(true), maxBatchLatticeCells(4e8), accumulateIndelCounts(false), useLaplacePseudocounts(true),
+      maxEMIterations(100), minEMImprovement(.001) {}
 
 void Reconstructor::seedGenerator() { generator = DPMatrix::random_engine(rndSeed); }
 
@@ -71,8 +72,10 @@ void Reconstructor::reconstruct(Dataset& dataset) {
   if (!usePosteriorsForProfile) seedGenerator();
   const vguard<Vec>& rootProb = model.insProb;
   dataset.lpFinalFwd = dataset.lpFinalTrace = NEG_INF;
+  dataset.indelCounts = IndelCounts();
   const ForwardMatrix::ProfilingStrategy strategy = (ForwardMatrix::ProfilingStrategy)(
       ForwardMatrix::CollapseChains | (keepGapsOpen ? ForwardMatrix::KeepGapsOpen : ForwardMatrix::DontKeepGapsOpen) |
+      (accumulateIndelCounts ? ForwardMatrix::CountIndelEvents : ForwardMatrix::DontCountIndelEvents) |
       (includeBestTraceInProfile ? ForwardMatrix::IncludeBestTrace : ForwardMatrix::DontIncludeBestTrace));
   vguard<vguard<LogProb> > logRootProb;
   for (const auto& rv : rootProb) logRootProb.push_back(log_vector(rv));
@@ -221,6 +224,10 @@ void Reconstructor::reconstruct(Dataset& dataset) {
           path = forward->bestAlignPath();
           nodeProf = forward->bestProfile();
         }
+        if (accumulateIndelCounts) {         // src/recon.cpp:981-1013: Backward at the root, getCounts
+          BackwardMatrix backward(*forward);
+          dataset.indelCounts = backward.getCounts();
+        }
         dataset.lpFinalFwd = forward->lpEnd;
       } else if (usePosteriorsForProfile) {
         BackwardMatrix backward(*forward);
@@ -344,6 +351,37 @@ void Reconstructor::reconstructAll(vguard<Dataset*>& datasets) {
       detail::mergeTiming(fillTiming, mine);
     });
   for (std::thread& w : workers) w.join();
+}
+
+// reference src/recon.cpp:1373-1383 (every dataset is reconstructed here: counts on a given reconstruction are
+// historian_amd/counts.py's)
+void Reconstructor::countAll(vguard<Dataset*>& datasets) {
+  Require(!datasets.empty(), "Please supply some data");
+  reconstructAll(datasets);
+  dataCounts = IndelCounts();
+  for (const Dataset* d : datasets) dataCounts += d->indelCounts;
+  dataPlusPriorCounts = dataCounts + priorCounts;
+}
+
+// reference src/recon.cpp:1385-1410 with the substitution rates fixed: E-step = countAll under the current rates (every
+// ProbModel is rebuilt from `model` by reconstruct), M-step = IndelCounts::optimize of data + prior counts
+void Reconstructor::fit(vguard<Dataset*>& datasets) {
+  Require(accumulateIndelCounts, "With indel AND substitution rates fixed, model has no free parameters to fit.");
+  Require(!datasets.empty(), "Please supply some data");
+  const bool gotPrior = useLaplacePseudocounts;
+  priorCounts = gotPrior ? IndelCounts(1., 1.) : IndelCounts();
+  priorCounts.lp = 0;
+  emLogLikelihood.clear();
+  LogProb lpLast = NEG_INF;
+  for (size_t iter = 0; iter < maxEMIterations; ++iter) {
+    countAll(datasets);
+    const LogProb lpData = dataCounts.lp, lpPrior = gotPrior ? priorCounts.logPrior(model) : 0;
+    const LogProb lpWithPrior = lpData + lpPrior;
+    emLogLikelihood.push_back(lpWithPrior);
+    if (lpWithPrior <= lpLast + std::abs(lpLast) * minEMImprovement) break;
+    dataPlusPriorCounts.optimize(model);
+    lpLast = lpWithPrior;
+  }
 }
 
 // Alignment(ungapped, path).gapped(): leaves show residues, internal nodes the wildcard character

@@ -446,11 +446,59 @@ AlignPath ForwardMatrix::traceAlignPath(const Path& path) const {
 // ---------------------------------------------------------------------------------------------------------------------
 ForwardMatrix::EffectiveTransition::EffectiveTransition() : lpBestAlignPath(kNegInf), lpPath(kNegInf) {}
 
+// transitionEigenCounts, the indel part (reference src/forward.cpp:579-652): the counts the child transitions carry, then
+// the pair HMM's own events and waiting times
+IndelCounts ForwardMatrix::transitionIndelCounts(const CellCoords& src, const CellCoords& dest) const {
+  IndelCounts c;
+  if (src.xpos != dest.xpos) c += x.getTrans(src.xpos, dest.xpos)->counts;
+  if (src.ypos != dest.ypos) c += y.getTrans(src.ypos, dest.ypos)->counts;
+  const bool xNull = x.state[dest.xpos].isNull(), yNull = y.state[dest.ypos].isNull();
+  const int s = src.state, d = dest.state;
+  switch (d) {
+  case PairHMM::IMM:
+    if (!xNull && !yNull) {
+      if (s == PairHMM::IMM || s == PairHMM::IMD) { c.insTime += hmm.l.t; c.delTime += hmm.l.t; }
+      if (s == PairHMM::IMM || s == PairHMM::IDM) { c.insTime += hmm.r.t; c.delTime += hmm.r.t; }
+    }
+    break;
+  case PairHMM::IMD:
+    if (!xNull) {
+      if (s == PairHMM::IMM || s == PairHMM::IMD) { c.insTime += hmm.l.t; c.delTime += hmm.l.t; }
+      if (s == d) c.delExt += 1;
+      else { c.del += 1; c.delTime += hmm.r.delWait; }
+    }
+    break;
+  case PairHMM::IIW:
+    if (!xNull) {
+      if (s == d) c.insExt += 1;
+      else { c.ins += 1; c.insTime += hmm.l.insWait; }
+    }
+    break;
+  case PairHMM::IDM:
+    if (!yNull) {
+      if (s == PairHMM::IMM || s == PairHMM::IDM) { c.insTime += hmm.r.t; c.delTime += hmm.r.t; }
+      if (s == d) c.delExt += 1;
+      else { c.del += 1; c.delTime += hmm.l.delWait; }
+    }
+    break;
+  case PairHMM::IMI:
+    if (!yNull) {
+      if (s == d) c.insExt += 1;
+      else { c.ins += 1; c.insTime += hmm.r.insWait; }
+    }
+    break;
+  default:
+    break;
+  }
+  return c;
+}
+
 Profile ForwardMatrix::makeProfile(const set<CellCoords>& cells, ProfilingStrategy strategy) {
   Assert(cells.count(startCell), "Missing SSS");
   Assert(cells.count(endCell), "Missing EEE");
   const double tStart = wallSeconds();
   if (!haveHostCells && batch) prefetchCells(cells);   // the fwdLogProb annotations below read these cells
+  const bool counting = (strategy & CountIndelEvents) != 0;
 
   const vguard<Cell> chosen(cells.begin(), cells.end());            // cell order
   const size_t n = chosen.size();
@@ -531,6 +579,7 @@ Profile ForwardMatrix::makeProfile(const set<CellCoords>& cells, ProfilingStrate
         EffectiveTransition& e = slot(reach[fromIdx[k][q]], stateOf[k]);
         e.lpPath = e.lpBestAlignPath = into[k][q].second + inserted;
         e.bestAlignPath = transitionAlignPath(into[k][q].first, c);
+        if (counting) e.counts = transitionIndelCounts(into[k][q].first, c);
       }
       continue;
     }
@@ -541,10 +590,18 @@ Profile ForwardMatrix::makeProfile(const set<CellCoords>& cells, ProfilingStrate
     for (size_t q = 0; q < into[k].size(); ++q) {
       const LogProb through = into[k][q].second;
       const AlignPath step = transitionAlignPath(into[k][q].first, c);
+      const IndelCounts stepCounts = counting ? transitionIndelCounts(into[k][q].first, c) : IndelCounts();
       vguard<Reach>& ofSource = reach[fromIdx[k][q]];
       for (const Reach& r : onward) {
         EffectiveTransition& e = slot(ofSource, r.first);
-        log_accum_exp(e.lpPath, through + inserted + r.second.lpPath);
+        const LogProb lpPath = through + inserted + r.second.lpPath;
+        log_accum_exp(e.lpPath, lpPath);
+        if (counting) {
+          // the counts of the paths summed so far, mixed in proportion to their probabilities (src/forward.cpp:794-798)
+          const double ppPath = exp(lpPath - e.lpPath);
+          e.counts *= 1 - ppPath;
+          e.counts += (stepCounts + r.second.counts) * ppPath;
+        }
         const LogProb best = through + inserted + r.second.lpBestAlignPath;
         if (best > e.lpBestAlignPath) {
           e.lpBestAlignPath = best;
@@ -564,6 +621,7 @@ Profile ForwardMatrix::makeProfile(const set<CellCoords>& cells, ProfilingStrate
       t.dest = r.first;
       t.lpTrans = r.second.lpPath;
       t.alignPath = r.second.bestAlignPath;
+      t.counts = r.second.counts;
       prof.trans.push_back(t);
       ProfileState& from = prof.state[t.src];
       (prof.state[t.dest].isNull() ? from.nullOut : from.absorbOut).push_back(ti);
@@ -809,6 +867,27 @@ BackwardMatrix::BackwardMatrix(ForwardMatrix& fwd) : DPMatrix(fwd.x, fwd.y, fwd.
     sourceDestTransTest();
     Warn("Forward log-likelihood is %g, Backward log-likelihood is %g", fwd.lpEnd, lpStartDev);
   }
+}
+
+IndelCounts BackwardMatrix::getCounts() {
+  Assert(batch, "getCounts needs the device-resident matrices");
+  const auto table = [](const Profile& p) {
+    vguard<double> t(6 * p.trans.size());
+    for (size_t k = 0; k < p.trans.size(); ++k) {
+      const IndelCounts& c = p.trans[k].counts;
+      const double v[6] = {c.ins, c.del, c.insExt, c.delExt, c.insTime, c.delTime};
+      std::copy(v, v + 6, t.begin() + 6 * k);
+    }
+    return t;
+  };
+  const vguard<double> xc = table(x), yc = table(y);
+  const double times[6] = {hmm.l.t, hmm.r.t, hmm.l.insWait, hmm.l.delWait, hmm.r.insWait, hmm.r.delWait};
+  double out[6];
+  detail::check(hx_batch_event_counts(batch, jobIndex, xc.data(), yc.data(), times, out, NULL, NULL), "hx_batch_event_counts");
+  IndelCounts counts;
+  counts.ins = out[0]; counts.del = out[1]; counts.insExt = out[2]; counts.delExt = out[3]; counts.insTime = out[4]; counts.delTime = out[5];
+  counts.lp = fwd.lpEnd;
+  return counts;
 }
 
 double BackwardMatrix::cellPostProb(const CellCoords& c) const { return exp(fwd.cell(c) + cell(c) - fwd.lpEnd); }

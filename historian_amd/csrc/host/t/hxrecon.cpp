@@ -4,6 +4,11 @@
 //   seqs <fasta of ungapped leaf sequences>
 //   guide <fasta of the gapped guide alignment>      (optional)
 //   band <n> | samples <n> | maxstates <n> | seed <n> | posterior <minPostProb> | batch <0|1>   (optional)
+//   count indel                      (optional: `historian count` with fixed substitution rates - no root traceback; per
+//                                     family "indelCounts <key> <hex> <%.9g>" for ins del insExt delExt insTime delTime lp,
+//                                     then the same summed over families as "indelCountsTotal <key> ...")
+//   fit <maxIter> [<minImprovement>] (optional: `historian fit -fixsubrates`, EM over the indel rates with Laplace pseudocounts;
+//                                     prints "em <iteration> <hex> <%.9g>" per iteration, then insRate delRate insExtProb delExtProb)
 //   tree <N>   followed by N lines:  <parent index or -1> <branch length> <name>   (post-order, root last)
 // Output: final Forward / trace log-likelihoods as hex floats, the band used per node, and the
 // gapped reconstruction (one row per tree node on the root path).
@@ -17,6 +22,15 @@
 using namespace historian;
 
 // one job file -> the reconstruction parameters (the first file's stand for all) and one family
+static bool fitting = false;   // a `fit` key was read
+
+static void printCounts(const char* tag, const IndelCounts& c) {
+  const std::pair<const char*, double> v[7] = {{"ins", c.ins}, {"del", c.del}, {"insExt", c.insExt}, {"delExt", c.delExt},
+                                               {"insTime", c.insTime}, {"delTime", c.delTime}, {"lp", c.lp}};
+  for (const auto& kv : v) printf("%s %s %a %.9g\n", tag, kv.first, kv.second, kv.second);
+  fflush(stdout);
+}
+
 static void readJob(const char* file, Reconstructor& recon, bool setParams, Reconstructor::Dataset& ds) {
   std::ifstream in(file);
   Require(in.good(), "Couldn't open %s", file);
@@ -33,6 +47,18 @@ static void readJob(const char* file, Reconstructor& recon, bool setParams, Reco
     else if (key == "seed") in >> r.rndSeed;
     else if (key == "batch") { int b; in >> b; r.batchReadyNodes = b != 0; }
     else if (key == "posterior") { in >> r.minPostProb; r.usePosteriorsForProfile = true; }
+    else if (key == "count") {
+      string what; in >> what;
+      Require(what == "indel", "Only indel counts are supported (count %s in %s)", what.c_str(), file);
+      r.accumulateIndelCounts = true; r.reconstructRoot = false;
+    } else if (key == "fit") {
+      string rest; std::getline(in, rest);
+      std::istringstream args(rest);
+      Require((bool)(args >> r.maxEMIterations), "fit needs a maximum number of iterations in %s", file);
+      double minInc;
+      if (args >> minInc) r.minEMImprovement = minInc;
+      r.accumulateIndelCounts = true; r.reconstructRoot = false; fitting = true;
+    }
     else if (key == "tree") {
       int n; in >> n;
       for (int k = 0; k < n; ++k) {
@@ -108,7 +134,18 @@ int main(int argc, char** argv) {
     all.push_back(&families.back());
   }
   const double t0 = wallSeconds();
-  if (all.size() == 1) recon.reconstruct(*all[0]);
+  if (fitting) {
+    recon.fit(all);
+    for (size_t k = 0; k < recon.emLogLikelihood.size(); ++k)
+      printf("em %zu %a %.9g\n", k + 1, recon.emLogLikelihood[k], recon.emLogLikelihood[k]);
+    const std::pair<const char*, double> rates[4] = {{"insRate", recon.model.insRate}, {"delRate", recon.model.delRate},
+                                                     {"insExtProb", recon.model.insExtProb}, {"delExtProb", recon.model.delExtProb}};
+    for (const auto& kv : rates) printf("%s %a %.9g\n", kv.first, kv.second, kv.second);
+    fflush(stdout);
+    exit(EXIT_SUCCESS);
+  }
+  if (recon.accumulateIndelCounts) recon.countAll(all);
+  else if (all.size() == 1) recon.reconstruct(*all[0]);
   else recon.reconstructAll(all);
   if (getenv("HX_TIMING")) {
     const double total = wallSeconds() - t0;
@@ -124,6 +161,8 @@ int main(int argc, char** argv) {
   for (size_t k = 0; k < all.size(); ++k) {
     if (all.size() > 1) { printf("family %zu\n", k); fflush(stdout); }
     printFamily(*all[k]);
+    if (recon.accumulateIndelCounts) printCounts("indelCounts", all[k]->indelCounts);
   }
+  if (recon.accumulateIndelCounts) printCounts("indelCountsTotal", recon.dataCounts);
   exit(EXIT_SUCCESS);
 }

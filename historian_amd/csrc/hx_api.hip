@@ -133,10 +133,10 @@ struct Arena {
 
 // offsets into the arena for one profile
 struct ProfOff {
-  size_t flags, in_off, in_src, in_lp, ao_off, ao_dst, ao_lp, no_off, no_dst, no_lp;
+  size_t flags, in_off, in_src, in_lp, in_idx, ao_off, ao_dst, ao_lp, no_off, no_dst, no_lp;
   size_t lp_absorb, sub, ins, rootsub, env, cls, cls_rep, pack, ecls, subc, insc, rootsubc, fpack;
   bool has_env;
-  int n, empty, n_cls, chain, interior_emit, lp_zero;
+  int n, n_trans, empty, n_cls, chain, interior_emit, lp_zero;
 };
 
 int check_csr(const int32_t* off, const int32_t* idx, int N, int T, const char* what) {
@@ -243,6 +243,8 @@ int flatten_profile(const hx_profile* p, int CA, bool need_env, bool is_y, Arena
   o.in_off = ar.put(p->in_off, sizeof(int32_t) * (N + 1));
   o.in_src = ar.put(in_src.data(), sizeof(int32_t) * in_src.size());
   o.in_lp = ar.put(in_lp.data(), sizeof(double) * in_lp.size());
+  o.in_idx = ar.put(p->in_idx, sizeof(int32_t) * in_src.size());   // in-slot -> transition index (hx_batch_event_counts)
+  o.n_trans = T;
   o.ao_off = ar.put(p->aout_off, sizeof(int32_t) * (N + 1));
   o.ao_dst = ar.put(ao_dst.data(), sizeof(int32_t) * ao_dst.size());
   o.ao_lp = ar.put(ao_lp.data(), sizeof(double) * ao_lp.size());
@@ -596,6 +598,14 @@ struct hx_batch {
   void* h_trace = nullptr;
   int64_t trace_cap = 0;
   bool trace_ties_valid = false;     // the near-tie flags of the last hx_batch_best_trace are in d_trace_n's third block
+  struct TransIndex {                // per job: in-slot -> transition index of both profiles (hx_batch_event_counts)
+    const int32_t* x_in_idx;
+    const int32_t* y_in_idx;
+    int32_t x_trans, y_trans;
+  };
+  std::vector<TransIndex> trans_index;
+  double* d_events = nullptr;        // hx_batch_event_counts: scratch kept with the batch, grown on demand
+  size_t events_doubles = 0;
 };
 
 namespace {
@@ -1030,12 +1040,14 @@ int allocate_and_bind(hx_batch* b, const Arena& ar, const std::vector<JobOff>& o
   rot.bwd_band = rot.n > 0 && !getenv("HX_BAND_BWD_OLD");
   for (int p = rot.begin; p < rot.begin + rot.n; ++p)
     if (!offs[b->order[p]].band_rows_bwd) rot.bwd_band = false;
+  b->trans_index.resize((size_t)b->n_jobs);
   for (int k = 0; k < b->n_jobs; ++k) {
     DevJob& J = b->jobs[k];
     const JobOff& jo = offs[k];
     char* base = b->d_arena;
     bind_profile(J.x, jo.x, base);
     bind_profile(J.y, jo.y, base);
+    b->trans_index[k] = {reinterpret_cast<int32_t*>(base + jo.x.in_idx), reinterpret_cast<int32_t*>(base + jo.y.in_idx), jo.x.n_trans, jo.y.n_trans};
     J.log_root = reinterpret_cast<double*>(base + jo.log_root);
     J.log_sub_l = reinterpret_cast<double*>(base + jo.log_sub_l);
     J.log_sub_r = reinterpret_cast<double*>(base + jo.log_sub_r);
@@ -1189,6 +1201,7 @@ int hx_batch_destroy(hx_batch* b) {
   if (b->d_trace) (void)hipFree(b->d_trace);
   if (b->d_trace_n) (void)hipFree(b->d_trace_n);
   if (b->h_trace) (void)hipHostFree(b->h_trace);
+  if (b->d_events) (void)hipFree(b->d_events);
   delete b;
   return HX_OK;
 }
@@ -1964,6 +1977,45 @@ int hx_batch_indel_counts(hx_batch* b, int32_t job, const double* branch_times, 
   }
   (void)hipFree(d);
   return rc == HX_OK ? HX_OK : fail(rc, "indel-count kernel failed: %s", hipGetErrorString(hipGetLastError()));
+}
+
+int hx_batch_event_counts(hx_batch* b, int32_t job, const double* x_counts, const double* y_counts, const double* branch_times, double* out,
+                          double* x_post, double* y_post) {
+  if (const int rc = open_reader(b, branch_times && out, &job, NEED_FORWARD | NEED_BACKWARD,
+                                  "hx_batch_event_counts needs the Forward and the Backward fill"))
+    return rc;
+  const hx_batch::TransIndex& ti = b->trans_index[job];
+  const DevJob& J = b->jobs[job];
+  const int grid = event_counts_grid(J.n_rows, J.n_cols);
+  const int xT = ti.x_trans, yT = ti.y_trans;
+  // scratch layout: tm[6] | out[6] | x_post[xT] | y_post[yT] | x_counts[xT][6] | y_counts[yT][6] | partials[2][grid][6]
+  const size_t n_x = (size_t)xT, n_y = (size_t)yT;
+  const size_t o_xp = 12, o_yp = o_xp + n_x, o_xc = o_yp + n_y, o_yc = o_xc + 6 * n_x, o_part = o_yc + 6 * n_y;
+  const size_t total = o_part + 12 * (size_t)grid;
+  if (total > b->events_doubles) {                 // (a count / fit loop calls this per root and iteration: no per-call hipFree)
+    if (b->d_events) (void)hipFree(b->d_events);
+    b->d_events = nullptr;
+    b->events_doubles = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&b->d_events), sizeof(double) * total) != hipSuccess)
+      return fail(HX_ERR_OUT_OF_MEMORY, "device allocation of %zu event-count doubles failed", total);
+    b->events_doubles = total;
+  }
+  double* const d = b->d_events;
+  hipStream_t st = b->last_stream;
+  HIP_TRY(hipMemsetAsync(d, 0, sizeof(double) * o_xc, st));
+  HIP_TRY(hipMemcpyAsync(d, branch_times, 6 * sizeof(double), hipMemcpyHostToDevice, st));
+  if (x_counts && n_x) HIP_TRY(hipMemcpyAsync(d + o_xc, x_counts, 6 * n_x * sizeof(double), hipMemcpyHostToDevice, st));
+  if (y_counts && n_y) HIP_TRY(hipMemcpyAsync(d + o_yc, y_counts, 6 * n_y * sizeof(double), hipMemcpyHostToDevice, st));
+  ensure_state_records(b, st);
+  launch_event_counts(b->d_jobs, job, d, ti.x_in_idx, ti.y_in_idx, d + o_xp, d + o_yp, x_counts ? d + o_xc : nullptr, xT,
+                      y_counts ? d + o_yc : nullptr, yT, d + o_part, grid, d + 6, Tab8{g_dev[b->device].tab},
+                      !(b->flags & HX_FORCE_GENERIC), st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, d + 6, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (x_post && n_x) HIP_TRY(hipMemcpyAsync(x_post, d + o_xp, n_x * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (y_post && n_y) HIP_TRY(hipMemcpyAsync(y_post, d + o_yp, n_y * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return HX_OK;
 }
 
 int hx_batch_read_prepared(hx_batch* b, int32_t job, double* subx, double* suby, double* insx, double* rootsubx,

@@ -100,6 +100,11 @@ inline int multi_patience() {
 
 void launch_indel_counts(const DevJob* d_jobs, int job, const double* d_tm, double* d_out, int64_t cells, Tab8 tab, bool plane_valid,
                          hipStream_t st);
+// hx_events.hip: indel events with the carried counts of the profiles' transitions (hx_batch_event_counts)
+int event_counts_grid(int n_rows, int n_cols);
+void launch_event_counts(const DevJob* d_jobs, int job, const double* d_tm, const int32_t* x_in_idx, const int32_t* y_in_idx,
+                         double* d_x_post, double* d_y_post, const double* d_x_counts, int x_T, const double* d_y_counts, int y_T,
+                         double* d_part, int grid, double* d_out, Tab8 tab, bool plane_valid, hipStream_t st);
 void launch_best_trace(const DevJob* d_jobs, int n_jobs, int32_t* d_paths, int64_t cap, int32_t* d_n_cells, Tab8 tab,
                        bool plane_valid, int32_t* d_near_tie, hipStream_t st);
 

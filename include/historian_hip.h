@@ -305,6 +305,17 @@ int hx_batch_last_kernel_ms(hx_batch* b, int32_t which, float* ms);
  * src/model.cpp:374-391); out[6] = {ins, del, insExt, delExt, insTime, delTime}.  Needs both fills; synchronises. */
 int hx_batch_indel_counts(hx_batch* b, int32_t job, const double* branch_times, double* out);
 
+/* The same counts for profiles whose transitions carry expected events of their own (a profile built with
+ * CountIndelEvents stands for sub-alignments; each transition carries the events of the paths it sums, src/forward.cpp:764-830):
+ * BackwardMatrix::getCounts with the x.getTrans(..)->counts / y.getTrans(..)->counts terms of transitionEigenCounts
+ * (src/forward.cpp:579-584).  x_counts / y_counts: [n_trans][6] {ins, del, insExt, delExt, insTime, delTime} per transition,
+ * indexed by hx_profile transition index, or NULL (no carried counts: the result is hx_batch_indel_counts').  out[6] as above.
+ * x_post / y_post (may be NULL): [n_trans] the posterior probability that the pair's path moves along each transition of the
+ * profile; transitions into END read 0 (getCounts stops before the end cell).  Every sum runs in an order fixed by the pair's
+ * shape - no atomics - so two calls give the same bits.  Needs both fills; synchronises. */
+int hx_batch_event_counts(hx_batch* b, int32_t job, const double* x_counts, const double* y_counts, const double* branch_times,
+                          double* out, double* x_post, double* y_post);
+
 /* -- guide-alignment Viterbi (reference src/quickalign.cpp, src/diagenv.cpp) -------------------
  * The pairwise DP that builds the guide alignment the Forward fills are banded around: a batch of
  * independent QuickAlignMatrix fills.  Results are bit-identical to the reference (adds and maxima). */
