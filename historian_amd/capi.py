@@ -67,6 +67,13 @@ class HxBranchJob(C.Structure):
                 ("max_distance", C.c_int32)]
 
 
+class HxSiblingJob(C.Structure):
+    _fields_ = [("l_len", C.c_int32), ("r_len", C.c_int32), ("components", C.c_int32), ("alphabet", C.c_int32),
+                ("l_sub", C.POINTER(C.c_double)), ("r_sub", C.POINTER(C.c_double)), ("log_root", C.POINTER(C.c_double)),
+                ("l_emit", C.POINTER(C.c_double)), ("r_emit", C.POINTER(C.c_double)), ("trans", (C.c_double * 12) * 11),
+                ("l_env", C.POINTER(C.c_int32)), ("r_env", C.POINTER(C.c_int32)), ("max_distance", C.c_int32)]
+
+
 class HxSumprodModel(C.Structure):
     _fields_ = [("alph_size", C.c_int32), ("components", C.c_int32), ("n_nodes", C.c_int32), ("parent", _i32p),
                 ("ins_prob", _f64p), ("log_cpt_weight", _f64p), ("branch_sub", _f64p),
@@ -89,7 +96,9 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_quick_batch_total_cells", "hx_quick_batch_last_kernel_ms", "hx_sumprod_columns", "hx_sumprod_last_kernel_ms",
            "hx_batch_read_matrix_async", "hx_batch_wait_read", "hx_batch_indel_counts", "hx_batch_event_counts", "hx_batch_shared_wavefront_pairs", "hx_batch_relaunches",
            "hx_branch_batch_create", "hx_branch_batch_destroy", "hx_branch_batch_run", "hx_branch_batch_results",
-           "hx_branch_batch_read_matrix", "hx_branch_batch_total_cells", "hx_branch_batch_last_kernel_ms"]
+           "hx_branch_batch_read_matrix", "hx_branch_batch_total_cells", "hx_branch_batch_last_kernel_ms",
+           "hx_sibling_batch_create", "hx_sibling_batch_destroy", "hx_sibling_batch_run", "hx_sibling_batch_results",
+           "hx_sibling_batch_read_matrix", "hx_sibling_batch_total_cells", "hx_sibling_batch_last_kernel_ms"]
 
 
 class HxError(RuntimeError):
@@ -147,6 +156,14 @@ def load():
     lib.hx_branch_batch_total_cells.argtypes = [vp]
     lib.hx_branch_batch_total_cells.restype = C.c_int64
     lib.hx_branch_batch_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hx_sibling_batch_create.argtypes = [C.POINTER(HxSiblingJob), C.c_int32, C.POINTER(vp)]
+    lib.hx_sibling_batch_destroy.argtypes = [vp]
+    lib.hx_sibling_batch_run.argtypes = [vp, vp]
+    lib.hx_sibling_batch_results.argtypes = [vp, _f64p]
+    lib.hx_sibling_batch_read_matrix.argtypes = [vp, C.c_int32, _f64p]
+    lib.hx_sibling_batch_total_cells.argtypes = [vp]
+    lib.hx_sibling_batch_total_cells.restype = C.c_int64
+    lib.hx_sibling_batch_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.hx_quick_batch_destroy.argtypes = [vp]
     lib.hx_quick_batch_run.argtypes = [vp, vp]
     lib.hx_quick_batch_results.argtypes = [vp, _f64p, _i32p, _i32p]
@@ -550,6 +567,78 @@ class BranchBatch:
         ms = C.c_float()
         _check(load().hx_branch_batch_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+class SiblingBatch:
+    """n independent sibling-pair parent-proposal DPs (Sampler::SiblingMatrix, eleven states) resident on the device.
+    jobs: list of (l_sub [l_len][C][A], r_sub [r_len][C][A], log_root [C][A], l_emit [l_len], r_emit [r_len], trans [11][12],
+    l_env or None, r_env or None, max_distance)."""
+
+    STATES = ("IMM", "IMD", "IDM", "IDD", "WWW", "WWX", "WXW", "IMI", "IIW", "IDI", "IIX")
+
+    def __init__(self, jobs):
+        self.n = len(jobs)
+        self._keep = []
+        arr = (HxSiblingJob * max(self.n, 1))()
+        for k, (ls, rs, root, le, re_, trans, lenv, renv, md) in enumerate(jobs):
+            root = np.ascontiguousarray(root, dtype=np.float64)
+            ls = np.ascontiguousarray(ls, dtype=np.float64).reshape((-1,) + root.shape)
+            rs = np.ascontiguousarray(rs, dtype=np.float64).reshape((-1,) + root.shape)
+            le = np.ascontiguousarray(le, dtype=np.float64)
+            re_ = np.ascontiguousarray(re_, dtype=np.float64)
+            lv = None if lenv is None else np.ascontiguousarray(lenv, dtype=np.int32)
+            rv = None if renv is None else np.ascontiguousarray(renv, dtype=np.int32)
+            self._keep.append((ls, rs, root, le, re_, lv, rv))
+            j = arr[k]
+            j.l_len, j.r_len = ls.shape[0], rs.shape[0]
+            j.components, j.alphabet = root.shape
+            j.l_sub, j.r_sub, j.log_root, j.l_emit, j.r_emit = _p(ls, _f64p), _p(rs, _f64p), _p(root, _f64p), _p(le, _f64p), _p(re_, _f64p)
+            for s in range(11):
+                for d in range(12):
+                    j.trans[s][d] = trans[s][d]
+            j.l_env = C.cast(None, _i32p) if lv is None else lv.ctypes.data_as(_i32p)
+            j.r_env = C.cast(None, _i32p) if rv is None else rv.ctypes.data_as(_i32p)
+            j.max_distance = md
+        self._jobs = arr
+        self.shapes = [(arr[k].l_len + 1, arr[k].r_len + 1) for k in range(self.n)]
+        self._h = C.c_void_p()
+        _check(load().hx_sibling_batch_create(arr, self.n, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            load().hx_sibling_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, stream=None):
+        _check(load().hx_sibling_batch_run(self._h, C.c_void_p(stream or 0)))
+
+    def lp_end(self):
+        out = np.empty(self.n)
+        _check(load().hx_sibling_batch_results(self._h, _p(out, _f64p)))
+        return out
+
+    def read_matrix(self, job):
+        """dense [l_len + 1][r_len + 1][11]"""
+        if not 0 <= job < self.n:
+            _check(load().hx_sibling_batch_read_matrix(self._h, job, _p(np.empty(1), _f64p)))
+        out = np.empty(self.shapes[job] + (11,))
+        _check(load().hx_sibling_batch_read_matrix(self._h, job, _p(out, _f64p)))
+        return out
+
+    def total_cells(self):
+        return int(load().hx_sibling_batch_total_cells(self._h))
+
+    def kernel_ms(self):
+        """(fill kernel, whole step: clearing + emission pre-pass + fill) of the last run, HIP events"""
+        fill, step = C.c_float(), C.c_float()
+        _check(load().hx_sibling_batch_last_kernel_ms(self._h, C.byref(fill), C.byref(step)))
+        return fill.value, step.value
 
 
 class QuickBatch:

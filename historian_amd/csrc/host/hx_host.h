@@ -21,6 +21,9 @@
 // BackwardMatrix::getCounts returns the root's IndelCounts (device entry hx_batch_event_counts), and the Reconstructor
 // counts and fits indel rates (count / fit with fixed substitution rates).  The substitution half is not: the
 // CountSubstEvents bit is accepted and ignored, and SumProduct* must be NULL.
+// Sampler: BranchMatrix and the eleven-state SiblingMatrix (hx_host_sibling.cpp: fill on the device through
+// hx_sibling_batch_*, single or as fillBatch; sample / logPostProb / parentSeq over the copy read back) are mirrored here; the
+// sampler's moves (proposeMove, Move::accept, getConditionalPWMs) are not built.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -910,6 +913,73 @@ struct Sampler : TreeAlignFuncs {
                  const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos,
                  AlignRowIndex parentRow, AlignRowIndex childRow)
         : BranchMatrixBase(rates, parent, child, branchLength, envelope, xEnvelopePos, yEnvelopePos, parentRow, childRow, false) {}
+  };
+
+  // src/sampler.h:226-325, src/sampler.cpp:1185-1608: the parent-proposal DP of a sibling pair - left child profile against
+  // right child profile under their unobserved parent, eleven states per cell over SparseDPMatrix<11>.  The constructor
+  // prepares lSub, rSub, lEmit, rEmit, logRoot and the 35 transition scores in the reference's arithmetic, fills the lattice on
+  // the device (hx_sibling.hip through hx_sibling_batch_*) and reads it back dense; sample, logPostProb and parentSeq walk the
+  // copy.  fillBatch fills several matrices in one device batch (a move fills two, a sweep of moves many).  The sampler's
+  // moves (proposeMove, Move::accept, getConditionalPWMs) are not built.  Parity of this lattice is pinned by enumeration
+  // (tests/test_oracle_sibling.py), not by a reference fixture: none holds a sibling matrix.
+  class SiblingMatrix {
+  public:
+    enum State { SSS = 0, IMM = 0, IMD = 1, IDM = 2, IDD = 3, WWW = 4, WWX = 5, WXW = 6, IMI = 7, SSI = 7, IIW = 8, SIW = 8,
+                 IDI = 9, IIX = 10, EEE = 11 };
+    struct CellCoords { SeqIdx xpos, ypos; unsigned int state; };
+    typedef std::mt19937 random_engine;
+    const RateModel& model;
+    const ProbModel lProbModel, rProbModel;
+    const LogProbModel lLogProbModel, rLogProbModel;
+    vguard<vguard<LogProb>> logRoot;        // log(cptWeight) factored in
+    // the 35 transition scores (lpTransElimSelfLoopIDD)
+    LogProb imm_www, imm_imi, imm_iiw, imd_wwx, imd_iix, idm_wxw, idm_idi, idd_imm, idd_imd, idd_idm, idd_eee;
+    LogProb www_imm, www_imd, www_idm, www_idd, www_eee, wwx_imm, wwx_imd, wwx_idm, wwx_idd, wwx_eee;
+    LogProb wxw_imm, wxw_imd, wxw_idm, wxw_idd, wxw_eee, imi_www, imi_imi, imi_iiw, iiw_www, iiw_iiw, idi_wxw, idi_idi;
+    LogProb iix_wwx, iix_iix;
+    AlignRowIndex lRow, rRow, pRow;
+    const PosWeightMatrix lSub, rSub;
+    const vguard<LogProb> lEmit, rEmit;
+    const SeqIdx xSize, ySize;
+    LogProb lpEnd;
+
+    SiblingMatrix(const RateModel& model, const PosWeightMatrix& lSeq, const PosWeightMatrix& rSeq, double plDist, double prDist,
+                  const GuideAlignmentEnvelope& env, const vguard<SeqIdx>& lEnvPos, const vguard<SeqIdx>& rEnvPos,
+                  AlignRowIndex lRow, AlignRowIndex rRow, AlignRowIndex pRow);
+    // the constructor's arguments behind the model, for fillBatch (the objects pointed to outlive the matrices)
+    struct Args {
+      const PosWeightMatrix* lSeq; const PosWeightMatrix* rSeq;
+      double plDist, prDist;
+      const GuideAlignmentEnvelope* env; const vguard<SeqIdx>* lEnvPos; const vguard<SeqIdx>* rEnvPos;
+      AlignRowIndex lRow, rRow, pRow;
+    };
+    static vguard<std::unique_ptr<SiblingMatrix>> fillBatch(const RateModel& model, const vguard<Args>& args);   // one hx_sibling_batch
+
+    LogProb cell(SeqIdx xpos, SeqIdx ypos, unsigned int state) const;   // -inf outside the envelope; state EEE: lpEnd at the last cell
+    LogProb cell(const CellCoords& at) const { return cell(at.xpos, at.ypos, at.state); }
+    bool inEnvelope(SeqIdx xpos, SeqIdx ypos) const;
+    AlignPath sample(random_engine& generator) const;
+    LogProb logPostProb(const AlignPath& lrpPath) const;
+    PosWeightMatrix parentSeq(const AlignPath& lrpPath) const;
+    static State getState(State src, bool leftUngapped, bool rightUngapped, bool parentUngapped);
+    static void getColumn(const CellCoords& at, bool& leftUngapped, bool& rightUngapped, bool& parentUngapped);
+    LogProb lpTrans(State src, State dest) const;
+    LogProb lpTransElimSelfLoopIDD(State src, State dest) const;
+    LogProb lpTransElimWait(State src, State dest) const;
+    double iddSelfLoopProb() const { return model.insExtProb * lProbModel.delExt * rProbModel.delExt; }
+    LogProb iddStay() const { return log(iddSelfLoopProb()); }
+    LogProb iddExit() const { return log(1 / (1 - iddSelfLoopProb())); }
+    LogProb logMatch(SeqIdx xpos, SeqIdx ypos) const;
+    LogProb lpEmit(const CellCoords& at) const;
+    void transTable(double out[11][12]) const;      // lpTransElimSelfLoopIDD as the C ABI's source x destination table
+  private:
+    struct Deferred {};
+    SiblingMatrix(const RateModel& model, const Args& a, Deferred);       // everything but the fill
+    static void fillOnDevice(const vguard<SiblingMatrix*>& matrices);
+    const GuideAlignmentEnvelope& env;
+    const vguard<SeqIdx>& xEnvPos;
+    const vguard<SeqIdx>& yEnvPos;
+    vguard<double> cells;      // dense [xSize][ySize][11] copy of the device matrix
   };
 };
 

@@ -6,6 +6,11 @@
 //   hxtest expm <model.json> <t>                   exp(R t) of every mixture component as hex floats, row by row
 //   hxtest branch <pair.fa> <model.json> <t>       the two sequences as parent and child of one branch (next row N4): Viterbi
 //                                                  and Forward log-likelihoods as hex floats, then the best alignment
+//   hxtest sibling <pair.fa> <model.json> <tl> <tr> [band]   the two sequences as left and right child of an unobserved parent
+//                                                  (N4, Sampler::SiblingMatrix; band: envelope around the ungapped diagonal):
+//                                                  lpEnd as a hex float, a seeded sampled alignment, its logPostProb, the first
+//                                                  rows of the parent profile, and fillBatch of two envelopes against single fills
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -87,12 +92,68 @@ int branchPair(int, char** args) {
   return 0;
 }
 
+int siblingPair(int nArgs, char** args) {
+  const vguard<FastSeq> two = readFastSeqs(args[0]);
+  Require(two.size() == 2, "Sequence file must have exactly two sequences");
+  RateModel rates;
+  rates.readFile(args[1]);
+  const double tl = atof(args[2]), tr = atof(args[3]);
+  const int C = rates.components();
+  const auto left = TreeAlignFuncs::leafPWM(two[0], rates.alphabet, C), right = TreeAlignFuncs::leafPWM(two[1], rates.alphabet, C);
+  vguard<SeqIdx> xPos(left.size() + 1), yPos(right.size() + 1);
+  for (size_t k = 0; k < xPos.size(); ++k) xPos[k] = (SeqIdx)k;
+  for (size_t k = 0; k < yPos.size(); ++k) yPos[k] = (SeqIdx)k;
+  // the guide of a band: the two sequences side by side without gaps, the longer one's tail unmatched
+  AlignPath diagonal;
+  const size_t width = std::max(left.size(), right.size());
+  for (size_t col = 0; col < width; ++col) {
+    diagonal[0].push_back(col < left.size());
+    diagonal[1].push_back(col < right.size());
+  }
+  const GuideAlignmentEnvelope everywhere, banded(diagonal, 0, 1, nArgs > 4 ? atoi(args[4]) : 10);
+  const GuideAlignmentEnvelope& chosen = nArgs > 4 ? banded : everywhere;
+  const Sampler::SiblingMatrix matrix(rates, left, right, tl, tr, chosen, xPos, yPos, 0, 1, 2);
+  printf("lpEnd %a\n", matrix.lpEnd);
+  Sampler::SiblingMatrix::random_engine generator(20);
+  const AlignPath path = matrix.sample(generator);
+  for (AlignRowIndex row = 0; row < 3; ++row) {
+    size_t next = 0;
+    for (bool here : path.at(row)) putchar(!here ? '-' : (row < 2 ? two[row].seq[next++] : '*'));
+    putchar('\n');
+  }
+  printf("logPostProb %a\n", matrix.logPostProb(path));
+  const auto parent = matrix.parentSeq(path);
+  for (size_t pos = 0; pos < parent.size() && pos < 3; ++pos) {
+    printf("parent %zu", pos);
+    for (const auto& cpt : parent[pos])
+      for (double v : cpt) printf(" %a", v);
+    printf("\n");
+  }
+  // two envelopes in one device batch against two single fills
+  typedef Sampler::SiblingMatrix::Args Args;
+  const vguard<Args> both = {Args{&left, &right, tl, tr, &everywhere, &xPos, &yPos, 0, 1, 2}, Args{&left, &right, tl, tr, &banded, &xPos, &yPos, 0, 1, 2}};
+  const auto batch = Sampler::SiblingMatrix::fillBatch(rates, both);
+  const Sampler::SiblingMatrix single0(rates, left, right, tl, tr, everywhere, xPos, yPos, 0, 1, 2), single1(rates, left, right, tl, tr, banded, xPos, yPos, 0, 1, 2);
+  const Sampler::SiblingMatrix* singles[2] = {&single0, &single1};
+  size_t different = 0;
+  for (int k = 0; k < 2; ++k)
+    for (SeqIdx i = 0; i < singles[k]->xSize; ++i)
+      for (SeqIdx j = 0; j < singles[k]->ySize; ++j)
+        for (unsigned s = 0; s < 11; ++s) {
+          const double a = batch[k]->cell(i, j, s), b = singles[k]->cell(i, j, s);
+          if (memcmp(&a, &b, sizeof a) != 0) ++different;
+        }
+  printf("fillBatch lpEnd %a %a single %a %a cells that differ %zu\n", batch[0]->lpEnd, batch[1]->lpEnd, single0.lpEnd, single1.lpEnd, different);
+  return 0;
+}
+
 const Command commands[] = {
     {"logsumexp", 0, 1, "[-slow|-fast]", lseGrid},
     {"seqprofile", 2, 2, "<alphabet> <sequence>", leafProfileJson},
     {"quickalign", 3, 3, "<seqfile> <modelfile> <time>", guidePair},
     {"expm", 2, 2, "<modelfile> <time>", substitutionMatrix},
     {"branch", 3, 3, "<seqfile> <modelfile> <time>", branchPair},
+    {"sibling", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", siblingPair},
 };
 
 }  // namespace

@@ -6,7 +6,7 @@
 // MCMC sampler's branch move); cell storage and envelope of TreeAlignFuncs::SparseDPMatrix<3> (src/sampler.h:66-166), the
 // per-cell emission BranchMatrixBase::logMatch (src/sampler.h:207-209).
 //
-// Two kernels.  k_branch_emission evaluates logMatch(i, j) = logInnerProduct(xSeq[i-1], ySub[j-1]) for every in-envelope cell
+// Two kernels.  k_pair_emission (hx_pairdp.h) evaluates logMatch(i, j) = logInnerProduct(xSeq[i-1], ySub[j-1]) for every in-envelope cell
 // up front - it does not depend on DP values, is fully parallel, and uses the reference's table log_sum_exp bit for bit.
 // k_branch_fill sweeps a pair with ONE wavefront: 64-row strips one after the other, lane <-> row, step <-> anti-diagonal; a
 // cell's left source is the lane's own previous cell, up and diagonal are the previous lane's cells of one and two steps ago
@@ -19,8 +19,6 @@
 // Storage: three state planes per pair, strip-skewed like the Forward matrices (hx_device.h cell_slot), -inf outside the
 // envelope; hx_branch_batch_read_matrix returns the dense [x_len + 1][y_len + 1][3] array.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -30,6 +28,7 @@
 #include "hx_common.h"
 #include "hx_policy.h"
 #include "hx_kernels.h"
+#include "hx_pairdp.h"
 #include "../../include/historian_hip.h"
 
 namespace hx {
@@ -56,35 +55,6 @@ struct DevBranch {
   const int32_t* win;           // banded: [n_strips][3][2] step windows of the strips (half-open, merged, in order; empty ones last), or nullptr
 };
 
-__device__ __forceinline__ bool branch_in_env(const DevBranch& J, const int i, const int j) {
-  // TreeAlignFuncs::SparseDPMatrix::inEnvelope (src/sampler.h:146-149)
-  if (i == 0 || j == 0 || i == J.X - 1 || j == J.Y - 1 || J.max_dist < 0) return true;
-  int d = J.x_env[i] - J.y_env[j];
-  d = d < 0 ? -d : d;
-  return d <= J.max_dist;
-}
-
-// logMatch for every in-envelope cell with i, j >= 1: the nested logInnerProduct of src/logsumexp.h:132-151 - over the
-// components, of the sum over the residues - in the reference's table arithmetic.  grid (jobs, row slices)
-__global__ void k_branch_emission(const DevBranch* __restrict__ jobs, const double* __restrict__ tab) {
-  const DevBranch& J = jobs[blockIdx.x];
-  const int C = J.C, A = J.CA / C;
-  const int64_t n = (int64_t)J.X * J.Y;
-  for (int64_t c = (int64_t)blockIdx.y * blockDim.x + threadIdx.x; c < n; c += (int64_t)gridDim.y * blockDim.x) {
-    const int i = (int)(c / J.Y), j = (int)(c % J.Y);
-    if (i == 0 || j == 0 || !branch_in_env(J, i, j)) continue;
-    const double* xs = J.x_pwm + (size_t)(i - 1) * J.CA;
-    const double* ys = J.y_sub + (size_t)(j - 1) * J.CA;
-    double lip = HX_NEG_INF;
-    for (int cpt = 0; cpt < C; ++cpt) {
-      double inner = HX_NEG_INF;
-      for (int a = 0; a < A; ++a) inner = lse(inner, xs[cpt * A + a] + ys[cpt * A + a], tab);
-      lip = lse(lip, inner, tab);
-    }
-    J.emis[cell_slot(J.strip_stride, i, j)] = lip;
-  }
-}
-
 __global__ void k_branch_clear(const DevBranch* __restrict__ jobs) {
   const DevBranch& J = jobs[blockIdx.x];
   const int64_t n = 3 * J.plane;
@@ -93,11 +63,6 @@ __global__ void k_branch_clear(const DevBranch* __restrict__ jobs) {
 
 typedef double d2v __attribute__((ext_vector_type(2)));
 struct B3 { double m, i, d; };
-
-// value of lane `src` (wave-uniform)
-__device__ __forceinline__ double read_lane64(const double v, const int src) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
 
 template <bool VITERBI>
 __device__ __forceinline__ double combine(const double a, const double b, const double* __restrict__ tab) {
@@ -111,8 +76,6 @@ __device__ __forceinline__ double combine(const double a, const double b, const 
 // producer's stores (the consumer's loads are agent-scope: served by L2, where the stores are by then).  A strip therefore
 // starts ~HXBR_BLK + 64 steps behind the one above, and a branch of S strips takes columns + ~80 (S - 1) steps instead of the
 // S (columns + 63) of one wavefront per branch.  Waits cannot form a cycle: strip s waits for strip s - 1 only.
-#define HXBR_BLK 16
-#define HXBR_MAX_STRIPS 1024
 // YL: the child side of a step - insertion score and envelope coordinate of its column - out of LDS (staged once per
 // workgroup; the launcher checks that the longest child profile of the launch fits), not fetched from memory inside the step;
 // the step's emission term is fetched one step ahead either way.
@@ -167,11 +130,7 @@ __global__ void __launch_bounds__(1024) k_branch_fill(const DevBranch* __restric
     if (s > 0 && t0 >= 1 && t0 - 1 < Y) {
       // ... except lane 0's diagonal source of the window's first step: cell (row above, column t0 - 1) belongs to the strip
       // above, whose band may well hold it
-      while (seen < t0) {
-        seen = __builtin_amdgcn_readfirstlane(prog[s - 1]);
-        if (seen < t0) __builtin_amdgcn_s_sleep(2);
-      }
-      asm volatile("" ::: "memory");
+      strip_wait(prog, s - 1, seen, t0);
       if (lane == 0) {
         const int64_t sl = cell_slot(ss, (s << 6) - 1, t0 - 1);
         diag.m = __hip_atomic_load(M + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -187,11 +146,7 @@ __global__ void __launch_bounds__(1024) k_branch_fill(const DevBranch* __restric
         // the strip above's last row, HXBR_BLK columns at a time
         const int c0 = t & ~(HXBR_BLK - 1);
         const int need = c0 + HXBR_BLK < Y ? c0 + HXBR_BLK : Y;
-        while (seen < need) {
-          seen = __builtin_amdgcn_readfirstlane(prog[s - 1]);
-          if (seen < need) __builtin_amdgcn_s_sleep(2);
-        }
-        asm volatile("" ::: "memory");
+        strip_wait(prog, s - 1, seen, need);
         const int c = c0 + lane;
         bnd = none;
         if (lane < HXBR_BLK && c < Y) {
@@ -296,63 +251,6 @@ struct hx_branch_batch {
   hipStream_t last_stream = nullptr;
   bool done = false;
 };
-
-namespace {
-// Step windows of a banded branch's strips (steps t = column + row-in-strip): what is always inside the envelope - the first
-// and the last column (SparseDPMatrix::inEnvelope, src/sampler.h:146-149) - and the band, as up to three half-open ranges that
-// together hold every in-envelope cell of the strip's rows (supersets are harmless: a cell is tested again).  The strips of
-// the first and the last row sweep everything.  Any envelope coordinates (not only non-decreasing ones): the columns of a
-// coordinate value are bracketed once, a row takes the brackets of the values within max_distance of its own.
-std::vector<int32_t> branch_windows(const int32_t* xenv, const int32_t* yenv, int X, int Y, int band) {
-  const int n_strips = (X + HX_STRIP - 1) / HX_STRIP, nsteps = Y + HX_STRIP - 1;
-  std::vector<int32_t> w(6 * (size_t)n_strips, 0);
-  int V = 0;
-  for (int j = 0; j < Y; ++j) V = std::max(V, (int)yenv[j]);
-  std::vector<int> minj(V + 1, INT_MAX), maxj(V + 1, -1);
-  for (int j = 0; j < Y; ++j) {
-    const int v = yenv[j] < 0 ? 0 : yenv[j];
-    minj[v] = std::min(minj[v], j);
-    maxj[v] = std::max(maxj[v], j);
-  }
-  // (prefix brackets would make a row O(1); bands are tens of values wide)
-  for (int s = 0; s < n_strips; ++s) {
-    int32_t* o = &w[6 * (size_t)s];
-    const int rows = std::min(HX_STRIP, X - s * HX_STRIP);
-    if (s == 0 || s == n_strips - 1) { o[0] = 0; o[1] = (nsteps + 1) & ~1; continue; }
-    int lo = INT_MAX, hi = -1;
-    for (int l = 0; l < rows; ++l) {
-      const int xe = xenv[s * HX_STRIP + l] < 0 ? 0 : xenv[s * HX_STRIP + l];
-      int jmin = INT_MAX, jmax = -1;
-      for (int v = std::max(0, xe - band); v <= std::min(V, xe + band); ++v) {
-        jmin = std::min(jmin, minj[v]);
-        jmax = std::max(jmax, maxj[v]);
-      }
-      if (jmax < 0) continue;
-      lo = std::min(lo, jmin + l);
-      hi = std::max(hi, jmax + l);
-    }
-    std::pair<int, int> r[3] = {{0, rows}, {lo, hi + 1}, {Y - 1, Y - 1 + rows}};
-    if (hi < 0) r[1] = {INT_MAX, INT_MAX};         // (no band cell in the strip)
-    // in order, merged where they touch
-    std::sort(r, r + 3);
-    int n = 0;
-    for (int k = 0; k < 3; ++k) {
-      if (r[k].second <= r[k].first) continue;
-      if (n > 0 && r[k].first <= o[2 * (n - 1) + 1]) o[2 * (n - 1) + 1] = std::max(o[2 * (n - 1) + 1], r[k].second);
-      else { o[2 * n] = r[k].first; o[2 * n + 1] = r[k].second; ++n; }
-    }
-    // whole step pairs (the fill stores a row's cells of steps 2m, 2m + 1 together), merged again where they now touch
-    int m = 0;
-    for (int k = 0; k < n; ++k) {
-      const int a = o[2 * k] & ~1, b = std::min((o[2 * k + 1] + 1) & ~1, (nsteps + 1) & ~1);
-      if (m > 0 && a <= o[2 * (m - 1) + 1]) o[2 * (m - 1) + 1] = std::max(o[2 * (m - 1) + 1], b);
-      else { o[2 * m] = a; o[2 * m + 1] = b; ++m; }
-    }
-    for (int k = m; k < 3; ++k) o[2 * k] = o[2 * k + 1] = 0;
-  }
-  return w;
-}
-}  // namespace
 
 extern "C" {
 
@@ -473,7 +371,7 @@ int hx_branch_batch_run(hx_branch_batch* b, int32_t viterbi, void* stream) {
   for (int j0 = 0; j0 < b->n_jobs; j0 += 16384) {        // (grid.x of at most 16384 jobs per launch)
     const int n = b->n_jobs - j0 < 16384 ? b->n_jobs - j0 : 16384;
     hipLaunchKernelGGL(k_branch_clear, dim3(n, 16), dim3(256), 0, st, b->d_jobs + j0);
-    hipLaunchKernelGGL(k_branch_emission, dim3(n, 16), dim3(256), 0, st, b->d_jobs + j0, tab);
+    hipLaunchKernelGGL(k_pair_emission<DevBranch>, dim3(n, 16), dim3(256), 0, st, b->d_jobs + j0, tab);
   }
   if (hipEventRecord(b->ev[0], st) != hipSuccess) return api_fail(HX_ERR_HIP, "hipEventRecord failed");
   for (int j0 = 0; j0 < b->n_jobs; j0 += 65536) {

@@ -116,6 +116,34 @@ def pair_hmm_trans(l, r):
     return t
 
 
+def sibling_trans(l, r, root_ext):
+    """The 35 transition scores of Sampler::SiblingMatrix as the [11][12] source x destination table of hx_sibling_job, -inf
+    where absent: lpTransElimSelfLoopIDD (reference src/sampler.cpp:1451-1566) - sums of logs in the reference's order, the
+    IDD self-loop folded into IDD's exits.  l, r: branch_params of the two branches; root_ext: RateModel insExtProb."""
+    lg = lambda v: math.log(v) if v > 0 else NEG_INF
+    re_, rne = lg(root_ext), lg(1 - root_ext)
+    li, ld, lie, lde = lg(l["ins"]), lg(l["dele"]), lg(l["ins_ext"]), lg(l["del_ext"])
+    lni, lnd, lnie, lnde = lg(1 - l["ins"]), lg(1 - l["dele"]), lg(1 - l["ins_ext"]), lg(1 - l["del_ext"])
+    ri, rd, rie, rde = lg(r["ins"]), lg(r["dele"]), lg(r["ins_ext"]), lg(r["del_ext"])
+    rni, rnd, rnie, rnde = lg(1 - r["ins"]), lg(1 - r["dele"]), lg(1 - r["ins_ext"]), lg(1 - r["del_ext"])
+    IMM, IMD, IDM, IDD, WWW, WWX, WXW, IMI, IIW, IDI, IIX, EEE = range(12)
+    t = np.full((11, 12), NEG_INF)
+    t[IMM, WWW], t[IMM, IMI], t[IMM, IIW] = lni + rni, ri, li + rni
+    t[IMD, WWX], t[IMD, IIX] = lni, li
+    t[IDM, WXW], t[IDM, IDI] = rni, ri
+    idd_exit = math.log(1 / (1 - root_ext * l["del_ext"] * r["del_ext"]))
+    t[IDD, IMM], t[IDD, IMD], t[IDD, IDM] = re_ + lnde + rnde + idd_exit, re_ + lnde + rde + idd_exit, re_ + lde + rnde + idd_exit
+    t[IDD, EEE] = rne + lnde + rnde + idd_exit
+    t[WWW, IMM], t[WWW, IMD], t[WWW, IDM], t[WWW, IDD], t[WWW, EEE] = re_ + lnd + rnd, re_ + lnd + rd, re_ + ld + rnd, re_ + ld + rd, 0.
+    t[WWX, IMM], t[WWX, IMD], t[WWX, IDM], t[WWX, IDD], t[WWX, EEE] = re_ + lnd + rnde, re_ + lnd + rde, re_ + ld + rnde, re_ + ld + rde, rnde
+    t[WXW, IMM], t[WXW, IMD], t[WXW, IDM], t[WXW, IDD], t[WXW, EEE] = re_ + lnde + rnd, re_ + lnde + rd, re_ + lde + rnd, re_ + lde + rd, lnde
+    t[IMI, WWW], t[IMI, IMI], t[IMI, IIW] = lni + rnie, rie, li + rnie
+    t[IIW, WWW], t[IIW, IIW] = lnie, lie
+    t[IDI, WXW], t[IDI, IDI] = rnie, rie
+    t[IIX, WWX], t[IIX, IIX] = lnie, lie
+    return t
+
+
 def make_hmm(model, t_l, t_r, sub_l=None, sub_r=None):
     """PairHMM image for one internal node (reference src/recon.cpp:946-948)."""
     sub_l = model.sub_prob(t_l) if sub_l is None else sub_l

@@ -421,6 +421,42 @@ int hx_branch_batch_read_matrix(hx_branch_batch* b, int32_t job, double* out);
 int64_t hx_branch_batch_total_cells(const hx_branch_batch* b);
 int hx_branch_batch_last_kernel_ms(hx_branch_batch* b, float* ms);
 
+/* ---- row N4, second lattice: the sibling-pair parent-proposal DP ---------------------------------------------------------
+ * Sampler::SiblingMatrix (reference src/sampler.h:226-325, src/sampler.cpp:1185-1342): a left child profile and a right
+ * child profile under their unobserved parent, eleven states per cell over TreeAlignFuncs::SparseDPMatrix<11>, inside a
+ * GuideAlignmentEnvelope.  State indices: IMM (= SSS) 0, IMD 1, IDM 2, IDD 3, WWW 4, WWX 5, WXW 6, IMI (= SSI) 7,
+ * IIW (= SIW) 8, IDI 9, IIX 10; EEE 11 as a destination only.  The fill uses the reference's table log_sum_exp in the
+ * reference's order; cells and lpEnd are bit-identical to the restated recursion (tests/sibling_ref.py), which is pinned by
+ * enumeration - no reference fixture holds a sibling matrix. */
+typedef struct hx_sibling_job {
+  int32_t l_len, r_len;      /* positions of the left / right child profile; the matrix has (l_len + 1) x (r_len + 1) cells */
+  int32_t components;        /* mixture components C                                                                     */
+  int32_t alphabet;          /* A                                                                                        */
+  const double* l_sub;       /* [l_len][C][A] lSub = preMultiply(lSeq, lLogProbModel.logSubProb) (src/sampler.cpp:1196)  */
+  const double* r_sub;       /* [r_len][C][A] rSub                                                                       */
+  const double* log_root;    /* [C][A] log insProb with log cptWeight[c] added (src/sampler.cpp:1203-1205)               */
+  const double* l_emit;      /* [l_len] lEmit = calcInsProbs(lSeq, ...) (src/sampler.cpp:1198)                           */
+  const double* r_emit;      /* [r_len] rEmit                                                                            */
+  double trans[11][12];      /* [source][destination] lpTransElimSelfLoopIDD (src/sampler.cpp:1451-1457): the reference's
+                                35 members (the four *_eee in column 11), -inf everywhere else.  The caller computes them:
+                                they are logs of products of model parameters in the reference's order.                  */
+  const int32_t* l_env;      /* [l_len + 1] envelope coordinate of every position (see hx_branch_job); NULL with
+                                max_distance < 0                                                                         */
+  const int32_t* r_env;      /* [r_len + 1]                                                                              */
+  int32_t max_distance;      /* GuideAlignmentEnvelope::maxDistance; < 0: no band                                        */
+} hx_sibling_job;
+typedef struct hx_sibling_batch hx_sibling_batch;
+
+int hx_sibling_batch_create(const hx_sibling_job* jobs, int32_t n_jobs, hx_sibling_batch** out);   /* on the current device */
+int hx_sibling_batch_destroy(hx_sibling_batch* b);
+int hx_sibling_batch_run(hx_sibling_batch* b, void* stream);
+int hx_sibling_batch_results(hx_sibling_batch* b, double* lp_end /* [n_jobs] */);
+/* dense [l_len + 1][r_len + 1][11]; -inf outside the envelope, as SparseDPMatrix::cell() returns */
+int hx_sibling_batch_read_matrix(hx_sibling_batch* b, int32_t job, double* out);
+int64_t hx_sibling_batch_total_cells(const hx_sibling_batch* b);
+/* the fill kernel of the last run; step_ms (may be NULL): the whole step - clearing, emission pre-pass and fill */
+int hx_sibling_batch_last_kernel_ms(hx_sibling_batch* b, float* fill_ms, float* step_ms);
+
 #ifdef __cplusplus
 }
 #endif
