@@ -75,18 +75,26 @@ __device__ __forceinline__ L5 dpp_shr1_old(const L5& o, const L5& c) {
 // by the two low exponent bits and nine mantissa bits of the frexp mantissa, so that m == 0 (mantissa 0.0) lands on
 // entry 0 = {0, -inf} and comes out as -inf without a compare: real entries are 1024..1535.
 #define HXL_LOG_ENTRIES 1536
-__device__ __forceinline__ double log_scaled(double m, int e, const HX_LDS double* ltab) {
-  typedef double d2v __attribute__((ext_vector_type(2)));
+// In two halves, so that a caller can put other work between the table read and its use.  The read (the index is taken by an
+// opaque v_bfe_u32, so that index << 4 and the table's LDS base make one shift-and-add): ...
+typedef double log_entry __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ log_entry log_issue(double m, const HX_LDS double* ltab) {
   const double f = __builtin_amdgcn_frexp_mant(m);           // [0.5, 1), or 0
+  unsigned idx;                                              // bits 11..21 of the high word: == ((hi >> 7) & 0x7FF0) >> 4
+  asm("v_bfe_u32 %0, %1, 11, 11" : "=v"(idx) : "v"(__double2hiint(f)));
+  return *(const HX_LDS log_entry*)((const HX_LDS char*)ltab + (idx << 4));
+}
+// ... and the arithmetic
+__device__ __forceinline__ double log_finish(double m, int e, log_entry ce) {
+  const double f = __builtin_amdgcn_frexp_mant(m);
   const int k = __builtin_amdgcn_frexp_exp(m);
-  const unsigned byte_off = ((unsigned)__double2hiint(f) >> 7) & 0x7FF0u;
-  const d2v ce = *(const HX_LDS d2v*)((const HX_LDS char*)ltab + byte_off);
   const double r = __builtin_fma(f, ce.x, -1.0);
   double p = __builtin_fma(r, 1.0 / 3.0, -0.5);
   p = __builtin_fma(p, r, 1.0);
   const double lf = __builtin_fma(p, r, ce.y);
   return __builtin_fma((double)(e + k), 0.693147180559945309417, lf);
 }
+__device__ __forceinline__ double log_scaled(double m, int e, const HX_LDS double* ltab) { return log_finish(m, e, log_issue(m, ltab)); }
 
 // a stored log cell -> mantissas with a common exponent (only on the wrap-around link, see the kernel)
 __device__ __forceinline__ L5 from_logs(double a, double b, double c, double d, double g) {
@@ -137,6 +145,10 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
   static_assert(!BANDED || W == 1, "banded batches run one wavefront per pair");
   static_assert(PPW == 1 || BANDED, "several pairs per workgroup: banded batches only");
   constexpr int THREADS = W * PPW * 64, PT = W * 64;       // threads of the workgroup / of a pair
+  // The Forward fill's step pair is hand-scheduled (step_pair below) on a wave-uniform strip number.  The Backward fill keeps
+  // the compiler's schedule: it holds all 18 transition probabilities in scalar registers to the end of the step, and the
+  // uniform strip's further scalars would be spilled and reloaded inside the step loop (measured: 9.4 -> 9.7 ms on 256 pairs).
+  constexpr bool RESCHED = DIR == 0;
   constexpr int RING_ENTRIES = BANDED ? 0 : W * HXL_RING;  // (a banded pair is one wave: every strip boundary is the wrap-around link)
   typedef double d2v __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -195,7 +207,7 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
   __syncthreads();
   const int R = J.n_rows, Cc = J.n_cols;
   const int max_dist = J.max_dist;
-  const int lane = threadIdx.x & 63, wave = PPW == 1 ? (int)(threadIdx.x >> 6) : 0;   // wave within its pair
+  const int lane = threadIdx.x & 63, wave = PPW == 1 ? (RESCHED ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6)) : 0;   // wave within its pair
   const int64_t plane = J.plane, ss = J.strip_stride;
   const int blk = J.blk;                                     // doubles per step-pair block (hx_device.h cell_slot_blk)
   HX_GLOBAL double* __restrict__ M = as_global(DIR ? J.bwd : J.fwd);
@@ -289,7 +301,7 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     // column sequence numbers: column j of strip s is number (s / W) * Cc + j of its wave's ring
     const int above_base = ((s - 1) / WT) * Cc;
     const int my_base = (s / WT) * Cc;
-    int64_t store_base2 = (int64_t)s * ss + (lane << 1);
+    int64_t store_base = (int64_t)s * ss;          // (wave-uniform; the lane adds its 16 bytes)
     int store_t0 = 0;                              // (band-compressed storage: a window's cells are stored from its own offset)
     const int nsteps = (Cc + 64) & ~1;             // Cc + 63 anti-diagonals, rounded up to whole step pairs
 
@@ -399,28 +411,31 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
       int E;
       if (DIR == 0) {
       // the five sums of src/forward.cpp:103-115,139-150,171-180 on probabilities
+        // the diagonal cell's chain first: its registers are free after five products and take the ring entry
+        // (row0-1, t+1), lane 0's upper neighbour of the next step, which the other four chains then cover.
+        // Unconditional: past the last column it returns a stale entry, which only feeds cells outside the lattice.
+        double s_imm = u2.imm * P[0][0];
+        s_imm = lin_acc<TRUNC>(u2.imd, P[1][0], s_imm);
+        s_imm = lin_acc<TRUNC>(u2.idm, P[2][0], s_imm);
+        s_imm = lin_acc<TRUNC>(u2.imi, P[3][0], s_imm);
+        s_imm = lin_acc<TRUNC>(u2.iiw, P[4][0], s_imm);
+        const int e_diag = u2.e;
+        __builtin_amdgcn_sched_barrier(0);
+        u2 = ring_entry(t + 1);
+        __builtin_amdgcn_sched_barrier(0);
         double s_imd = u1.imm * P[0][1];
         double s_iiw = u1.imm * P[0][4];
         double s_idm = left.imm * P[0][2];
         double s_imi = left.imm * P[0][3];
-        double s_imm = u2.imm * P[0][0];
         s_imd = lin_acc<TRUNC>(u1.imd, P[1][1], s_imd);
         s_iiw = lin_acc<TRUNC>(u1.imi, P[3][4], s_iiw);
         s_idm = lin_acc<TRUNC>(left.imd, P[1][2], s_idm);
         s_imi = lin_acc<TRUNC>(left.imi, P[3][3], s_imi);
-        s_imm = lin_acc<TRUNC>(u2.imd, P[1][0], s_imm);
         s_imd = lin_acc<TRUNC>(u1.idm, P[2][1], s_imd);
         s_iiw = lin_acc<TRUNC>(u1.iiw, P[4][4], s_iiw);
         s_idm = lin_acc<TRUNC>(left.idm, P[2][2], s_idm);
-        s_imm = lin_acc<TRUNC>(u2.idm, P[2][0], s_imm);
         s_imd = lin_acc<TRUNC>(u1.imi, P[3][1], s_imd);
         s_idm = lin_acc<TRUNC>(left.iiw, P[4][2], s_idm);
-        s_imm = lin_acc<TRUNC>(u2.imi, P[3][0], s_imm);
-        s_imm = lin_acc<TRUNC>(u2.iiw, P[4][0], s_imm);
-        const int e_diag = u2.e;
-        // (row0-1, t+1), lane 0's upper neighbour of the next step, into the registers the diagonal cell has just
-        // vacated.  Unconditional: past the last column it returns a stale entry, which only feeds cells outside the lattice.
-        u2 = ring_entry(t + 1);
         // common exponent of the new cell, and the three groups brought to it; a state that may not be entered
         // (y or x state not ready: src/forward.cpp:97,133) is shifted out of the fp64 range, i.e. to zero
         E = left.e > u1.e ? left.e : u1.e;
@@ -531,29 +546,66 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     if (BANDED && whi[wi] <= wlo[wi]) continue;
     const int wstart = BANDED ? wlo[wi] : 0, wend = BANDED ? whi[wi] : nsteps;
     if (BANDED) { ca = l5_zero(); cb = l5_zero(); ua = l5_zero(); ub = l5_zero(); }
-    if (BANDED && DIR == 0 && J.strip_base) { store_base2 = J.strip_base[2 * s + wi] + (lane << 1); store_t0 = wstart; }
+    if (BANDED && DIR == 0 && J.strip_base) { store_base = J.strip_base[2 * s + wi]; store_t0 = wstart; }
     open_sweep(wstart);
     first_words(wstart);
     // a pair of steps: in the strip-skewed layout its two cells per row are adjacent, 16 bytes per lane and state plane
     auto step_pair = [&](const int t) {
-      step(t, cb, ca, ua, ub, next_word(t));
-      const double l0 = log_scaled(ca.imm, ca.e, lt), l1 = log_scaled(ca.imd, ca.e, lt),
-                   l2 = log_scaled(ca.idm, ca.e, lt), l3 = log_scaled(ca.imi, ca.e, lt),
-                   l4 = log_scaled(ca.iiw, ca.e, lt);
-      step(t + 1, ca, cb, ub, ua, next_word(t + 1));
-      const double h0 = log_scaled(cb.imm, cb.e, lt), h1 = log_scaled(cb.imd, cb.e, lt),
-                   h2 = log_scaled(cb.idm, cb.e, lt), h3 = log_scaled(cb.imi, cb.e, lt),
-                   h4 = log_scaled(cb.iiw, cb.e, lt);
-      {
-        // t64 = j + (i & 63) = t
-        const int64_t sl = store_base2 + (int64_t)((t - store_t0) >> 1) * blk;
-        HX_GLOBAL d2v* M2 = (HX_GLOBAL d2v*)(M + sl);
+      if (RESCHED) {
+        // The first cell's table reads are covered by step(t + 1); the second cell's go out two at a time under the arithmetic
+        // of the first cell's logarithms (the barriers keep the compiler from gathering them behind it).
+        step(t, cb, ca, ua, ub, next_word(t));
+        const log_entry ea0 = log_issue(ca.imm, lt), ea1 = log_issue(ca.imd, lt), ea2 = log_issue(ca.idm, lt),
+                        ea3 = log_issue(ca.imi, lt), ea4 = log_issue(ca.iiw, lt);
+        step(t + 1, ca, cb, ub, ua, next_word(t + 1));
+        const log_entry eb0 = log_issue(cb.imm, lt), eb1 = log_issue(cb.imd, lt);
+        __builtin_amdgcn_sched_barrier(0);
+        const double l0 = log_finish(ca.imm, ca.e, ea0), l1 = log_finish(ca.imd, ca.e, ea1);
+        const log_entry eb2 = log_issue(cb.idm, lt), eb3 = log_issue(cb.imi, lt);
+        __builtin_amdgcn_sched_barrier(0);
+        const double l2 = log_finish(ca.idm, ca.e, ea2), l3 = log_finish(ca.imi, ca.e, ea3);
+        const log_entry eb4 = log_issue(cb.iiw, lt);
+        __builtin_amdgcn_sched_barrier(0);
+        const double l4 = log_finish(ca.iiw, ca.e, ea4);
+        {
+          // Plane k leaves as soon as its pair {l_k, h_k} is complete (t64 = j + (i & 63) = t).  The address is a wave-uniform
+          // 64-bit base per plane in scalar registers plus the lane's 32-bit byte offset: no vector address arithmetic.
+          HX_GLOBAL char* Mu = (HX_GLOBAL char*)(M + (store_base + (int64_t)((t - store_t0) >> 1) * blk));
+          unsigned voff = (unsigned)lane << 4;
+          asm("" : "+v"(voff));                 // (defined in this block, or the 64-bit sum is hoisted and the stores take vector addresses)
+          const int64_t pb = plane * 8;
+          // write-once data that this kernel never reads again (the wrap-around link reads 1/64 of it, from L2 or
+          // memory): non-temporal stores - 17.4 -> 15.8 ms on the headline workload with separate state planes; with the
+          // interleaved layout (5 KiB contiguous per iteration) they measure the same as plain stores.
+          // MULTI: the strip below may run on another XCD: write-through stores (never `nt`, which stays in this XCD's L2)
+          const auto put = [&](const int k, const double l, const double h) {
+            const d2v v{l, h};
+            if (MULTI) asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(Mu + k * pb) : "memory");
+            else __builtin_nontemporal_store(v, (HX_GLOBAL d2v*)(Mu + k * pb + voff));
+          };
+          const double h0 = log_finish(cb.imm, cb.e, eb0);
+          put(0, l0, h0);
+          const double h1 = log_finish(cb.imd, cb.e, eb1);
+          put(1, l1, h1);
+          const double h2 = log_finish(cb.idm, cb.e, eb2);
+          put(2, l2, h2);
+          const double h3 = log_finish(cb.imi, cb.e, eb3);
+          put(3, l3, h3);
+          const double h4 = log_finish(cb.iiw, cb.e, eb4);
+          put(4, l4, h4);
+        }
+      } else {
+        step(t, cb, ca, ua, ub, next_word(t));
+        const double l0 = log_scaled(ca.imm, ca.e, lt), l1 = log_scaled(ca.imd, ca.e, lt),
+                     l2 = log_scaled(ca.idm, ca.e, lt), l3 = log_scaled(ca.imi, ca.e, lt),
+                     l4 = log_scaled(ca.iiw, ca.e, lt);
+        step(t + 1, ca, cb, ub, ua, next_word(t + 1));
+        const double h0 = log_scaled(cb.imm, cb.e, lt), h1 = log_scaled(cb.imd, cb.e, lt),
+                     h2 = log_scaled(cb.idm, cb.e, lt), h3 = log_scaled(cb.imi, cb.e, lt),
+                     h4 = log_scaled(cb.iiw, cb.e, lt);
+        HX_GLOBAL d2v* M2 = (HX_GLOBAL d2v*)(M + (store_base + (lane << 1) + (int64_t)((t - store_t0) >> 1) * blk));
         const int64_t plane2 = plane >> 1;
-        // write-once data that this kernel never reads again (the wrap-around link reads 1/64 of it, from L2 or
-        // memory): non-temporal stores - 17.4 -> 15.8 ms on the headline workload with separate state planes; with the
-        // interleaved layout (5 KiB contiguous per iteration) they measure the same as plain stores
         if (MULTI) {
-          // the strip below may run on another XCD: write-through stores (never `nt`, which stays in this XCD's L2)
           const d2v v0{l0, h0}, v1{l1, h1}, v2{l2, h2}, v3{l3, h3}, v4{l4, h4};
           asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[0]), "v"(v0) : "memory");
           asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[plane2]), "v"(v1) : "memory");
@@ -561,11 +613,11 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
           asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[3 * plane2]), "v"(v3) : "memory");
           asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[4 * plane2]), "v"(v4) : "memory");
         } else {
-        __builtin_nontemporal_store(d2v{l0, h0}, &M2[0]);
-        __builtin_nontemporal_store(d2v{l1, h1}, &M2[plane2]);
-        __builtin_nontemporal_store(d2v{l2, h2}, &M2[2 * plane2]);
-        __builtin_nontemporal_store(d2v{l3, h3}, &M2[3 * plane2]);
-        __builtin_nontemporal_store(d2v{l4, h4}, &M2[4 * plane2]);
+          __builtin_nontemporal_store(d2v{l0, h0}, &M2[0]);
+          __builtin_nontemporal_store(d2v{l1, h1}, &M2[plane2]);
+          __builtin_nontemporal_store(d2v{l2, h2}, &M2[2 * plane2]);
+          __builtin_nontemporal_store(d2v{l3, h3}, &M2[3 * plane2]);
+          __builtin_nontemporal_store(d2v{l4, h4}, &M2[4 * plane2]);
         }
       }
       if (wrap_out && !BANDED) {

@@ -1,7 +1,6 @@
 import sys, time, numpy as np
 import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench
-from historian_amd import capi, hostmodel
+from historian_amd import capi, hostmodel, workload
 import torch
 model = hostmodel.RateModel.load(os.path.dirname(os.path.dirname(os.path.abspath(__file__))) + '/tests/golden/models/wag.json')
 capi.init(0)
@@ -11,7 +10,7 @@ P = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 tr = []
 for k in range(P):
     rng = np.random.default_rng(1000 + k)
-    xs, ys = bench.synth_pair(rng, pi, 2000)
+    xs, ys = workload.synth_pair(rng, pi, 2000)
     tr.append((hostmodel.leaf_profile(xs, 20), hostmodel.leaf_profile(ys, 20), hmm, -1))
 for mode in ("linear", "fast", "exact"):
     b = capi.Batch(tr, {"linear": capi.HX_LSE_LINEAR, "fast": capi.HX_LSE_FAST, "exact": 0}[mode] | capi.HX_KEEP_BACKWARD)
