@@ -74,6 +74,10 @@ class HxSiblingJob(C.Structure):
                 ("l_env", C.POINTER(C.c_int32)), ("r_env", C.POINTER(C.c_int32)), ("max_distance", C.c_int32)]
 
 
+class HxPairCell(C.Structure):
+    _fields_ = [("xpos", C.c_int32), ("ypos", C.c_int32), ("state", C.c_int32)]
+
+
 class HxSumprodModel(C.Structure):
     _fields_ = [("alph_size", C.c_int32), ("components", C.c_int32), ("n_nodes", C.c_int32), ("parent", _i32p),
                 ("ins_prob", _f64p), ("log_cpt_weight", _f64p), ("branch_sub", _f64p),
@@ -98,7 +102,10 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_branch_batch_create", "hx_branch_batch_destroy", "hx_branch_batch_run", "hx_branch_batch_results",
            "hx_branch_batch_read_matrix", "hx_branch_batch_total_cells", "hx_branch_batch_last_kernel_ms",
            "hx_sibling_batch_create", "hx_sibling_batch_destroy", "hx_sibling_batch_run", "hx_sibling_batch_results",
-           "hx_sibling_batch_read_matrix", "hx_sibling_batch_total_cells", "hx_sibling_batch_last_kernel_ms"]
+           "hx_sibling_batch_read_matrix", "hx_sibling_batch_total_cells", "hx_sibling_batch_last_kernel_ms",
+           "hx_branch_batch_best_paths", "hx_branch_batch_sample_paths", "hx_branch_batch_max_steps", "hx_branch_batch_read_cells",
+           "hx_sibling_batch_sample_paths", "hx_sibling_batch_max_steps", "hx_sibling_batch_read_cells",
+           "hx_branch_batch_last_walk_ms", "hx_sibling_batch_last_walk_ms"]
 
 
 class HxError(RuntimeError):
@@ -164,6 +171,16 @@ def load():
     lib.hx_sibling_batch_total_cells.argtypes = [vp]
     lib.hx_sibling_batch_total_cells.restype = C.c_int64
     lib.hx_sibling_batch_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    _u32p, _i64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+    lib.hx_branch_batch_best_paths.argtypes = [vp, _u8p, C.c_int64, _i32p]
+    lib.hx_branch_batch_sample_paths.argtypes = [vp, _u32p, _i64p, _u8p, C.c_int64, _i32p, _i32p]
+    lib.hx_sibling_batch_sample_paths.argtypes = [vp, _u32p, _i64p, _u8p, C.c_int64, _i32p, _i32p]
+    for f in (lib.hx_branch_batch_max_steps, lib.hx_sibling_batch_max_steps):
+        f.argtypes, f.restype = [vp], C.c_int64
+    lib.hx_branch_batch_last_walk_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hx_sibling_batch_last_walk_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hx_branch_batch_read_cells.argtypes = [vp, C.c_int32, C.c_int64, vp, _f64p, _f64p]
+    lib.hx_sibling_batch_read_cells.argtypes = [vp, C.c_int32, C.c_int64, vp, _f64p, _f64p]
     lib.hx_quick_batch_destroy.argtypes = [vp]
     lib.hx_quick_batch_run.argtypes = [vp, vp]
     lib.hx_quick_batch_results.argtypes = [vp, _f64p, _i32p, _i32p]
@@ -504,10 +521,72 @@ class Batch:
         return out, [int(d) for d in draws]
 
 
-class BranchBatch:
+class _PairWalks:
+    """The walks through the device-resident matrices of a BranchBatch / SiblingBatch and the gather of cells along paths
+    (include/historian_hip.h: hx_*_batch_best_paths / sample_paths / read_cells)."""
+
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(load(), "hx_%s_batch_%s" % (self._prefix, name))
+
+    def max_steps(self):
+        return int(self._fn("max_steps")(self._h))
+
+    def walk_ms(self):
+        """the walk kernel of the last best_paths / sample_paths, HIP events"""
+        ms = C.c_float()
+        _check(self._fn("last_walk_ms")(self._h, C.byref(ms)))
+        return ms.value
+
+    def _paths(self, states, n_steps):
+        return [None if n < 0 else [int(v) for v in states[k, :n]] for k, n in enumerate(n_steps)]
+
+    def sample_paths(self, words, cap=None, raw=False):
+        """words: one sequence of 32-bit engine words per job.  -> (paths, n_steps, words_used): paths[k] = the states chosen
+        at every step of job k's walk, End side first, or None for a walk that failed (n_steps[k] < 0 says why)."""
+        if len(words) != self.n:
+            raise ValueError("one word stream per job")
+        streams = [np.ascontiguousarray(w, dtype=np.uint32).reshape(-1) for w in words]
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(w) for w in streams])
+        flat = np.concatenate(streams) if streams else np.zeros(0, dtype=np.uint32)
+        cap = self.max_steps() if cap is None else cap
+        states = np.zeros((self.n, max(cap, 0)), dtype=np.uint8)
+        n_steps = np.zeros(self.n, dtype=np.int32)
+        used = np.zeros(self.n, dtype=np.int32)
+        _check(self._fn("sample_paths")(self._h, _p(flat, C.POINTER(C.c_uint32)), _p(off, C.POINTER(C.c_int64)), _p(states, _u8p), cap,
+                                        _p(n_steps, _i32p), _p(used, _i32p)))
+        if raw:
+            return states, n_steps, used
+        return self._paths(states, n_steps), [int(v) for v in n_steps], [int(v) for v in used]
+
+    def read_cells(self, job, ijs):
+        """ijs: (xpos, ypos, state) triples.  -> (cells, log_match), one value each per triple"""
+        at = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+        cells, lm = np.empty(len(at)), np.empty(len(at))
+        _check(self._fn("read_cells")(self._h, job, len(at), at.ctypes.data_as(C.c_void_p) if len(at) else None, _p(cells, _f64p),
+                                      _p(lm, _f64p)))
+        return cells, lm
+
+
+class BranchBatch(_PairWalks):
     """n independent per-branch pair DPs (Refiner::BranchMatrix / Sampler::BranchMatrix) resident on the device.
     jobs: list of (x_pwm [x_len][C][A], y_sub [y_len][C][A], y_emit [y_len], trans [3][4], x_env or None, y_env or None,
     max_distance)."""
+
+    _prefix = "branch"
+
+    def best_paths(self, cap=None, raw=False):
+        """Refiner::BranchMatrix::best of every job (the batch must have run with viterbi=True).  -> (paths, n_steps) as
+        sample_paths gives them; raw=True: the arrays (states [n, cap], n_steps [n])"""
+        cap = self.max_steps() if cap is None else cap
+        states = np.zeros((self.n, max(cap, 0)), dtype=np.uint8)
+        n_steps = np.zeros(self.n, dtype=np.int32)
+        _check(load().hx_branch_batch_best_paths(self._h, _p(states, _u8p), cap, _p(n_steps, _i32p)))
+        if raw:
+            return states, n_steps
+        return self._paths(states, n_steps), [int(v) for v in n_steps]
 
     def __init__(self, jobs):
         self.n = len(jobs)
@@ -569,12 +648,13 @@ class BranchBatch:
         return ms.value
 
 
-class SiblingBatch:
+class SiblingBatch(_PairWalks):
     """n independent sibling-pair parent-proposal DPs (Sampler::SiblingMatrix, eleven states) resident on the device.
     jobs: list of (l_sub [l_len][C][A], r_sub [r_len][C][A], log_root [C][A], l_emit [l_len], r_emit [r_len], trans [11][12],
     l_env or None, r_env or None, max_distance)."""
 
     STATES = ("IMM", "IMD", "IDM", "IDD", "WWW", "WWX", "WXW", "IMI", "IIW", "IDI", "IIX")
+    _prefix = "sibling"
 
     def __init__(self, jobs):
         self.n = len(jobs)

@@ -41,6 +41,8 @@
 struct hx_batch;
 struct hx_quick_batch;
 struct hx_quick_job;
+struct hx_branch_batch;
+struct hx_sibling_batch;
 
 namespace historian {
 
@@ -687,6 +689,9 @@ double* pinnedTake(size_t doubles, size_t& capacity);
 void pinnedReserve(size_t doubles, int count);     // make sure `count` free page-locked buffers of that size exist (call while the device is busy)
 void pinnedGive(double* p, size_t capacity);
 void check(int rc, const char* what);
+bool hostWalks();                     // HX_HOST_WALKS=1: the pair matrices' walks run on the host, over the dense copy
+long denseMatrixReads();              // dense copies of branch / sibling matrices read back so far (a walk on the device reads none)
+void countDenseMatrixRead();
 }  // namespace detail
 
 // ---- src/fastseq.h (k-mers), src/diagenv.h, src/quickalign.h ---------------------------------
@@ -853,8 +858,9 @@ struct AlignGraph {
 // ---- src/sampler.h:19-215, src/refiner.h:8-18: the per-branch pair DPs ----------------
 // Parent profile x against child profile y across one branch: three states per cell (Match, Insert, Delete), the lattice of
 // TreeAlignFuncs::SparseDPMatrix<3> inside a GuideAlignmentEnvelope.  The fill runs on the device (hx_branch.hip through the
-// C ABI hx_branch_batch_*): Viterbi for Refiner::BranchMatrix, the reference's log_sum_exp for Sampler::BranchMatrix; the
-// matrix comes back dense and cell(), best() walk it on the host as the reference does.
+// C ABI hx_branch_batch_*): Viterbi for Refiner::BranchMatrix, the reference's log_sum_exp for Sampler::BranchMatrix.  The
+// matrix stays on the device: best(), sample() and logPathProb() walk it there (hx_branch_batch_best_paths / sample_paths /
+// read_cells); the dense copy is read on the first cell() call only.  HX_HOST_WALKS=1 keeps the host walks over the copy.
 struct TreeAlignFuncs {
   typedef vguard<vguard<vguard<LogProb>>> PosWeightMatrix;      // pwm[pos][cpt][tok]
   enum State { Start = 0, Match = 0, Insert = 1, Delete = 2, End = 3 };   // ProbModel::State (src/model.h:135-137)
@@ -882,16 +888,23 @@ struct TreeAlignFuncs {
                      const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos,
                      AlignRowIndex parentRow, AlignRowIndex childRow, bool viterbi);
     LogProb cell(SeqIdx xpos, SeqIdx ypos, unsigned int state) const;   // -inf outside the envelope; state End: lpEnd at the last cell
+    LogProb cell(const CellCoords& at) const { return cell(at.xpos, at.ypos, at.state); }
     bool inEnvelope(SeqIdx xpos, SeqIdx ypos) const;
     LogProb logMatch(SeqIdx xpos, SeqIdx ypos) const;
     LogProb lpTrans(State src, State dest) const;
     LogProb lpEmit(const CellCoords& at) const;
     static void getColumn(const CellCoords& at, bool& xUngapped, bool& yUngapped);
+    static State getState(bool xUngapped, bool yUngapped) { return xUngapped ? (yUngapped ? Match : Delete) : Insert; }   // ProbModel::getState
+    LogProb logPathProb(const AlignPath& path) const;                   // src/sampler.cpp:1122-1154
+  protected:
+    // the alignment a device walk's recorded states spell (End side first), as the reference's loops build it
+    AlignPath pathOfStates(const unsigned char* states, int nSteps) const;
+    std::shared_ptr<hx_branch_batch> batch;     // the device-resident matrix (job 0 of its own batch)
   private:
     const GuideAlignmentEnvelope& env;
     const vguard<SeqIdx>& xEnvPos;
     const vguard<SeqIdx>& yEnvPos;
-    vguard<double> cells;      // dense [xSize][ySize][3] copy of the device matrix
+    mutable vguard<double> cells;      // dense [xSize][ySize][3] copy of the device matrix, read on the first cell()
   };
 };
 
@@ -907,8 +920,11 @@ struct Refiner : TreeAlignFuncs {
 };
 
 struct Sampler : TreeAlignFuncs {
-  class BranchMatrix : public BranchMatrixBase {          // src/sampler.cpp:1034-1084 (the fill; the sampling moves are not built)
+  class BranchMatrix : public BranchMatrixBase {          // src/sampler.cpp:1034-1160 (the sampling moves are not built)
   public:
+    typedef std::mt19937 random_engine;
+    AlignPath sample(random_engine& generator) const;     // src/sampler.cpp:1088-1120
+    LogProb logPostProb(const AlignPath& path) const;      // src/sampler.cpp:1156-1160
     BranchMatrix(const RateModel& rates, const PosWeightMatrix& parent, const PosWeightMatrix& child, double branchLength,
                  const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos,
                  AlignRowIndex parentRow, AlignRowIndex childRow)
@@ -918,8 +934,10 @@ struct Sampler : TreeAlignFuncs {
   // src/sampler.h:226-325, src/sampler.cpp:1185-1608: the parent-proposal DP of a sibling pair - left child profile against
   // right child profile under their unobserved parent, eleven states per cell over SparseDPMatrix<11>.  The constructor
   // prepares lSub, rSub, lEmit, rEmit, logRoot and the 35 transition scores in the reference's arithmetic, fills the lattice on
-  // the device (hx_sibling.hip through hx_sibling_batch_*) and reads it back dense; sample, logPostProb and parentSeq walk the
-  // copy.  fillBatch fills several matrices in one device batch (a move fills two, a sweep of moves many).  The sampler's
+  // the device (hx_sibling.hip through hx_sibling_batch_*) and keeps it there: sample and logPostProb go through
+  // hx_sibling_batch_sample_paths / read_cells, the matrices of a fillBatch share their batch (sampleBatch walks them in one
+  // launch), and the dense copy is read on the first cell() call only.  HX_HOST_WALKS=1 keeps the host walks over the copy.
+  // fillBatch fills several matrices in one device batch (a move fills two, a sweep of moves many).  The sampler's
   // moves (proposeMove, Move::accept, getConditionalPWMs) are not built.  Parity of this lattice is pinned by enumeration
   // (tests/test_oracle_sibling.py), not by a reference fixture: none holds a sibling matrix.
   class SiblingMatrix {
@@ -959,6 +977,8 @@ struct Sampler : TreeAlignFuncs {
     LogProb cell(const CellCoords& at) const { return cell(at.xpos, at.ypos, at.state); }
     bool inEnvelope(SeqIdx xpos, SeqIdx ypos) const;
     AlignPath sample(random_engine& generator) const;
+    // sample() of several matrices, matrix k from generators[k]: one launch when they are the matrices of one fillBatch
+    static vguard<AlignPath> sampleBatch(const vguard<const SiblingMatrix*>& matrices, const vguard<random_engine*>& generators);
     LogProb logPostProb(const AlignPath& lrpPath) const;
     PosWeightMatrix parentSeq(const AlignPath& lrpPath) const;
     static State getState(State src, bool leftUngapped, bool rightUngapped, bool parentUngapped);
@@ -976,10 +996,15 @@ struct Sampler : TreeAlignFuncs {
     struct Deferred {};
     SiblingMatrix(const RateModel& model, const Args& a, Deferred);       // everything but the fill
     static void fillOnDevice(const vguard<SiblingMatrix*>& matrices);
+    AlignPath sampleOnHost(random_engine& generator) const;
+    // the walk's recorded states replayed against the real generator; false: a geometric draw took other than two words
+    bool replay(const unsigned char* states, int nSteps, random_engine& generator, AlignPath& path) const;
     const GuideAlignmentEnvelope& env;
     const vguard<SeqIdx>& xEnvPos;
     const vguard<SeqIdx>& yEnvPos;
-    vguard<double> cells;      // dense [xSize][ySize][11] copy of the device matrix
+    std::shared_ptr<hx_sibling_batch> batch;    // the device-resident matrices of the fill this one came from
+    int jobIndex = 0, batchJobs = 0;
+    mutable vguard<double> cells;      // dense [xSize][ySize][11] copy of the device matrix, read on the first cell()
   };
 };
 

@@ -2,8 +2,12 @@
 // and Sampler::BranchMatrix (src/sampler.cpp:1005-1084) over TreeAlignFuncs::SparseDPMatrix<3> (src/sampler.h:66-215).
 // Everything that is per position - the child profile through the branch's substitution matrix, its insertion scores, the
 // eleven transition scores - is prepared here in the reference's arithmetic; the lattice is filled on the device
-// (hx_branch.hip) and read back dense; the traceback walks the copy.
+// (hx_branch.hip) and stays there: the best path, the sampled path and the cells along a path come from the device
+// (hx_pairdp.h), the dense copy is read only when cell() is called (or with HX_HOST_WALKS=1, which keeps the host walks).
+#include <atomic>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <limits>
 #include "hx_host.h"
 #include "../../../include/historian_hip.h"
@@ -11,6 +15,16 @@
 namespace historian {
 
 static const double kNegInf = -std::numeric_limits<double>::infinity();
+
+namespace detail {
+static std::atomic<long> g_denseReads(0);
+bool hostWalks() {
+  const char* e = getenv("HX_HOST_WALKS");
+  return e && strcmp(e, "1") == 0;
+}
+long denseMatrixReads() { return g_denseReads.load(); }
+void countDenseMatrixRead() { ++g_denseReads; }
+}  // namespace detail
 
 double TreeAlignFuncs::transProb(const ProbModel& p, State src, State dest) {
   // rows: leaving Match, leaving Insert, leaving Delete; columns: into Match, Insert, Delete, End
@@ -103,15 +117,18 @@ TreeAlignFuncs::BranchMatrixBase::BranchMatrixBase(const RateModel& rates, const
   hx_branch_batch* b = nullptr;
   detail::check(hx_branch_batch_create(&job, 1, &b), "hx_branch_batch_create");
   detail::check(hx_branch_batch_run(b, viterbi ? 1 : 0, nullptr), "hx_branch_batch_run");
+  batch.reset(b, [](hx_branch_batch* p) { hx_branch_batch_destroy(p); });
   detail::check(hx_branch_batch_results(b, &lpEnd), "hx_branch_batch_results");
-  cells.resize((size_t)3 * xSize * ySize);
-  detail::check(hx_branch_batch_read_matrix(b, 0, cells.data()), "hx_branch_batch_read_matrix");
-  hx_branch_batch_destroy(b);
 }
 
 LogProb TreeAlignFuncs::BranchMatrixBase::cell(SeqIdx xpos, SeqIdx ypos, unsigned int state) const {
   if (state == End) return (xpos == xSize - 1 && ypos == ySize - 1) ? lpEnd : kNegInf;
   Assert(xpos < xSize && ypos < ySize && state < 3, "cell out of range");
+  if (cells.empty()) {
+    cells.resize((size_t)3 * xSize * ySize);
+    detail::check(hx_branch_batch_read_matrix(batch.get(), 0, cells.data()), "hx_branch_batch_read_matrix");
+    detail::countDenseMatrixRead();
+  }
   return cells[((size_t)xpos * ySize + ypos) * 3 + state];
 }
 
@@ -140,7 +157,37 @@ void TreeAlignFuncs::BranchMatrixBase::getColumn(const CellCoords& at, bool& xUn
 
 // The best alignment: from the End state back to the start, at every cell the source state whose score plus transition plus
 // this cell's emission is largest (the first such state in the order Match, Insert, Delete), src/refiner.cpp:62-104.
+AlignPath TreeAlignFuncs::BranchMatrixBase::pathOfStates(const unsigned char* states, int nSteps) const {
+  CellCoords at{(SeqIdx)(xSize - 1), (SeqIdx)(ySize - 1), End};
+  vguard<bool> xBack, yBack;
+  for (int k = 0; k < nSteps; ++k) {
+    bool xHere, yHere;
+    getColumn(at, xHere, yHere);
+    if (xHere || yHere) { xBack.push_back(xHere); yBack.push_back(yHere); }
+    at = CellCoords{(SeqIdx)(at.xpos - (xHere ? 1 : 0)), (SeqIdx)(at.ypos - (yHere ? 1 : 0)), states[k]};
+  }
+  Assert(at.xpos == 0 && at.ypos == 0, "A device walk stopped at cell (%u,%u)", at.xpos, at.ypos);
+  AlignPath path;
+  path[xRow] = AlignRowPath(xBack.rbegin(), xBack.rend());
+  path[yRow] = AlignRowPath(yBack.rbegin(), yBack.rend());
+  return path;
+}
+
+static void walkFailed(int code, const char* what) {
+  Assert(code != -2, "%s: traceback state has zero probability", what);
+  Assert(code != -1, "%s: the matrix's end score is -inf", what);
+  Assert(code >= 0, "%s: the device walk failed (code %d)", what, code);
+}
+
 AlignPath Refiner::BranchMatrix::best() const {
+  if (!detail::hostWalks()) {
+    const int64_t cap = std::max<int64_t>(1, hx_branch_batch_max_steps(batch.get()));
+    vguard<unsigned char> states((size_t)cap);
+    int32_t nSteps = 0;
+    detail::check(hx_branch_batch_best_paths(batch.get(), states.data(), cap, &nSteps), "hx_branch_batch_best_paths");
+    walkFailed(nSteps, "Refiner::BranchMatrix::best");
+    return pathOfStates(states.data(), nSteps);
+  }
   CellCoords at{(SeqIdx)(xSize - 1), (SeqIdx)(ySize - 1), End};
   vguard<bool> xBack, yBack;
   while (at.xpos > 0 || at.ypos > 0) {
@@ -162,6 +209,93 @@ AlignPath Refiner::BranchMatrix::best() const {
   path[xRow] = AlignRowPath(xBack.rbegin(), xBack.rend());
   path[yRow] = AlignRowPath(yBack.rbegin(), yBack.rend());
   return path;
+}
+
+// Sampler::BranchMatrix::sample (src/sampler.cpp:1088-1120): from End back to the start, at every step one of the three source
+// states drawn by its share (random_key_log, src/util.h:220-236: one 32-bit draw).  On the device the walk takes its words
+// from a copy of the generator; the real generator is then advanced by what the walk used.
+AlignPath Sampler::BranchMatrix::sample(random_engine& generator) const {
+  if (!detail::hostWalks()) {
+    const int64_t cap = std::max<int64_t>(1, hx_branch_batch_max_steps(batch.get()));
+    random_engine ahead = generator;
+    vguard<uint32_t> words((size_t)cap);
+    for (uint32_t& w : words) w = (uint32_t)ahead();
+    const int64_t off[2] = {0, cap};
+    vguard<unsigned char> states((size_t)cap);
+    int32_t nSteps = 0, used = 0;
+    detail::check(hx_branch_batch_sample_paths(batch.get(), words.data(), off, states.data(), cap, &nSteps, &used), "hx_branch_batch_sample_paths");
+    walkFailed(nSteps, "Sampler::BranchMatrix::sample");
+    generator.discard((unsigned long long)used);
+    return pathOfStates(states.data(), nSteps);
+  }
+  CellCoords at{(SeqIdx)(xSize - 1), (SeqIdx)(ySize - 1), End};
+  vguard<bool> xBack, yBack;
+  while (at.xpos > 0 || at.ypos > 0) {
+    bool xHere, yHere;
+    getColumn(at, xHere, yHere);
+    if (xHere || yHere) { xBack.push_back(xHere); yBack.push_back(yHere); }
+    const SeqIdx px = at.xpos - (xHere ? 1 : 0), py = at.ypos - (yHere ? 1 : 0);
+    const LogProb emit = lpEmit(at);
+    double via[3], top = kNegInf;
+    for (int s = 0; s < 3; ++s) {
+      via[s] = cell(px, py, s) + lpTrans((State)s, (State)at.state) + emit;
+      top = std::max(top, via[s]);
+    }
+    Assert(top > kNegInf, "Traceback state has zero probability at cell (%u,%u,%u)", at.xpos, at.ypos, at.state);
+    double total = 0;
+    for (int s = 0; s < 3; ++s) total += exp(via[s] - top);
+    double left = generator() / (((double)random_engine::max()) + 1) * total;
+    int from = -1;
+    for (int s = 0; s < 3 && from < 0; ++s)
+      if ((left -= exp(via[s] - top)) <= 0) from = s;
+    Assert(from >= 0, "random_key_log failed");
+    at = CellCoords{px, py, (unsigned)from};
+  }
+  AlignPath path;
+  path[xRow] = AlignRowPath(xBack.rbegin(), xBack.rend());
+  path[yRow] = AlignRowPath(yBack.rbegin(), yBack.rend());
+  return path;
+}
+
+// The score of one alignment through the matrix (src/sampler.cpp:1122-1154), summed here in the reference's order; the cells
+// along the path and their logMatch come from the device in one gather (or, with HX_HOST_WALKS=1, from the dense copy).
+LogProb TreeAlignFuncs::BranchMatrixBase::logPathProb(const AlignPath& path) const {
+  const AlignRowPath &xPath = path.at(xRow), &yPath = path.at(yRow);
+  const AlignColIndex cols = alignPathColumns(path);
+  vguard<hx_pair_cell> at;
+  CellCoords c{0, 0, Start};
+  bool left = false;
+  for (AlignColIndex col = 0; col < cols && !left; ++col) {
+    if (xPath[col]) ++c.xpos;
+    if (yPath[col]) ++c.ypos;
+    c.state = getState(xPath[col], yPath[col]);
+    if (c.xpos >= xSize || c.ypos >= ySize || !inEnvelope(c.xpos, c.ypos)) left = true;
+    else at.push_back(hx_pair_cell{(int32_t)c.xpos, (int32_t)c.ypos, (int32_t)c.state});
+  }
+  if (left) return kNegInf;
+  vguard<double> value(at.size()), match(at.size());
+  if (detail::hostWalks())
+    for (size_t q = 0; q < at.size(); ++q) {
+      value[q] = cell(at[q].xpos, at[q].ypos, at[q].state);
+      match[q] = at[q].state == Match ? logMatch(at[q].xpos, at[q].ypos) : 0;
+    }
+  else
+    detail::check(hx_branch_batch_read_cells(batch.get(), 0, (int64_t)at.size(), at.data(), value.data(), match.data()), "hx_branch_batch_read_cells");
+  LogProb lp = 0;
+  unsigned int state = Start;
+  for (size_t q = 0; q < at.size(); ++q) {
+    const unsigned int before = state;
+    state = at[q].state;
+    const LogProb lpe = state == Match ? match[q] : (state == Insert ? yEmit[at[q].ypos - 1] : 0);
+    lp += lpTrans((State)before, (State)state) + lpe;
+    lp = std::min(lp, value[q]);      // "mitigate precision errors"
+  }
+  return lp + lpTrans((State)state, End);
+}
+
+LogProb Sampler::BranchMatrix::logPostProb(const AlignPath& path) const {
+  const LogProb lp = logPathProb(path);
+  return std::min(lp, lpEnd) - lpEnd;
 }
 
 }  // namespace historian

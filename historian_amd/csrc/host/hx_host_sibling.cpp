@@ -2,7 +2,9 @@
 // src/sampler.h:226-325, src/sampler.cpp:1185-1608) over TreeAlignFuncs::SparseDPMatrix<11>.  What is per position - the two
 // child profiles through their branches' substitution matrices, their insertion scores, the root distribution - and the 35
 // transition scores are prepared here in the reference's arithmetic; the lattice is filled on the device (hx_sibling.hip), one
-// matrix or several in one batch, and read back dense; sample, logPostProb and parentSeq walk the copy.
+// matrix or several in one batch, and stays there, the matrices of a fill sharing their batch: sample and logPostProb go
+// through the device's walks and gather (hx_pairdp.h), the dense copy is read only when cell() is called (or with
+// HX_HOST_WALKS=1, which keeps the host walks over it).
 #include <cmath>
 #include <limits>
 #include <random>
@@ -113,18 +115,24 @@ void SM::fillOnDevice(const vguard<SiblingMatrix*>& matrices) {
   detail::check(hx_sibling_batch_run(b, nullptr), "hx_sibling_batch_run");
   vguard<double> lp(jobs.size());
   detail::check(hx_sibling_batch_results(b, lp.data()), "hx_sibling_batch_results");
+  const std::shared_ptr<hx_sibling_batch> shared(b, [](hx_sibling_batch* p) { hx_sibling_batch_destroy(p); });
   for (size_t k = 0; k < matrices.size(); ++k) {
     SiblingMatrix& m = *matrices[k];
     m.lpEnd = lp[k];
-    m.cells.resize((size_t)11 * m.xSize * m.ySize);
-    detail::check(hx_sibling_batch_read_matrix(b, (int32_t)k, m.cells.data()), "hx_sibling_batch_read_matrix");
+    m.batch = shared;
+    m.jobIndex = (int)k;
+    m.batchJobs = (int)matrices.size();
   }
-  hx_sibling_batch_destroy(b);
 }
 
 LogProb SM::cell(SeqIdx xpos, SeqIdx ypos, unsigned int state) const {
   if (state == EEE) return (xpos == xSize - 1 && ypos == ySize - 1) ? lpEnd : kNegInf;
   Assert(xpos < xSize && ypos < ySize && state < 11, "cell out of range");
+  if (cells.empty()) {
+    cells.resize((size_t)11 * xSize * ySize);
+    detail::check(hx_sibling_batch_read_matrix(batch.get(), jobIndex, cells.data()), "hx_sibling_batch_read_matrix");
+    detail::countDenseMatrixRead();
+  }
   return cells[((size_t)xpos * ySize + ypos) * 11 + state];
 }
 
@@ -261,6 +269,90 @@ LogProb SM::lpTransElimWait(State src, State dest) const {
 // the source cell, drawn by its share of the cell's sum (random_key_log, src/util.h:220-236: one 32-bit draw); an IDD column
 // is repeated a geometric number of times, the self-loop the fill eliminated.
 AlignPath SM::sample(random_engine& generator) const {
+  if (detail::hostWalks()) return sampleOnHost(generator);
+  return sampleBatch(vguard<const SiblingMatrix*>(1, this), vguard<random_engine*>(1, &generator))[0];
+}
+
+// The device's walk of every matrix given (hx_sibling_batch_sample_paths: one wavefront per job), matrices of one fill in one
+// launch.  A walk takes its words from a copy of the matrix's generator, drawn ahead: one per step, two more at every visit
+// of IDD - at most 3 (l + r) + 3 steps of which at most l + r + 1 stand in IDD.  The recorded states are then replayed
+// against the real generator, which draws the IDD self-loop counts with the real distribution and ends where the host walk
+// would leave it.
+vguard<AlignPath> SM::sampleBatch(const vguard<const SiblingMatrix*>& matrices, const vguard<random_engine*>& generators) {
+  Assert(matrices.size() == generators.size(), "sampleBatch: one generator per matrix");
+  vguard<AlignPath> paths(matrices.size());
+  vguard<bool> done(matrices.size(), false);
+  for (size_t first = 0; first < matrices.size(); ++first) {
+    if (done[first]) continue;
+    if (detail::hostWalks()) {
+      paths[first] = matrices[first]->sampleOnHost(*generators[first]);
+      done[first] = true;
+      continue;
+    }
+    // every matrix given that lives in this one's batch
+    hx_sibling_batch* b = matrices[first]->batch.get();
+    const int nJobs = matrices[first]->batchJobs;
+    vguard<int> which(nJobs, -1);
+    for (size_t k = first; k < matrices.size(); ++k)
+      if (!done[k] && matrices[k]->batch.get() == b && which[matrices[k]->jobIndex] < 0) which[matrices[k]->jobIndex] = (int)k;
+    const int64_t cap = std::max<int64_t>(1, hx_sibling_batch_max_steps(b));
+    vguard<int64_t> off(nJobs + 1, 0);
+    vguard<uint32_t> words;
+    for (int j = 0; j < nJobs; ++j) {
+      if (which[j] >= 0) {       // (a job nobody asked for gets no words: its walk ends at once)
+        const SiblingMatrix& m = *matrices[which[j]];
+        const size_t need = 5 * ((size_t)m.xSize + m.ySize) + 8;
+        random_engine ahead = *generators[which[j]];
+        for (size_t w = 0; w < need; ++w) words.push_back((uint32_t)ahead());
+      }
+      off[j + 1] = (int64_t)words.size();
+    }
+    vguard<unsigned char> states((size_t)nJobs * cap);
+    vguard<int32_t> nSteps(nJobs), used(nJobs);
+    detail::check(hx_sibling_batch_sample_paths(b, words.data(), off.data(), states.data(), cap, nSteps.data(), used.data()),
+                  "hx_sibling_batch_sample_paths");
+    for (int j = 0; j < nJobs; ++j) {
+      if (which[j] < 0) continue;
+      const size_t k = which[j];
+      Assert(nSteps[j] != -2, "Traceback state has zero probability (sibling matrix %zu)", k);
+      Assert(nSteps[j] >= 0, "The device walk of sibling matrix %zu failed (code %d)", k, nSteps[j]);
+      const random_engine before = *generators[k];
+      if (!matrices[k]->replay(&states[(size_t)j * cap], nSteps[j], *generators[k], paths[k])) {
+        *generators[k] = before;
+        paths[k] = matrices[k]->sampleOnHost(*generators[k]);
+      }
+      done[k] = true;
+    }
+  }
+  return paths;
+}
+
+bool SM::replay(const unsigned char* states, int nSteps, random_engine& generator, AlignPath& path) const {
+  CellCoords at{(SeqIdx)(xSize - 1), (SeqIdx)(ySize - 1), EEE};
+  vguard<bool> lBack, rBack, pBack;
+  for (int k = 0; k < nSteps; ++k) {
+    bool l, r, p;
+    getColumn(at, l, r, p);
+    if (l || r || p) { lBack.push_back(l); rBack.push_back(r); pBack.push_back(p); }
+    if ((State)at.state == IDD) {
+      // the device walk skipped two words here: what libstdc++'s geometric_distribution takes unless its rejection loop runs
+      random_engine expected = generator;
+      expected.discard(2);
+      std::geometric_distribution<int> loops(iddSelfLoopProb());
+      for (int n = loops(generator); n > 0; --n) { lBack.push_back(l); rBack.push_back(r); pBack.push_back(p); }
+      if (!(expected == generator)) return false;
+    }
+    generator();      // the step's draw
+    at = CellCoords{(SeqIdx)(at.xpos - (l ? 1 : 0)), (SeqIdx)(at.ypos - (r ? 1 : 0)), states[k]};
+  }
+  Assert(at.xpos == 0 && at.ypos == 0, "A device walk stopped at cell (%u,%u)", at.xpos, at.ypos);
+  path[lRow] = AlignRowPath(lBack.rbegin(), lBack.rend());
+  path[rRow] = AlignRowPath(rBack.rbegin(), rBack.rend());
+  path[pRow] = AlignRowPath(pBack.rbegin(), pBack.rend());
+  return true;
+}
+
+AlignPath SM::sampleOnHost(random_engine& generator) const {
   CellCoords at{(SeqIdx)(xSize - 1), (SeqIdx)(ySize - 1), EEE};
   vguard<bool> lBack, rBack, pBack;
   while (at.xpos > 0 || at.ypos > 0) {
@@ -298,19 +390,36 @@ AlignPath SM::sample(random_engine& generator) const {
 LogProb SM::logPostProb(const AlignPath& lrpPath) const {
   const AlignColIndex cols = alignPathColumns(lrpPath);
   const AlignRowPath &lPath = lrpPath.at(lRow), &rPath = lrpPath.at(rRow), &pPath = lrpPath.at(pRow);
-  LogProb lp = 0;
+  // the cells the path visits, then their values - one gather on the device, or the dense copy - then the reference's sum
+  vguard<hx_pair_cell> at;
   CellCoords c{0, 0, SSS};
   for (AlignColIndex col = 0; col < cols; ++col) {
     const bool dl = lPath[col], dr = rPath[col], dp = pPath[col];
     if (dl) ++c.xpos;
     if (dr) ++c.ypos;
-    const State before = (State)c.state;
-    c.state = getState(before, dl, dr, dp);
+    c.state = getState((State)c.state, dl, dr, dp);
     if (c.xpos >= xSize || c.ypos >= ySize || !inEnvelope(c.xpos, c.ypos)) return kNegInf;
-    lp += lpTransElimWait(before, (State)c.state) + lpEmit(c);
-    lp = std::min(lp, cell(c));      // "mitigate precision errors"
+    at.push_back(hx_pair_cell{(int32_t)c.xpos, (int32_t)c.ypos, (int32_t)c.state});
   }
-  lp += lpTransElimWait((State)c.state, EEE);
+  vguard<double> value(at.size()), match(at.size());
+  if (detail::hostWalks())
+    for (size_t q = 0; q < at.size(); ++q) {
+      value[q] = cell(at[q].xpos, at[q].ypos, at[q].state);
+      match[q] = (at[q].state == IMM && at[q].xpos > 0 && at[q].ypos > 0) ? logMatch(at[q].xpos, at[q].ypos) : kNegInf;
+    }
+  else
+    detail::check(hx_sibling_batch_read_cells(batch.get(), jobIndex, (int64_t)at.size(), at.data(), value.data(), match.data()),
+                  "hx_sibling_batch_read_cells");
+  LogProb lp = 0;
+  State state = SSS;
+  for (size_t q = 0; q < at.size(); ++q) {
+    const State before = state;
+    state = (State)at[q].state;
+    const CellCoords here{(SeqIdx)at[q].xpos, (SeqIdx)at[q].ypos, (unsigned)at[q].state};
+    lp += lpTransElimWait(before, state) + (state == IMM ? match[q] : lpEmit(here));
+    lp = std::min(lp, value[q]);      // "mitigate precision errors"
+  }
+  lp += lpTransElimWait(state, EEE);
   lp = std::min(lp, lpEnd);
   return lp - lpEnd;
 }

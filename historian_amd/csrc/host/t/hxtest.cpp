@@ -10,7 +10,17 @@
 //                                                  (N4, Sampler::SiblingMatrix; band: envelope around the ungapped diagonal):
 //                                                  lpEnd as a hex float, a seeded sampled alignment, its logPostProb, the first
 //                                                  rows of the parent profile, and fillBatch of two envelopes against single fills
+//   hxtest walks <pair.fa> <model.json> <tl> <tr> [band]     the walks through the sibling matrix of the pair and through a branch
+//                                                  matrix over it (left sequence as parent, right as child, branch tl): a
+//                                                  seeded sampled alignment of either, its logPostProb, the generator's next
+//                                                  word, best() of the Viterbi matrix, sampleBatch of a fillBatch against
+//                                                  single samples, and the number of dense matrix copies read (0 unless
+//                                                  HX_HOST_WALKS=1)
+//   hxtest walktime <pair.fa> <model.json> <tl> <tr> <n> [band]   timing (tools/walks_bench.py): fillBatch of n copies of the
+//                                                  pair's sibling matrix, then - timed apart - what a walk needs first (the dense
+//                                                  copies with HX_HOST_WALKS=1, nothing otherwise), sampleBatch and logPostProb
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -147,6 +157,116 @@ int siblingPair(int nArgs, char** args) {
   return 0;
 }
 
+void printRows(const AlignPath& path, const vguard<FastSeq>& two, AlignRowIndex rows) {
+  for (AlignRowIndex row = 0; row < rows; ++row) {
+    size_t next = 0;
+    for (bool here : path.at(row)) putchar(!here ? '-' : (row < 2 ? two[row].seq[next++] : '*'));
+    putchar('\n');
+  }
+}
+
+int pairWalks(int nArgs, char** args) {
+  const vguard<FastSeq> two = readFastSeqs(args[0]);
+  Require(two.size() == 2, "Sequence file must have exactly two sequences");
+  RateModel rates;
+  rates.readFile(args[1]);
+  const double tl = atof(args[2]), tr = atof(args[3]);
+  const int C = rates.components();
+  const auto left = TreeAlignFuncs::leafPWM(two[0], rates.alphabet, C), right = TreeAlignFuncs::leafPWM(two[1], rates.alphabet, C);
+  vguard<SeqIdx> xPos(left.size() + 1), yPos(right.size() + 1);
+  for (size_t k = 0; k < xPos.size(); ++k) xPos[k] = (SeqIdx)k;
+  for (size_t k = 0; k < yPos.size(); ++k) yPos[k] = (SeqIdx)k;
+  AlignPath diagonal;
+  const size_t width = std::max(left.size(), right.size());
+  for (size_t col = 0; col < width; ++col) {
+    diagonal[0].push_back(col < left.size());
+    diagonal[1].push_back(col < right.size());
+  }
+  const GuideAlignmentEnvelope everywhere, banded(diagonal, 0, 1, nArgs > 4 ? atoi(args[4]) : 10);
+  const GuideAlignmentEnvelope& chosen = nArgs > 4 ? banded : everywhere;
+  typedef Sampler::SiblingMatrix::random_engine Engine;
+  {
+    const Sampler::SiblingMatrix matrix(rates, left, right, tl, tr, chosen, xPos, yPos, 0, 1, 2);
+    Engine generator(20);
+    const AlignPath path = matrix.sample(generator);
+    printf("sibling lpEnd %a\n", matrix.lpEnd);
+    printRows(path, two, 3);
+    printf("sibling logPostProb %a\nsibling next word %lu\n", matrix.logPostProb(path), (unsigned long)generator());
+  }
+  {
+    const Sampler::BranchMatrix forward(rates, left, right, tl, chosen, xPos, yPos, 0, 1);
+    Engine generator(21);
+    const AlignPath path = forward.sample(generator);
+    printf("branch lpEnd %a\n", forward.lpEnd);
+    printRows(path, two, 2);
+    printf("branch logPostProb %a\nbranch next word %lu\n", forward.logPostProb(path), (unsigned long)generator());
+    const Refiner::BranchMatrix viterbi(rates, left, right, tl, chosen, xPos, yPos, 0, 1);
+    printf("viterbi lpEnd %a\n", viterbi.lpEnd);
+    printRows(viterbi.best(), two, 2);
+  }
+  {
+    // two envelopes filled in one device batch and sampled in one launch, against two single matrices, generator for generator
+    typedef Sampler::SiblingMatrix::Args Args;
+    const vguard<Args> both = {Args{&left, &right, tl, tr, &everywhere, &xPos, &yPos, 0, 1, 2}, Args{&left, &right, tl, tr, &banded, &xPos, &yPos, 0, 1, 2}};
+    const auto batch = Sampler::SiblingMatrix::fillBatch(rates, both);
+    Engine g0(30), g1(31), h0(30), h1(31);
+    const vguard<AlignPath> together = Sampler::SiblingMatrix::sampleBatch({batch[0].get(), batch[1].get()}, {&g0, &g1});
+    const Sampler::SiblingMatrix single0(rates, left, right, tl, tr, everywhere, xPos, yPos, 0, 1, 2), single1(rates, left, right, tl, tr, banded, xPos, yPos, 0, 1, 2);
+    const bool same = together[0] == single0.sample(h0) && together[1] == single1.sample(h1) && g0 == h0 && g1 == h1;
+    printf("sampleBatch equals single samples: %s\n", same ? "yes" : "no");
+    printRows(together[1], two, 3);
+  }
+  printf("dense matrix reads: %ld\n", detail::denseMatrixReads());
+  return 0;
+}
+
+int walkTiming(int nArgs, char** args) {
+  const vguard<FastSeq> two = readFastSeqs(args[0]);
+  Require(two.size() == 2, "Sequence file must have exactly two sequences");
+  RateModel rates;
+  rates.readFile(args[1]);
+  const double tl = atof(args[2]), tr = atof(args[3]);
+  const int n = atoi(args[4]), C = rates.components();
+  Require(n >= 1, "At least one matrix");
+  const auto left = TreeAlignFuncs::leafPWM(two[0], rates.alphabet, C), right = TreeAlignFuncs::leafPWM(two[1], rates.alphabet, C);
+  vguard<SeqIdx> xPos(left.size() + 1), yPos(right.size() + 1);
+  for (size_t k = 0; k < xPos.size(); ++k) xPos[k] = (SeqIdx)k;
+  for (size_t k = 0; k < yPos.size(); ++k) yPos[k] = (SeqIdx)k;
+  AlignPath diagonal;
+  for (size_t col = 0; col < std::max(left.size(), right.size()); ++col) {
+    diagonal[0].push_back(col < left.size());
+    diagonal[1].push_back(col < right.size());
+  }
+  const GuideAlignmentEnvelope everywhere, banded(diagonal, 0, 1, nArgs > 5 ? atoi(args[5]) : 10);
+  const GuideAlignmentEnvelope& chosen = nArgs > 5 ? banded : everywhere;
+  typedef Sampler::SiblingMatrix SM;
+  typedef std::chrono::steady_clock Clock;
+  auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  const vguard<SM::Args> args1((size_t)n, SM::Args{&left, &right, tl, tr, &chosen, &xPos, &yPos, 0, 1, 2});
+  for (int rep = 0; rep < 4; ++rep) {        // the first repetition warms up
+    const auto t0 = Clock::now();
+    const auto batch = SM::fillBatch(rates, args1);
+    const auto t1 = Clock::now();
+    if (detail::hostWalks())
+      for (const auto& m : batch) (void)m->cell(0, 0, 0);       // the dense copy a host walk needs before it can start
+    const auto t2 = Clock::now();
+    vguard<SM::random_engine> engines;
+    vguard<const SM*> matrices;
+    vguard<SM::random_engine*> generators;
+    for (int k = 0; k < n; ++k) engines.emplace_back(100 + k);
+    for (int k = 0; k < n; ++k) { matrices.push_back(batch[k].get()); generators.push_back(&engines[k]); }
+    const vguard<AlignPath> paths = SM::sampleBatch(matrices, generators);
+    const auto t3 = Clock::now();
+    double total = 0;
+    for (int k = 0; k < n; ++k) total += batch[k]->logPostProb(paths[k]);
+    const auto t4 = Clock::now();
+    printf("%s %d matrices of %zu x %zu: fillBatch %.2f ms, dense copies %.2f ms, sampleBatch %.2f ms, logPostProb %.2f ms; columns of "
+           "the first alignment %zu, sum of logPostProb %.6f, dense matrix reads %ld\n", rep ? "run" : "warm-up", n, left.size(), right.size(),
+           ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), (size_t)alignPathColumns(paths[0]), total, detail::denseMatrixReads());
+  }
+  return 0;
+}
+
 const Command commands[] = {
     {"logsumexp", 0, 1, "[-slow|-fast]", lseGrid},
     {"seqprofile", 2, 2, "<alphabet> <sequence>", leafProfileJson},
@@ -154,6 +274,8 @@ const Command commands[] = {
     {"expm", 2, 2, "<modelfile> <time>", substitutionMatrix},
     {"branch", 3, 3, "<seqfile> <modelfile> <time>", branchPair},
     {"sibling", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", siblingPair},
+    {"walks", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", pairWalks},
+    {"walktime", 5, 6, "<seqfile> <modelfile> <left time> <right time> <matrices> [band]", walkTiming},
 };
 
 }  // namespace

@@ -233,6 +233,29 @@ __global__ void k_branch_dense(const DevBranch* __restrict__ jobs, const int job
   }
 }
 
+// the three-state lattice as the walks of hx_pairdp.h see it (BranchMatrixBase::getColumn / lpEmit, src/sampler.cpp:1166-1183)
+struct BranchLattice {
+  typedef DevBranch Job;
+  enum { NS = 3, ND = 4, END = 3 };
+  static __device__ __forceinline__ void column(const int i, const int j, const int state, bool& x, bool& y) {
+    const bool m = state == 0 && i > 0 && j > 0;
+    x = m || state == 2;
+    y = m || state == 1;
+  }
+  // lpEmit: where the term lies (p, left alone when it lies nowhere) and its value when it lies nowhere
+  struct Emit {
+    const double *emis, *y_emit;
+    int64_t ss;
+    __device__ __forceinline__ explicit Emit(const DevBranch& J) : emis(J.emis), y_emit(J.y_emit), ss(J.strip_stride) {}
+    __device__ __forceinline__ double from(const int i, const int j, const int state, const double*& p) const {
+      if (state == 0 && i > 0 && j > 0) p = emis + cell_slot(ss, i, j);
+      if (state == 1 && j > 0) p = y_emit + (j - 1);
+      return (state == 0 || state == 1) ? HX_NEG_INF : 0.0;
+    }
+  };
+  static __device__ __forceinline__ bool self_loop(const int) { return false; }
+};
+
 }  // namespace
 }  // namespace hx
 
@@ -250,6 +273,8 @@ struct hx_branch_batch {
   hipEvent_t ev[2] = {nullptr, nullptr};
   hipStream_t last_stream = nullptr;
   bool done = false;
+  float walk_ms = -1.f;             // the walk kernel of the last best_paths / sample_paths (HIP events)
+  bool viterbi = false;             // the form of the last run
 };
 
 extern "C" {
@@ -393,6 +418,7 @@ int hx_branch_batch_run(hx_branch_batch* b, int32_t viterbi, void* stream) {
   }
   if (hipEventRecord(b->ev[1], st) != hipSuccess || hipGetLastError() != hipSuccess) return api_fail(HX_ERR_HIP, "hx_branch_batch_run: launch failed");
   b->done = true;
+  b->viterbi = viterbi != 0;
   b->last_stream = st;
   return HX_OK;
 }
@@ -436,5 +462,29 @@ int hx_branch_batch_last_kernel_ms(hx_branch_batch* b, float* ms) {
     return api_fail(HX_ERR_HIP, "hx_branch_batch_last_kernel_ms: HIP call failed");
   return HX_OK;
 }
+
+int hx_branch_batch_best_paths(hx_branch_batch* b, uint8_t* states, int64_t cap, int32_t* n_steps) {
+  if (b && b->done && !b->viterbi) return api_fail(HX_ERR_STATE, "hx_branch_batch_best_paths: the batch last ran with viterbi = 0");
+  return pair_walk_paths<BranchLattice, true>(b, nullptr, nullptr, states, cap, n_steps, nullptr);
+}
+
+int hx_branch_batch_sample_paths(hx_branch_batch* b, const uint32_t* words, const int64_t* word_off, uint8_t* states, int64_t cap,
+                                 int32_t* n_steps, int32_t* words_used) {
+  if (b && b->done && b->viterbi) return api_fail(HX_ERR_STATE, "hx_branch_batch_sample_paths: the batch last ran with viterbi != 0");
+  return pair_walk_paths<BranchLattice, false>(b, words, word_off, states, cap, n_steps, words_used);
+}
+
+int64_t hx_branch_batch_max_steps(const hx_branch_batch* b) {
+  int64_t most = 0;
+  if (b)
+    for (const DevBranch& J : b->jobs) most = std::max<int64_t>(most, (int64_t)(J.X - 1) + (J.Y - 1) + 1);      // (every state but End moves: header)
+  return most;
+}
+
+int hx_branch_batch_read_cells(hx_branch_batch* b, int32_t job, int64_t n, const hx_pair_cell* at, double* cells, double* log_match) {
+  return pair_read_cells<3>(b, job, n, at, cells, log_match);
+}
+
+int hx_branch_batch_last_walk_ms(hx_branch_batch* b, float* ms) { return pair_last_walk_ms(b, ms); }
 
 }  // extern "C"

@@ -269,6 +269,30 @@ __global__ void k_sibling_dense(const DevSibling* __restrict__ jobs, const int j
   }
 }
 
+// the eleven-state lattice as the walks of hx_pairdp.h see it (SiblingMatrix::getColumn / lpEmit, src/sampler.cpp:1414-1449)
+struct SiblingLattice {
+  typedef DevSibling Job;
+  enum { NS = 11, ND = 12, END = EEE };
+  static __device__ __forceinline__ void column(const int i, const int j, const int state, bool& l, bool& r) {
+    l = (state == IMM && i > 0 && j > 0) || state == IMD || ((state == IIW || state == IIX) && i > 0);
+    r = (state == IMM && i > 0 && j > 0) || state == IDM || ((state == IMI || state == IDI) && j > 0);
+  }
+  // lpEmit: where the term lies (p, left alone when it lies nowhere) and its value when it lies nowhere
+  struct Emit {
+    const double *emis, *x_emit, *y_emit;
+    int64_t ss;
+    __device__ __forceinline__ explicit Emit(const DevSibling& J) : emis(J.emis), x_emit(J.x_emit), y_emit(J.y_emit), ss(J.strip_stride) {}
+    __device__ __forceinline__ double from(const int i, const int j, const int state, const double*& p) const {
+      const bool right = state == IDM || state == IMI || state == IDI, left = state == IMD || state == IIW || state == IIX;
+      if (state == IMM && i > 0 && j > 0) p = emis + cell_slot(ss, i, j);
+      if (right && j > 0) p = y_emit + (j - 1);
+      if (left && i > 0) p = x_emit + (i - 1);
+      return (state == IMM || right || left) ? HX_NEG_INF : 0.0;
+    }
+  };
+  static __device__ __forceinline__ bool self_loop(const int state) { return state == IDD; }
+};
+
 }  // namespace
 }  // namespace hx
 
@@ -285,6 +309,7 @@ struct hx_sibling_batch {
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};       // before the step, before the fill, after it
   hipStream_t last_stream = nullptr;
   bool done = false;
+  float walk_ms = -1.f;             // the walk kernel of the last best_paths / sample_paths (HIP events)
 };
 
 extern "C" {
@@ -477,5 +502,23 @@ int hx_sibling_batch_last_kernel_ms(hx_sibling_batch* b, float* fill_ms, float* 
     return api_fail(HX_ERR_HIP, "hx_sibling_batch_last_kernel_ms: HIP call failed");
   return HX_OK;
 }
+
+int hx_sibling_batch_sample_paths(hx_sibling_batch* b, const uint32_t* words, const int64_t* word_off, uint8_t* states, int64_t cap,
+                                  int32_t* n_steps, int32_t* words_used) {
+  return pair_walk_paths<SiblingLattice, false>(b, words, word_off, states, cap, n_steps, words_used);
+}
+
+int64_t hx_sibling_batch_max_steps(const hx_sibling_batch* b) {
+  int64_t most = 0;
+  if (b)
+    for (const DevSibling& J : b->jobs) most = std::max<int64_t>(most, 3 * ((int64_t)(J.X - 1) + (J.Y - 1)) + 3);      // (wait states and IDD stay: header)
+  return most;
+}
+
+int hx_sibling_batch_read_cells(hx_sibling_batch* b, int32_t job, int64_t n, const hx_pair_cell* at, double* cells, double* log_match) {
+  return pair_read_cells<NS>(b, job, n, at, cells, log_match);
+}
+
+int hx_sibling_batch_last_walk_ms(hx_sibling_batch* b, float* ms) { return pair_last_walk_ms(b, ms); }
 
 }  // extern "C"

@@ -421,6 +421,45 @@ int hx_branch_batch_read_matrix(hx_branch_batch* b, int32_t job, double* out);
 int64_t hx_branch_batch_total_cells(const hx_branch_batch* b);
 int hx_branch_batch_last_kernel_ms(hx_branch_batch* b, float* ms);
 
+/* ---- row N4: a filled pair matrix consumed where it lies ------------------------------------------------------------------
+ * A walk touches x + y cells of an x * y matrix; these entry points walk the device-resident matrices of a batch (one
+ * wavefront per job, all jobs side by side) and gather the cells along given paths, so that no consumer copies a matrix.
+ *
+ * states is [n_jobs][cap]: the state chosen at every step of job k's walk, End side first - states[k][0] is the state the
+ * walk chose at cell (x_len, y_len) from End; the caller rebuilds coordinates and columns with getColumn as the reference's
+ * loops do (src/refiner.cpp:62-104, src/sampler.cpp:1088-1120, 1343-1386).  n_steps[k] = the number of steps, or < 0 for a walk
+ * that failed, which never stops the other jobs: -1 lpEnd = -inf, -2 a state of zero probability (the reference's Assert),
+ * -3 cap too small, -5 the reference's "random_key_log failed", -6 out of words.
+ * How many steps a walk can take follows from the transition table.  Three states: every state but End moves at least one
+ * position, so at most x_len + y_len + 1.  Eleven states: the wait states and IDD do not move, IDD is entered from a wait
+ * state only and a wait state from an emitting state only, so at most two steps that stay between two that move and three
+ * (EEE, IDD, a wait state) before the first: at most 3 (l_len + r_len) + 3.  hx_*_batch_max_steps returns the largest bound
+ * over the jobs of the batch: size cap once.
+ *
+ * best_paths: Refiner::BranchMatrix::best - the first maximal state in the order Match, Insert, Delete; additions and
+ * comparisons only, so the path is bit-identical to the host walk through the same matrix.  The batch must last have run with
+ * viterbi != 0 (else HX_ERR_STATE); sample_paths needs viterbi == 0.
+ * sample_paths: random_key_log (src/util.h:220-236) over w[s] = (cell(s) + T[s][state]) + lpEmit in state order, u = word / 2^32
+ * for one word of the caller's 32-bit engine per step (random_double, src/util.h:138-142); job k's words are
+ * words[word_off[k] .. word_off[k + 1]), words_used[k] says how many its walk consumed.  The eleven-state walk, standing in
+ * IDD, first consumes TWO words without interpreting them: the reference draws a std::geometric_distribution<int> there for
+ * the self-loop the fill eliminated (libstdc++: one canonical double = two words), and the caller turns them into the count.
+ * exp() is the device library's: a walk can leave the host's only where a draw falls within rounding of the boundary
+ * between two states' shares. */
+int hx_branch_batch_best_paths(hx_branch_batch* b, uint8_t* states, int64_t cap, int32_t* n_steps);
+int hx_branch_batch_sample_paths(hx_branch_batch* b, const uint32_t* words, const int64_t* word_off /* [n_jobs + 1] */,
+                                 uint8_t* states, int64_t cap, int32_t* n_steps, int32_t* words_used);
+int64_t hx_branch_batch_max_steps(const hx_branch_batch* b);
+/* Duration in milliseconds of the walk kernel of the last best_paths / sample_paths (HIP events around it). */
+int hx_branch_batch_last_walk_ms(hx_branch_batch* b, float* ms);
+/* cells[q] = the matrix's value at (at[q].xpos, at[q].ypos, at[q].state), log_match[q] = logMatch(xpos, ypos) as the fill
+ * used it (-inf where xpos or ypos is 0 or the cell is outside the envelope; log_match may be NULL).  HX_ERR_RANGE for a
+ * coordinate outside the matrix.  Path scores are summed by the caller in the reference's order. */
+typedef struct hx_pair_cell {
+  int32_t xpos, ypos, state;
+} hx_pair_cell;
+int hx_branch_batch_read_cells(hx_branch_batch* b, int32_t job, int64_t n, const hx_pair_cell* at, double* cells, double* log_match);
+
 /* ---- row N4, second lattice: the sibling-pair parent-proposal DP ---------------------------------------------------------
  * Sampler::SiblingMatrix (reference src/sampler.h:226-325, src/sampler.cpp:1185-1342): a left child profile and a right
  * child profile under their unobserved parent, eleven states per cell over TreeAlignFuncs::SparseDPMatrix<11>, inside a
@@ -456,6 +495,12 @@ int hx_sibling_batch_read_matrix(hx_sibling_batch* b, int32_t job, double* out);
 int64_t hx_sibling_batch_total_cells(const hx_sibling_batch* b);
 /* the fill kernel of the last run; step_ms (may be NULL): the whole step - clearing, emission pre-pass and fill */
 int hx_sibling_batch_last_kernel_ms(hx_sibling_batch* b, float* fill_ms, float* step_ms);
+/* The walks and the gather of the three-state batch (see hx_branch_batch_sample_paths), over the eleven states. */
+int hx_sibling_batch_sample_paths(hx_sibling_batch* b, const uint32_t* words, const int64_t* word_off /* [n_jobs + 1] */,
+                                  uint8_t* states, int64_t cap, int32_t* n_steps, int32_t* words_used);
+int64_t hx_sibling_batch_max_steps(const hx_sibling_batch* b);
+int hx_sibling_batch_last_walk_ms(hx_sibling_batch* b, float* ms);
+int hx_sibling_batch_read_cells(hx_sibling_batch* b, int32_t job, int64_t n, const hx_pair_cell* at, double* cells, double* log_match);
 
 #ifdef __cplusplus
 }
