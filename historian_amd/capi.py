@@ -795,9 +795,11 @@ class QuickBatch:
         return ms.value
 
 
-def sumprod_columns(parent, ins_prob, log_cpt_weight, branch_sub, evec, evec_inv, esc, tokens, weight=None, want_root_post=False):
+def sumprod_columns(parent, ins_prob, log_cpt_weight, branch_sub, evec, evec_inv, esc, tokens, weight=None, want_root_post=False,
+                    stream=None):
     """hx_sumprod_columns: parent [N]; ins_prob [C][A]; log_cpt_weight [C]; branch_sub [C][N][A][A]; evec, evec_inv [C][A][A]
-    complex; esc [C][N][A][A] complex; tokens [n_cols][N] int8 (-1 wildcard, -2 gap); weight [n_cols] or None.
+    complex; esc [C][N][A][A] complex; tokens [n_cols][N] int8 (-1 wildcard, -2 gap); weight [n_cols] or None; stream: the
+    stream the kernels run on (the call returns when they are done).
     Returns col_log_like [n_cols], root_counts [C][A], eigen_counts [C][A][A] complex, root_post [n_cols][A] or None."""
     ins_prob = np.ascontiguousarray(ins_prob, dtype=np.float64)
     c, a = ins_prob.shape
@@ -837,7 +839,7 @@ def sumprod_columns(parent, ins_prob, log_cpt_weight, branch_sub, evec, evec_inv
     post = np.empty((n_cols, a)) if want_root_post else None
     _check(load().hx_sumprod_columns(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), _p(w, _f64p) if w is not None else C.cast(None, _f64p),
                                      n_cols, _p(cll, _f64p), _p(root, _f64p), _p(ere, _f64p), _p(eim, _f64p),
-                                     _p(post, _f64p) if post is not None else C.cast(None, _f64p), None))
+                                     _p(post, _f64p) if post is not None else C.cast(None, _f64p), C.c_void_p(stream or 0)))
     return cll, root, ere + 1j * eim, post
 
 

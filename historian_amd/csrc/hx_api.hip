@@ -1231,11 +1231,18 @@ static bool band2_wanted(bool linear, int n, int n_w32) {
 static hipStream_t side_fork(hx_batch* b, hipStream_t st) {
   DeviceTables& D = g_dev[b->device];
   if (getenv("HX_NO_SIDE_STREAM")) return st;
-  if (!D.side_stream && hipStreamCreateWithFlags(&D.side_stream, hipStreamNonBlocking) != hipSuccess) { D.side_stream = nullptr; return st; }
+  hipStream_t side;
+  {
+    // (batches of one device may be launched from several host threads: one of them creates the stream)
+    std::lock_guard<std::mutex> lock(D.copy_mutex);
+    if (!D.side_stream && hipStreamCreateWithFlags(&D.side_stream, hipStreamNonBlocking) != hipSuccess) D.side_stream = nullptr;
+    side = D.side_stream;
+  }
+  if (!side) return st;
   for (int e = 0; e < 2; ++e)
     if (!b->ev_side[e] && hipEventCreateWithFlags(&b->ev_side[e], hipEventDisableTiming) != hipSuccess) { b->ev_side[e] = nullptr; return st; }
-  if (hipEventRecord(b->ev_side[0], st) != hipSuccess || hipStreamWaitEvent(D.side_stream, b->ev_side[0], 0) != hipSuccess) return st;
-  return D.side_stream;
+  if (hipEventRecord(b->ev_side[0], st) != hipSuccess || hipStreamWaitEvent(side, b->ev_side[0], 0) != hipSuccess) return st;
+  return side;
 }
 static int side_join(hx_batch* b, hipStream_t st, hipStream_t side) {
   if (side == st) return HX_OK;
@@ -1422,7 +1429,6 @@ int hx_batch_backward(hx_batch* b, void* stream) {
   if ((rc = use_device(b)) != HX_OK) return rc;
   const DeviceTables& D = g_dev[b->device];
   hipStream_t st = static_cast<hipStream_t>(stream);
-  ensure_state_records(b, st);                    // (the Backward fill of chain profiles runs the general pipeline, which reads them)
   if (!b->d_bwd) {
     // not pre-allocated with HX_KEEP_BACKWARD: allocate the Backward matrices now and re-publish the job tables
     HIP_TRY(hipStreamSynchronize(b->last_stream));
@@ -1431,8 +1437,13 @@ int hx_batch_backward(hx_batch* b, void* stream) {
     if ((rc = publish_jobs(b)) != HX_OK) return rc;
   } else if (st != b->last_stream) {
     // the Backward fill reads what the Forward launch prepared (and, for the posterior, follows it): order the streams
+    // (last_stream is the stream of the last Forward or Backward launch - readers leave it alone - so st == last_stream
+    // means that st already follows the Forward launch)
     HIP_TRY(hipStreamWaitEvent(st, b->ev[0][1], 0));
   }
+  // Only now, behind the Forward launch on either branch: for a batch of leaf pairs the records are built here, from what the
+  // Forward launch's preparation wrote (the Backward fill of chain profiles runs the general pipeline, which reads them)
+  ensure_state_records(b, st);
   b->used_multi[1] = false;
   HIP_TRY(hipEventRecord(b->ev[1][0], st));
   for (int c = 0; c < KC_COUNT; ++c) {

@@ -18,6 +18,22 @@
  *     -inf and the caller widens the band (reference src/recon.cpp:956-975).
  *   - all log-probabilities are IEEE fp64; -inf means probability zero.
  *   - "stream" arguments are a hipStream_t passed as void* (NULL = default stream).
+ *
+ * Streams
+ *   - Asynchronous on the caller's stream (they return once the work is queued): hx_batch_forward, hx_batch_backward on a
+ *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
+ *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
+ *     matrices), then queues; hx_sumprod_columns runs its kernels on `stream` and returns when they are done.
+ *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
+ *     Forward launch (an event), with no host synchronisation.
+ *   - Readers (results, matrices, cells, tracebacks, walks, counts) synchronise with the batch's LAST stream only - the stream
+ *     of its most recent launch - and queue their own kernels there.
+ *   - Any other two launches of one batch on two different streams (Forward after Forward, Forward after Backward, ...) are
+ *     the caller's to order; launches of one batch on one stream need no synchronisation between them.
+ *   - Each device has one side stream (the edge kernel of large banded batches: forked behind the preparation, joined before
+ *     the fill's last kernel on the caller's stream) and one copy stream (hx_batch_read_matrix_async), shared by all batches
+ *     of the device, from any host thread.  Batches that use them queue behind one another there; results do not change.
+ *   - Stream capture (HIP graphs) is not supported: the calls contain synchronous copies and allocations.
  */
 #ifndef HISTORIAN_HIP_H
 #define HISTORIAN_HIP_H
