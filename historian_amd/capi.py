@@ -522,13 +522,42 @@ class Batch:
 
 
 class _PairWalks:
-    """The walks through the device-resident matrices of a BranchBatch / SiblingBatch and the gather of cells along paths
-    (include/historian_hip.h: hx_*_batch_best_paths / sample_paths / read_cells)."""
+    """What a BranchBatch and a SiblingBatch share: the batch's lifetime, its results and dense matrices, the walks through the
+    device-resident matrices and the gather of cells along paths (include/historian_hip.h: hx_*_batch_destroy / results /
+    read_matrix / total_cells / best_paths / sample_paths / read_cells)."""
 
     _prefix = None
+    _states = None      # states per cell
 
     def _fn(self, name):
         return getattr(load(), "hx_%s_batch_%s" % (self._prefix, name))
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lp_end(self):
+        out = np.empty(self.n)
+        _check(self._fn("results")(self._h, _p(out, _f64p)))
+        return out
+
+    def read_matrix(self, job):
+        """dense [X][Y][states] of one job"""
+        if not 0 <= job < self.n:
+            _check(self._fn("read_matrix")(self._h, job, _p(np.empty(1), _f64p)))      # raises HX_ERR_RANGE
+        out = np.empty(self.shapes[job] + (self._states,))
+        _check(self._fn("read_matrix")(self._h, job, _p(out, _f64p)))
+        return out
+
+    def total_cells(self):
+        return int(self._fn("total_cells")(self._h))
 
     def max_steps(self):
         return int(self._fn("max_steps")(self._h))
@@ -576,6 +605,7 @@ class BranchBatch(_PairWalks):
     max_distance)."""
 
     _prefix = "branch"
+    _states = 3
 
     def best_paths(self, cap=None, raw=False):
         """Refiner::BranchMatrix::best of every job (the batch must have run with viterbi=True).  -> (paths, n_steps) as
@@ -615,32 +645,8 @@ class BranchBatch(_PairWalks):
         self._h = C.c_void_p()
         _check(load().hx_branch_batch_create(arr, self.n, C.byref(self._h)))
 
-    def close(self):
-        if self._h:
-            load().hx_branch_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, viterbi=True, stream=None):
         _check(load().hx_branch_batch_run(self._h, 1 if viterbi else 0, C.c_void_p(stream or 0)))
-
-    def lp_end(self):
-        out = np.empty(self.n)
-        _check(load().hx_branch_batch_results(self._h, _p(out, _f64p)))
-        return out
-
-    def read_matrix(self, job):
-        out = np.empty(self.shapes[job] + (3,))
-        _check(load().hx_branch_batch_read_matrix(self._h, job, _p(out, _f64p)))
-        return out
-
-    def total_cells(self):
-        return int(load().hx_branch_batch_total_cells(self._h))
 
     def kernel_ms(self):
         ms = C.c_float()
@@ -655,6 +661,7 @@ class SiblingBatch(_PairWalks):
 
     STATES = ("IMM", "IMD", "IDM", "IDD", "WWW", "WWX", "WXW", "IMI", "IIW", "IDI", "IIX")
     _prefix = "sibling"
+    _states = 11
 
     def __init__(self, jobs):
         self.n = len(jobs)
@@ -684,35 +691,8 @@ class SiblingBatch(_PairWalks):
         self._h = C.c_void_p()
         _check(load().hx_sibling_batch_create(arr, self.n, C.byref(self._h)))
 
-    def close(self):
-        if self._h:
-            load().hx_sibling_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def run(self, stream=None):
         _check(load().hx_sibling_batch_run(self._h, C.c_void_p(stream or 0)))
-
-    def lp_end(self):
-        out = np.empty(self.n)
-        _check(load().hx_sibling_batch_results(self._h, _p(out, _f64p)))
-        return out
-
-    def read_matrix(self, job):
-        """dense [l_len + 1][r_len + 1][11]"""
-        if not 0 <= job < self.n:
-            _check(load().hx_sibling_batch_read_matrix(self._h, job, _p(np.empty(1), _f64p)))
-        out = np.empty(self.shapes[job] + (11,))
-        _check(load().hx_sibling_batch_read_matrix(self._h, job, _p(out, _f64p)))
-        return out
-
-    def total_cells(self):
-        return int(load().hx_sibling_batch_total_cells(self._h))
 
     def kernel_ms(self):
         """(fill kernel, whole step: clearing + emission pre-pass + fill) of the last run, HIP events"""

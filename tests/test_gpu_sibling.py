@@ -139,7 +139,7 @@ def test_a_thousand_by_a_thousand(thousand, band):
 
 def test_a_right_child_too_long_for_lds():
     # above 8192 columns the right child's side of a step (rEmit, envelope coordinate) is read from memory inside the step:
-    # k_sibling_fill<false>, and k_branch_fill<*, false> of the three-state kernel the schedule comes from
+    # k_pair_fill<SiblingCell, false>, and k_pair_fill<BranchCell<*>, false> of the three-state lattice that shares the sweep
     built = [build((61, 70, 8300, 1, 4, None, False, True)), build((62, 70, 8250, 1, 4, 5, False, True))]
     b = capi.SiblingBatch([as_job(case, m) for case, m in built])
     b.run()

@@ -1,11 +1,12 @@
 """Per-branch pair DPs (next row N4, hx_branch.hip) on a batch the size of a refinement sweep: every branch of a 64-leaf tree
 (126 branches), parent and child profiles of `length` positions over the 20-letter alphabet, band 20 around the diagonal or
-none.  Prints kernel time and cells/s (24 B/cell: three fp64 states) for the Viterbi and the log_sum_exp form.
-    python tools/branch_bench.py [length] [branches] [band]       (on the GPU box)"""
+none.  Prints, for the Viterbi and the log_sum_exp form, over `reps` timed runs behind a warm-up run (HIP events): the fill
+kernel's median time and spread, every sample, and Gcell/s (24 B/cell: three fp64 states).
+    python tools/branch_bench.py [length] [branches] [band] [reps]       (on the GPU box)"""
 import math
 import os
+import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,6 +17,7 @@ from historian_amd import capi, hostmodel
 length = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 126
 band = int(sys.argv[3]) if len(sys.argv) > 3 else -1
+reps = int(sys.argv[4]) if len(sys.argv) > 4 else 7
 capi.init(0, hostmodel.lse_table())
 rng = np.random.default_rng(3)
 A = 20
@@ -34,12 +36,14 @@ if band >= 0:
 for viterbi in (True, False):
     b.run(viterbi=viterbi)
     b.lp_end()
-    t0 = time.perf_counter()
-    b.run(viterbi=viterbi)
-    lp = b.lp_end()
-    wall = time.perf_counter() - t0
-    ms = b.kernel_ms()
-    print("%d branches of %d x %d, band %s, %s: fill kernel %.2f ms = %.2f Gcell/s (%.3f of the HBM roofline at 24 B/cell), with emission "
-          "and clearing %.2f ms; lpEnd[0] %.4f" % (n, length, length, band if band >= 0 else "none", "Viterbi" if viterbi else "log_sum_exp", ms,
-                                                   cells / ms / 1e6, cells * 24 / (ms * 1e-3) / 8e12, wall * 1e3, lp[0]))
+    fills = []
+    for _ in range(reps):
+        b.run(viterbi=viterbi)
+        lp = b.lp_end()
+        fills.append(b.kernel_ms())
+    ms = statistics.median(fills)
+    print("%d branches of %d x %d, band %s, %s: fill kernel %.3f ms (min %.3f, max %.3f over %d runs) = %.2f Gcell/s (%.3f of the HBM "
+          "roofline at 24 B/cell); lpEnd[0] %.4f; samples %s"
+          % (n, length, length, band if band >= 0 else "none", "Viterbi" if viterbi else "log_sum_exp", ms, min(fills), max(fills), reps,
+             cells / ms / 1e6, cells * 24 / (ms * 1e-3) / 8e12, lp[0], " ".join("%.4f" % f for f in fills)))
 b.close()

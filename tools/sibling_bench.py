@@ -1,8 +1,8 @@
 """The sibling-pair parent-proposal DP (row N4's eleven-state lattice, hx_sibling.hip) on batches the size of
 tools/branch_bench.py's: `jobs` pairs of child profiles of `length` positions over the 20-letter alphabet, one component, band
 around the diagonal or none.  Prints, over `reps` timed runs behind a warm-up run (HIP events): the fill kernel's median time
-and spread, Gcell/s, the fraction of the HBM roofline at 88 B/cell (eleven fp64 states), time per table log_sum_exp (20 per
-cell), and the whole step - clearing, emission pre-pass and fill - next to it.
+and spread, every sample, Gcell/s, the fraction of the HBM roofline at 88 B/cell (eleven fp64 states), time per table
+log_sum_exp (20 per cell), and the whole step - clearing, emission pre-pass and fill - next to it.
     python tools/sibling_bench.py [length] [jobs] [band] [reps]       (on the GPU box)"""
 import math
 import os
@@ -49,8 +49,8 @@ for _ in range(reps):
 ms, st = statistics.median(fills), statistics.median(steps)
 print("%d sibling pairs of %d x %d, band %s: fill kernel %.2f ms (min %.2f, max %.2f over %d runs) = %.2f Gcell/s (%.3f of the HBM "
       "roofline at 88 B/cell), %.2f ps per table log_sum_exp at %d per cell; whole step (clear + emission + fill) %.2f ms "
-      "(min %.2f, max %.2f) = %.2f Gcell/s (%.3f); lpEnd[0] %.4f"
+      "(min %.2f, max %.2f) = %.2f Gcell/s (%.3f); lpEnd[0] %.4f; fill samples %s; step samples %s"
       % (n, length, length, band if band >= 0 else "none", ms, min(fills), max(fills), reps, cells / ms / 1e6,
          cells * 88 / (ms * 1e-3) / 8e12, ms * 1e9 / (cells * LSE_PER_CELL), LSE_PER_CELL, st, min(steps), max(steps),
-         cells / st / 1e6, cells * 88 / (st * 1e-3) / 8e12, lp[0]))
+         cells / st / 1e6, cells * 88 / (st * 1e-3) / 8e12, lp[0], " ".join("%.4f" % f for f in fills), " ".join("%.4f" % f for f in steps)))
 b.close()
