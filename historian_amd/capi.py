@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HX_LIB_PATH") or os.path.join(_HERE, "lib", "libhistorian_hip.so")
 
 HX_LSE_TABLE_ENTRIES = 100002
+HX_ERR_INVALID_ARG, HX_ERR_RANGE = -1, -8     # hx_status values the tests name (include/historian_hip.h)
 HX_LSE_EXACT, HX_LSE_FAST, HX_KEEP_BACKWARD, HX_FORCE_GENERIC, HX_SPARSE_ENVELOPE = 128, 1, 2, 4, 8
 HX_LSE_DEFAULT = 256    # the library's default policy (flags without any policy bit: HX_LSE_TRUNC)
 HX_BAND_COMPRESSED = 32   # banded jobs keep only the swept step windows (include/historian_hip.h)
@@ -90,6 +91,11 @@ class HxCell(C.Structure):
                 ("log_post_prob", C.c_double)]
 
 
+class HxDistanceModel(C.Structure):
+    _fields_ = [("alph_size", C.c_int32), ("n_components", C.c_int32), ("sub_rate", C.POINTER(C.c_double)),
+                ("cpt_weight", C.POINTER(C.c_double)), ("expected_sub_rate", C.c_double)]
+
+
 EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_create", "hx_batch_destroy",
            "hx_batch_forward", "hx_batch_backward", "hx_batch_sync", "hx_batch_lp_end", "hx_batch_lp_start",
            "hx_batch_layout", "hx_batch_read_matrix", "hx_batch_read_cells", "hx_batch_read_prepared",
@@ -105,7 +111,8 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_sibling_batch_read_matrix", "hx_sibling_batch_total_cells", "hx_sibling_batch_last_kernel_ms",
            "hx_branch_batch_best_paths", "hx_branch_batch_sample_paths", "hx_branch_batch_max_steps", "hx_branch_batch_read_cells",
            "hx_sibling_batch_sample_paths", "hx_sibling_batch_max_steps", "hx_sibling_batch_read_cells",
-           "hx_branch_batch_last_walk_ms", "hx_sibling_batch_last_walk_ms"]
+           "hx_branch_batch_last_walk_ms", "hx_sibling_batch_last_walk_ms",
+           "hx_distance_matrix", "hx_distance_neg_log_like", "hx_distance_last_kernel_ms", "hx_distance_last_products"]
 
 
 class HxError(RuntimeError):
@@ -192,6 +199,10 @@ def load():
     lib.hx_sumprod_columns.argtypes = [C.POINTER(HxSumprodModel), C.POINTER(C.c_int8), _f64p, C.c_int64, _f64p, _f64p, _f64p, _f64p,
                                        _f64p, vp]
     lib.hx_sumprod_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+    lib.hx_distance_matrix.argtypes = [C.POINTER(HxDistanceModel), C.POINTER(C.c_int8), C.c_int32, C.c_int64, C.c_int32, _f64p, _i32p, vp]
+    lib.hx_distance_neg_log_like.argtypes = [C.POINTER(HxDistanceModel), _i32p, _f64p, C.c_int32, _f64p, vp]
+    lib.hx_distance_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+    lib.hx_distance_last_products.argtypes = [C.POINTER(C.c_int64)]
     lib.hx_batch_read_matrix_async.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
     lib.hx_batch_indel_counts.argtypes = [vp, C.c_int32, _f64p, _f64p]
@@ -827,3 +838,58 @@ def sumprod_kernel_ms():
     ms = C.c_float()
     _check(load().hx_sumprod_last_kernel_ms(C.byref(ms)))
     return ms.value
+
+
+def _distance_model(sub_rate, cpt_weight, expected_sub_rate):
+    sub_rate = np.ascontiguousarray(sub_rate, dtype=np.float64)
+    cpt_weight = np.ascontiguousarray(cpt_weight, dtype=np.float64)
+    if sub_rate.ndim != 3 or sub_rate.shape[1] != sub_rate.shape[2] or cpt_weight.shape != (sub_rate.shape[0],):
+        raise ValueError("sub_rate must be [C][A][A] and cpt_weight [C]")
+    m = HxDistanceModel()
+    m.alph_size, m.n_components = sub_rate.shape[1], sub_rate.shape[0]
+    m.sub_rate, m.cpt_weight = _p(sub_rate, _f64p), _p(cpt_weight, _f64p)
+    m.expected_sub_rate = float(expected_sub_rate)
+    return m, (sub_rate, cpt_weight)
+
+
+def distance_matrix(sub_rate, cpt_weight, expected_sub_rate, tokens, max_iterations=100, stream=None):
+    """hx_distance_matrix: sub_rate [C][A][A]; cpt_weight [C]; expected_sub_rate: RateModel::expectedSubstitutionRate
+    (hostmodel.expected_sub_rate); tokens [n_seqs][n_cols] int8, negative = not counted; stream: the stream the kernels
+    run on (the call returns when they are done).  Returns dist [n_seqs][n_seqs] and the likelihood evaluations of
+    every pair in the order (0,1), (0,2) ..."""
+    m, keep = _distance_model(sub_rate, cpt_weight, expected_sub_rate)
+    tokens = np.ascontiguousarray(tokens, dtype=np.int8)
+    if tokens.ndim != 2:
+        raise ValueError("tokens must be [n_seqs][n_cols]")
+    n, cols = tokens.shape
+    dist = np.zeros((n, n))
+    evals = np.zeros(max(n * (n - 1) // 2, 1), dtype=np.int32)
+    _check(load().hx_distance_matrix(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), n, cols, max_iterations, _p(dist, _f64p),
+                                     _p(evals, _i32p), C.c_void_p(stream or 0)))
+    return dist, evals[:n * (n - 1) // 2]
+
+
+def distance_neg_log_like(sub_rate, cpt_weight, counts, t, stream=None):
+    """hx_distance_neg_log_like: counts [n][A][A] int32, t [n] -> f [n], the negative log-likelihood of each count matrix
+    at its t (the evaluation inside hx_distance_matrix's search)."""
+    m, keep = _distance_model(sub_rate, cpt_weight, 1.)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    if counts.shape != (t.size, m.alph_size, m.alph_size) or t.ndim != 1:
+        raise ValueError("counts must be [n][A][A] and t [n]")
+    f = np.empty(t.size)
+    _check(load().hx_distance_neg_log_like(C.byref(m), _p(counts, _i32p), _p(t, _f64p), t.size, _p(f, _f64p), C.c_void_p(stream or 0)))
+    return f
+
+
+def distance_kernel_ms():
+    ms = C.c_float()
+    _check(load().hx_distance_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+def distance_products():
+    """A x A matrix products taken by the most recent distance_matrix on this thread"""
+    n = C.c_int64()
+    _check(load().hx_distance_last_products(C.byref(n)))
+    return n.value

@@ -211,6 +211,8 @@ struct AlphabetOwner {
   size_t alphabetSize() const { return alphabet.size(); }
 };
 
+constexpr int DefaultDistanceMatrixIterations = 100;
+
 struct RateModel : AlphabetOwner {
   double insRate = 0, delRate = 0;           // indel rates and extension probabilities
   double insExtProb = 0, delExtProb = 0;
@@ -222,6 +224,11 @@ struct RateModel : AlphabetOwner {
   void read(const string& jsonText);
   static Vec getEqmProbVector(const Mat& rates);       // src/model.cpp:282-320
   vguard<Mat> getSubProbMatrix(double time) const;     // src/model.cpp:322-334 (gsl_linalg_exponential_ss restated)
+  // Tree estimation (hx_host_tree.cpp): src/model.cpp:336-347, 506-549.  distanceMatrix runs on the device
+  // (hx_distance_matrix); HX_HOST_DISTANCES=1 or an alphabet above 32 symbols takes mlDistance, the host restatement.
+  double expectedSubstitutionRate() const;
+  double mlDistance(const FastSeq& xGapped, const FastSeq& yGapped, int maxIterations = DefaultDistanceMatrixIterations) const;
+  vguard<vguard<double>> distanceMatrix(const vguard<FastSeq>& gappedSeq, int maxIterations = DefaultDistanceMatrixIterations) const;
 };
 
 struct ProbModel : AlphabetOwner {
@@ -605,9 +612,9 @@ string pairParentName(const string& lChildName, double lTime, const string& rChi
 // ---- src/recon.h / recon.cpp:864-915, 917-1052 (subset) ----------------------------------------
 // The progressive loop that calls the DP: one ForwardMatrix per internal node in post-order,
 // band-doubling retry on zero likelihood, sampled (or posterior) profiles for non-root nodes,
-// best alignment path at the root.  Tree building, guide-alignment construction, file formats,
-// refinement and counts are outside this build's scope: the tree arrives as post-order arrays
-// and the guide as an AlignPath over leaf rows.
+// best alignment path at the root.  Guide-alignment construction inside the driver, file formats and
+// refinement are outside this build's scope: the tree arrives as post-order arrays or is estimated
+// from the gapped guide rows (Reconstructor::buildTree), and the guide as an AlignPath over leaf rows.
 typedef int TreeNodeIndex;
 
 struct ReconTree {
@@ -622,6 +629,13 @@ struct ReconTree {
   TreeNodeIndex root() const { return nodes() - 1; }
   TreeNodeIndex getChild(TreeNodeIndex n, size_t k) const { return child[n][k]; }
   double branchLength(TreeNodeIndex n) const { return branchLen[n]; }
+  // src/tree.cpp:240-462 (hx_host_tree.cpp).  Both leave the nodes numbered, and the branch lengths rounded, as the
+  // reference's parse(toString()) at the end of its builders does, so post-order and the generator's order of use are its.
+  static double minBranchLength;         // TREE_MIN_BRANCH_LEN
+  void buildByNeighborJoining(const vguard<string>& leafNames, const vguard<vguard<double>>& distanceMatrix);
+  void buildByUPGMA(const vguard<string>& leafNames, const vguard<vguard<double>>& distanceMatrix);   // aborts unless ultrametric
+  bool isUltrametric(double epsilon = 1e-4) const;
+  string toString() const;               // Newick, branch lengths in the stream's default format
 };
 
 struct Reconstructor {
@@ -645,6 +659,8 @@ struct Reconstructor {
   double minEMImprovement;               // default .001
   IndelCounts priorCounts, dataCounts, dataPlusPriorCounts;
   vguard<LogProb> emLogLikelihood;       // fit: the log-likelihood (with the log-prior) of every EM iteration
+  bool useUPGMA = false;                 // -upgma: buildTree joins by UPGMA, else by neighbour joining
+  bool jukesCantorDistanceMatrix = false;   // -jc: distances are the Jukes-Cantor estimates, no likelihood search
 
   struct Dataset {
     ReconTree tree;
@@ -666,6 +682,7 @@ struct Reconstructor {
   vguard<int> devices;
 
   Reconstructor();
+  void buildTree(Dataset& family, const vguard<FastSeq>& gappedGuide);   // src/recon.cpp:732-743: family.tree from the guide rows
   void reconstruct(Dataset& family);
   void seedGenerator();
   void reconstructAll(vguard<Dataset*>& datasets);   // reference src/recon.cpp:1368-1372: every family

@@ -10,6 +10,10 @@
 //   fit <maxIter> [<minImprovement>] (optional: `historian fit -fixsubrates`, EM over the indel rates with Laplace pseudocounts;
 //                                     prints "em <iteration> <hex> <%.9g>" per iteration, then insRate delRate insExtProb delExtProb)
 //   tree <N>   followed by N lines:  <parent index or -1> <branch length> <name>   (post-order, root last)
+//   buildtree nj|upgma [jc]          (optional, instead of a tree block; needs guide: the tree is estimated from the guide's
+//                                     rows by neighbour joining or UPGMA over the maximum-likelihood distance matrix, or with
+//                                     jc over the Jukes-Cantor estimates - `historian recon -nj`, `-upgma`, `-jc`; an internal
+//                                     node is printed under the name node<index>)
 // Output: final Forward / trace log-likelihoods as hex floats, the band used per node, and the
 // gapped reconstruction (one row per tree node on the root path).
 #include <cstdio>
@@ -36,7 +40,8 @@ static void readJob(const char* file, Reconstructor& recon, bool setParams, Reco
   Require(in.good(), "Couldn't open %s", file);
   Reconstructor scratch;
   Reconstructor& r = setParams ? recon : scratch;
-  string key, seqFile, guideFile;
+  string key, seqFile, guideFile, buildTree;
+  bool buildTreeJC = false;
   while (in >> key) {
     if (key == "model") { string f; in >> f; if (setParams) r.model.readFile(f.c_str()); }
     else if (key == "seqs") in >> seqFile;
@@ -59,6 +64,13 @@ static void readJob(const char* file, Reconstructor& recon, bool setParams, Reco
       if (args >> minInc) r.minEMImprovement = minInc;
       r.accumulateIndelCounts = true; r.reconstructRoot = false; fitting = true;
     }
+    else if (key == "buildtree") {
+      string rest; std::getline(in, rest);
+      std::istringstream args(rest);
+      string jc;
+      Require((bool)(args >> buildTree) && (buildTree == "nj" || buildTree == "upgma"), "buildtree needs nj or upgma in %s", file);
+      if (args >> jc) { Require(jc == "jc", "Unknown buildtree option %s in %s", jc.c_str(), file); buildTreeJC = true; }
+    }
     else if (key == "tree") {
       int n; in >> n;
       for (int k = 0; k < n; ++k) {
@@ -68,6 +80,14 @@ static void readJob(const char* file, Reconstructor& recon, bool setParams, Reco
       }
       ds.tree.finish();
     } else Fail("Unknown key %s in %s", key.c_str(), file);
+  }
+  if (ds.tree.nodes() == 0 && !buildTree.empty()) {
+    Require(!guideFile.empty(), "buildtree needs a guide alignment in %s", file);
+    recon.useUPGMA = buildTree == "upgma";
+    recon.jukesCantorDistanceMatrix = buildTreeJC;
+    recon.buildTree(ds, readFastSeqs(guideFile.c_str()));
+    for (TreeNodeIndex n = 0; n < ds.tree.nodes(); ++n)
+      if (!ds.tree.isLeaf(n) && ds.tree.nodeName[n].empty()) ds.tree.nodeName[n] = "node" + std::to_string(n);
   }
   map<string, string> ungapped, gapped;
   for (const auto& fs : readFastSeqs(seqFile.c_str())) ungapped[fs.name] = fs.seq;

@@ -267,6 +267,37 @@ int walkTiming(int nArgs, char** args) {
   return 0;
 }
 
+// distances <alignfile> <modelfile> [max iterations [host pairs]]: RateModel::expectedSubstitutionRate and distanceMatrix over
+// the rows of a gapped alignment as hex floats ("rate <hex>", then "d <i> <j> <hex> <%.9g>" per pair).  With `host pairs` only
+// that many pairs, in the matrix's order, through mlDistance on the host, and "hostms <ms>": one core's time for them.
+int distances(int nArgs, char** args) {
+  const vguard<FastSeq> gapped = readFastSeqs(args[0]);
+  RateModel rates;
+  rates.readFile(args[1]);
+  const int maxIterations = nArgs > 2 ? atoi(args[2]) : DefaultDistanceMatrixIterations;
+  printf("rate %a\n", rates.expectedSubstitutionRate());
+  if (nArgs > 3) {
+    long left = atol(args[3]);
+    const double t0 = wallSeconds();
+    vguard<string> lines;
+    for (size_t i = 0; i + 1 < gapped.size() && left > 0; ++i)
+      for (size_t j = i + 1; j < gapped.size() && left > 0; ++j, --left) {
+        const double d = rates.mlDistance(gapped[i], gapped[j], maxIterations);
+        char text[96];
+        snprintf(text, sizeof text, "d %zu %zu %a %.9g", i, j, d, d);
+        lines.push_back(text);
+      }
+    const double ms = 1e3 * (wallSeconds() - t0);
+    for (const auto& l : lines) puts(l.c_str());
+    printf("hostms %.3f\n", ms);
+    return 0;
+  }
+  const auto dist = rates.distanceMatrix(gapped, maxIterations);
+  for (size_t i = 0; i + 1 < gapped.size(); ++i)
+    for (size_t j = i + 1; j < gapped.size(); ++j) printf("d %zu %zu %a %.9g\n", i, j, dist[i][j], dist[i][j]);
+  return 0;
+}
+
 const Command commands[] = {
     {"logsumexp", 0, 1, "[-slow|-fast]", lseGrid},
     {"seqprofile", 2, 2, "<alphabet> <sequence>", leafProfileJson},
@@ -276,6 +307,7 @@ const Command commands[] = {
     {"sibling", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", siblingPair},
     {"walks", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", pairWalks},
     {"walktime", 5, 6, "<seqfile> <modelfile> <left time> <right time> <matrices> [band]", walkTiming},
+    {"distances", 2, 4, "<alignfile> <modelfile> [max iterations [host pairs]]", distances},
 };
 
 }  // namespace

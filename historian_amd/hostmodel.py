@@ -74,6 +74,24 @@ class RateModel:
         return [expm(r * t) for r in self.sub_rate]
 
 
+def expected_sub_rate(model):
+    """RateModel::expectedSubstitutionRate (reference src/model.cpp:336-347): the substitution rate at equilibrium,
+    summed over the mixture components by weight - what hx_distance_model.expected_sub_rate takes."""
+    a = len(model.alphabet)
+    rate = 0.
+    for w, r in zip(model.cpt_weight, model.sub_rate):
+        m = np.vstack([r.T, np.ones((1, a))])
+        rhs = np.zeros(a + 1)
+        rhs[a] = 1
+        pi = np.maximum(np.linalg.lstsq(m, rhs, rcond=None)[0], 0.)
+        pi = pi / pi.sum()
+        for i in range(a):
+            for j in range(a):
+                if i != j:
+                    rate += float(w) * float(pi[i]) * float(r[i, j])
+    return rate
+
+
 def branch_params(model, t):
     """ProbModel(model, t) scalars (reference src/model.cpp:374-391)."""
     return dict(ins=1 - math.exp(-model.ins_rate * t), dele=1 - math.exp(-model.del_rate * t),

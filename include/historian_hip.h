@@ -23,7 +23,8 @@
  *   - Asynchronous on the caller's stream (they return once the work is queued): hx_batch_forward, hx_batch_backward on a
  *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
  *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
- *     matrices), then queues; hx_sumprod_columns runs its kernels on `stream` and returns when they are done.
+ *     matrices), then queues; hx_sumprod_columns, hx_distance_matrix and hx_distance_neg_log_like run their kernels on `stream` and return when they
+ *     are done.
  *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
  *     Forward launch (an event), with no host synchronisation.
  *   - Readers (results, matrices, cells, tracebacks, walks, counts) synchronise with the batch's LAST stream only - the stream
@@ -398,6 +399,37 @@ int hx_sumprod_columns(const hx_sumprod_model* model, const int8_t* tokens, cons
                        void* stream);
 /* Duration of the most recent hx_sumprod_columns kernel on this thread (HIP events on its stream). */
 int hx_sumprod_last_kernel_ms(float* ms);
+
+/* -- tree estimation: maximum-likelihood pairwise distances (reference src/model.cpp:506-655) ------
+ * RateModel::distanceMatrix for the rows of a gapped alignment: per pair of rows the counts of aligned residue
+ * pairs, DistanceMatrixParams::tJC as the starting point and tML's search (the bracket test, the four-step scan,
+ * GSL's golden-section iteration restated) over f(t) = -sum_ab n_ab log(sum_c w_c exp(R_c t)[a][b]).  One wavefront
+ * runs a pair's whole search.  exp(R t) is gsl_linalg_exponential_ss restated, with the operation order of the host
+ * mirror's RateModel::getSubProbMatrix, so its bits are the host's; the terms of f are added in (a, b) order.  What
+ * can differ from a host run is the device's log() inside f (tJC's one log is taken on the host between the two
+ * kernels for that reason).  Neighbour joining and UPGMA over the matrix stay on the host. */
+typedef struct hx_distance_model {
+  int32_t alph_size;            /* A <= 32                                                              */
+  int32_t n_components;         /* C >= 1                                                               */
+  const double* sub_rate;       /* [C][A][A] RateModel::subRate                                         */
+  const double* cpt_weight;     /* [C] RateModel::cptWeight                                             */
+  double expected_sub_rate;     /* RateModel::expectedSubstitutionRate(), computed by the caller        */
+} hx_distance_model;
+
+/* tokens: [n_seqs][n_cols], the residue's token or a negative value where the character is not counted (gap, wildcard,
+ * unknown).  dist: [n_seqs][n_seqs], symmetric with a zero diagonal.  evaluations: [n_seqs (n_seqs - 1) / 2] likelihood
+ * evaluations of each pair in the order (0,1), (0,2) ... or NULL.  max_iterations <= 0: the clamped tJC, nothing
+ * evaluated.  The work runs on `stream`; the call returns when it is done.  HX_ERR_RANGE: A outside 1 .. 32, C < 1, a
+ * token >= A; HX_ERR_INVALID_ARG: a null pointer, n_seqs < 2, n_cols < 0 - nothing is launched then. */
+int hx_distance_matrix(const hx_distance_model* model, const int8_t* tokens, int32_t n_seqs, int64_t n_cols,
+                       int32_t max_iterations, double* dist, int32_t* evaluations, void* stream);
+/* f(t[k]) for n count matrices [n][A][A] (counts >= 0): the likelihood evaluation of the search on its own. */
+int hx_distance_neg_log_like(const hx_distance_model* model, const int32_t* counts, const double* t, int32_t n,
+                             double* f, void* stream);
+/* Duration of the kernels of the most recent hx_distance_* call on this thread (HIP events on its stream). */
+int hx_distance_last_kernel_ms(float* ms);
+/* A x A matrix products taken by the searches of the most recent hx_distance_matrix on this thread (2 A^3 flops each). */
+int hx_distance_last_products(int64_t* products);
 
 /* Page-locked host memory for the destination of hx_batch_read_matrix: a device-to-host copy into
  * pageable memory runs at a fraction of the link rate (measured 4.7 GB/s for a 55 MB matrix).
