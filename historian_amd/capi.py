@@ -103,7 +103,7 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_quick_batch_create_on", "hx_batch_strip_windows", "hx_batch_total_cells", "hx_batch_job_kernel", "hx_batch_last_kernel_ms", "hx_host_alloc",
            "hx_host_free", "hx_quick_batch_create", "hx_quick_batch_destroy", "hx_quick_batch_run",
            "hx_quick_batch_results", "hx_quick_batch_layout", "hx_quick_batch_read_matrix",
-           "hx_quick_batch_total_cells", "hx_quick_batch_last_kernel_ms", "hx_sumprod_columns", "hx_sumprod_last_kernel_ms",
+           "hx_quick_batch_total_cells", "hx_quick_batch_last_kernel_ms", "hx_sumprod_columns", "hx_sumprod_last_kernel_ms", "hx_sumprod_ancestors",
            "hx_batch_read_matrix_async", "hx_batch_wait_read", "hx_batch_indel_counts", "hx_batch_event_counts", "hx_batch_shared_wavefront_pairs", "hx_batch_relaunches",
            "hx_branch_batch_create", "hx_branch_batch_destroy", "hx_branch_batch_run", "hx_branch_batch_results",
            "hx_branch_batch_read_matrix", "hx_branch_batch_total_cells", "hx_branch_batch_last_kernel_ms",
@@ -199,6 +199,7 @@ def load():
     lib.hx_sumprod_columns.argtypes = [C.POINTER(HxSumprodModel), C.POINTER(C.c_int8), _f64p, C.c_int64, _f64p, _f64p, _f64p, _f64p,
                                        _f64p, vp]
     lib.hx_sumprod_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
+    lib.hx_sumprod_ancestors.argtypes = [C.POINTER(HxSumprodModel), C.POINTER(C.c_int8), C.c_int64, _f64p, C.POINTER(C.c_int8), _f64p, vp]
     lib.hx_distance_matrix.argtypes = [C.POINTER(HxDistanceModel), C.POINTER(C.c_int8), C.c_int32, C.c_int64, C.c_int32, _f64p, _i32p, vp]
     lib.hx_distance_neg_log_like.argtypes = [C.POINTER(HxDistanceModel), _i32p, _f64p, C.c_int32, _f64p, vp]
     lib.hx_distance_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
@@ -832,6 +833,35 @@ def sumprod_columns(parent, ins_prob, log_cpt_weight, branch_sub, evec, evec_inv
                                      n_cols, _p(cll, _f64p), _p(root, _f64p), _p(ere, _f64p), _p(eim, _f64p),
                                      _p(post, _f64p) if post is not None else C.cast(None, _f64p), C.c_void_p(stream or 0)))
     return cll, root, ere + 1j * eim, post
+
+
+def sumprod_ancestors(parent, ins_prob, log_cpt_weight, branch_sub, tokens, want_post=False, stream=None):
+    """hx_sumprod_ancestors: parent [N]; ins_prob [C][A]; log_cpt_weight [C]; branch_sub [C][N][A][A]; tokens [n_cols][N] int8
+    (-1 wildcard, -2 gap); stream: the stream the kernels run on (the call returns when they are done).  The model's
+    eigen-basis pointers stay NULL: ancestor prediction does not read them.
+    Returns col_log_like [n_cols], best [n_cols][N] int8, node_post [n_cols][N][A] log posteriors or None."""
+    ins_prob = np.ascontiguousarray(ins_prob, dtype=np.float64)
+    c, a = ins_prob.shape
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    n = parent.size
+    tokens = np.ascontiguousarray(tokens, dtype=np.int8)
+    if tokens.ndim != 2 or tokens.shape[1] != n:
+        raise ValueError("tokens must be [n_cols][n_nodes]")
+    n_cols = tokens.shape[0]
+    log_cpt_weight = np.ascontiguousarray(log_cpt_weight, dtype=np.float64)
+    branch_sub = np.ascontiguousarray(branch_sub, dtype=np.float64)
+    if log_cpt_weight.shape != (c,) or branch_sub.shape != (c, n, a, a):
+        raise ValueError("log_cpt_weight must be [C] and branch_sub [C][N][A][A]")
+    m = HxSumprodModel()
+    m.alph_size, m.components, m.n_nodes = a, c, n
+    m.parent, m.ins_prob = _p(parent, _i32p), _p(ins_prob, _f64p)
+    m.log_cpt_weight, m.branch_sub = _p(log_cpt_weight, _f64p), _p(branch_sub, _f64p)
+    cll = np.empty(n_cols)
+    best = np.empty((n_cols, n), dtype=np.int8)
+    post = np.empty((n_cols, n, a)) if want_post else None
+    _check(load().hx_sumprod_ancestors(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), n_cols, _p(cll, _f64p), _p(best, C.POINTER(C.c_int8)),
+                                       _p(post, _f64p) if post is not None else C.cast(None, _f64p), C.c_void_p(stream or 0)))
+    return cll, best, post
 
 
 def sumprod_kernel_ms():

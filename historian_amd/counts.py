@@ -111,6 +111,59 @@ class ColumnCounter:
         return dict(col_log_like=cll, root_counts=root, eigen_counts=eig, counts=self.eigen.sub_counts(eig), root_post=post)
 
 
+# ---- `historian reconstruct -ancseq / -ancprob`: ancestral residues of a reconstruction (src/recon.cpp:1072-1085) ----
+
+class AncestorPredictor:
+    """Node posteriors of alignment columns on one tree (hx_sumprod_ancestors).  No eigen decomposition: exp(R t) of every
+    branch comes from model.sub_prob, as the reference's SumProduct takes it from ProbModel (src/sumprod.cpp:37-43),
+    unless branch_sub ([N] lists of [C] matrices) is passed."""
+
+    def __init__(self, model, parent, branch_length, branch_sub=None):
+        self.model, self.parent = model, np.asarray(parent, dtype=np.int32)
+        c, a, n = model.components(), len(model.alphabet), len(parent)
+        self.ins_prob = np.asarray(model.root, dtype=float).reshape(c, a)
+        self.log_cpt_weight = np.log(np.asarray(model.cpt_weight, dtype=float))
+        self.branch_sub = np.zeros((c, n, a, a))
+        for r in range(n):
+            if parent[r] < 0:
+                continue
+            sub = branch_sub[r] if branch_sub is not None else model.sub_prob(branch_length[r])
+            for cpt in range(c):
+                self.branch_sub[cpt, r] = sub[cpt]
+
+    def run(self, tokens, want_post=False):
+        """-> dict(col_log_like [n_cols], best [n_cols][N] int8, node_post [n_cols][N][A] log posteriors or None)"""
+        cll, best, post = capi.sumprod_ancestors(self.parent, self.ins_prob, self.log_cpt_weight, self.branch_sub, tokens, want_post)
+        return dict(col_log_like=cll, best=best, node_post=post)
+
+
+def predict_ancestors(model, parent, branch_length, rows, min_prob=None, max_prob=1., branch_sub=None):
+    """AlignColSumProduct::appendAncestralReconstructedColumn / appendAncestralPostProbColumn over a reconstruction.
+    rows: gapped strings, one per tree node.  -> (rows_out, pp): rows_out has every '*' (Alignment::isWildcard: that
+    character only - a leaf's 'x' stays) replaced by the most probable residue; pp is the reference's ReconPostProbMap
+    {row: {col: {char: prob}}} of the '*' cells' residues with log(min_prob) <= lp <= log(max_prob), or None when
+    min_prob is None (the reference's -ancprob default is .01).  branch_sub: as AncestorPredictor's."""
+    tok = tokenize_columns(model.alphabet, rows)
+    res = AncestorPredictor(model, parent, branch_length, branch_sub).run(tok, want_post=min_prob is not None)
+    best = res["best"]
+    rows_out = []
+    for r, row in enumerate(rows):
+        rows_out.append("".join(model.alphabet[best[col, r]] if ch == "*" else ch for col, ch in enumerate(row)))
+    if min_prob is None:
+        return rows_out, None
+    lp_min = math.log(min_prob) if min_prob > 0 else -math.inf
+    lp_max = math.log(max_prob)
+    pp = {}
+    for r, row in enumerate(rows):
+        for col, ch in enumerate(row):
+            if ch != "*":
+                continue
+            for k, lp in enumerate(res["node_post"][col, r]):
+                if lp_min <= lp <= lp_max:
+                    pp.setdefault(r, {}).setdefault(col, {})[model.alphabet[k]] = math.exp(lp)
+    return rows_out, pp
+
+
 # ---- `historian count -recon`: event counts of a fixed reconstruction (src/recon.cpp:1284-1291) ----
 
 def decay_wait_time(rate, t):

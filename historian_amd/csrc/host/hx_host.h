@@ -661,6 +661,11 @@ struct Reconstructor {
   vguard<LogProb> emLogLikelihood;       // fit: the log-likelihood (with the log-prior) of every EM iteration
   bool useUPGMA = false;                 // -upgma: buildTree joins by UPGMA, else by neighbour joining
   bool jukesCantorDistanceMatrix = false;   // -jc: distances are the Jukes-Cantor estimates, no likelihood search
+  bool predictAncestralSequence = false;          // -ancseq: predictAncestors fills Dataset::gappedAncestralRecon
+  bool reportAncestralSequenceProbability = false;   // -ancprob: ... and Dataset::gappedAncestralReconPostProb
+  double ancestralSequenceMinProb = .01;          // appendAncestralPostProbColumn's minProb (src/sumprod.h:98)
+  // AlignColSumProduct::ReconPostProbMap (src/sumprod.h:87): row -> column -> residue -> posterior probability
+  typedef map<AlignRowIndex, map<AlignColIndex, map<char, double>>> ReconPostProbMap;
 
   struct Dataset {
     ReconTree tree;
@@ -672,6 +677,8 @@ struct Reconstructor {
     IndelCounts indelCounts;             // accumulateIndelCounts: the root's expected indel events, lp = lpFinalFwd
     void prepareRecon();
     vguard<FastSeq> gappedRecon() const; // Alignment(ungapped, path).gapped()
+    vguard<FastSeq> gappedAncestralRecon;            // predictAncestors: gappedRecon() with every wildcard predicted
+    ReconPostProbMap gappedAncestralReconPostProb;   // ... and the posteriors behind it, -ancprob
   };
 
   // Not in the reference (which is one process, one core): the devices independent pair DPs are farmed over.
@@ -688,6 +695,9 @@ struct Reconstructor {
   void reconstructAll(vguard<Dataset*>& datasets);   // reference src/recon.cpp:1368-1372: every family
   void countAll(vguard<Dataset*>& datasets);         // src/recon.cpp:1373-1383: reconstruct every family, sum dataCounts
   void fit(vguard<Dataset*>& datasets);              // src/recon.cpp:1385-1410: EM over the indel rates of `model`
+  // src/recon.cpp:1072-1090 (hx_host_ancestors.cpp): every column of the reconstruction through hx_sumprod_ancestors
+  void predictAncestors(Dataset& dataset);
+  void predictAllAncestors(vguard<Dataset*>& datasets);
   static double familyCost(const Dataset& dataset);   // estimated lattice cells of a family's pair DPs
 };
 

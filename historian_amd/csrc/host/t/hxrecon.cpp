@@ -9,6 +9,10 @@
 //                                     then the same summed over families as "indelCountsTotal <key> ...")
 //   fit <maxIter> [<minImprovement>] (optional: `historian fit -fixsubrates`, EM over the indel rates with Laplace pseudocounts;
 //                                     prints "em <iteration> <hex> <%.9g>" per iteration, then insRate delRate insExtProb delExtProb)
+//   ancseq | ancprob [<minProb>]     (optional: `historian recon -ancseq`, `-ancprob` - after a family's rows, "anc <node> <name>
+//                                     <row>" for every row, its wildcards replaced by the most probable residue; with
+//                                     ancprob, which implies ancseq, also "pp <node> <column, 1-based> <char> <hex> <%.6f>" for
+//                                     every residue of a wildcard cell with a posterior of minProb, default .01, or more)
 //   tree <N>   followed by N lines:  <parent index or -1> <branch length> <name>   (post-order, root last)
 //   buildtree nj|upgma [jc]          (optional, instead of a tree block; needs guide: the tree is estimated from the guide's
 //                                     rows by neighbour joining or UPGMA over the maximum-likelihood distance matrix, or with
@@ -63,6 +67,14 @@ static void readJob(const char* file, Reconstructor& recon, bool setParams, Reco
       double minInc;
       if (args >> minInc) r.minEMImprovement = minInc;
       r.accumulateIndelCounts = true; r.reconstructRoot = false; fitting = true;
+    }
+    else if (key == "ancseq") r.predictAncestralSequence = true;
+    else if (key == "ancprob") {
+      string rest; std::getline(in, rest);
+      std::istringstream args(rest);
+      double minProb;
+      if (args >> minProb) r.ancestralSequenceMinProb = minProb;
+      r.predictAncestralSequence = r.reportAncestralSequenceProbability = true;
     }
     else if (key == "buildtree") {
       string rest; std::getline(in, rest);
@@ -125,6 +137,13 @@ static void printFamily(const Reconstructor::Dataset& ds) {
     std::cout << "\n";
   }
   std::cout.flush();
+  for (size_t r = 0; r < ds.gappedAncestralRecon.size(); ++r)
+    std::cout << "anc " << r << " " << ds.tree.nodeName[r] << " " << ds.gappedAncestralRecon[r].seq << "\n";
+  std::cout.flush();
+  for (const auto& row : ds.gappedAncestralReconPostProb)
+    for (const auto& col : row.second)
+      for (const auto& cp : col.second) printf("pp %zu %zu %c %a %.6f\n", row.first, col.first + 1, cp.first, cp.second, cp.second);
+  fflush(stdout);
 }
 
 // hxrecon [-devices d0,d1,...] <jobfile> [<jobfile> ...]
@@ -167,6 +186,7 @@ int main(int argc, char** argv) {
   if (recon.accumulateIndelCounts) recon.countAll(all);
   else if (all.size() == 1) recon.reconstruct(*all[0]);
   else recon.reconstructAll(all);
+  recon.predictAllAncestors(all);
   if (getenv("HX_TIMING")) {
     const double total = wallSeconds() - t0;
     const FillTiming& f = fillTiming;

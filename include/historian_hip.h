@@ -23,7 +23,7 @@
  *   - Asynchronous on the caller's stream (they return once the work is queued): hx_batch_forward, hx_batch_backward on a
  *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
  *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
- *     matrices), then queues; hx_sumprod_columns, hx_distance_matrix and hx_distance_neg_log_like run their kernels on `stream` and return when they
+ *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix and hx_distance_neg_log_like run their kernels on `stream` and return when they
  *     are done.
  *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
  *     Forward launch (an event), with no host synchronisation.
@@ -397,7 +397,22 @@ typedef struct hx_sumprod_model {
 int hx_sumprod_columns(const hx_sumprod_model* model, const int8_t* tokens, const double* weight, int64_t n_cols,
                        double* col_log_like, double* root_counts, double* eigen_re, double* eigen_im, double* root_post,
                        void* stream);
-/* Duration of the most recent hx_sumprod_columns kernel on this thread (HIP events on its stream). */
+/* -- ancestral sequences (-ancseq, -ancprob): the residue posterior of every node of every column --
+ * SumProduct::initColumn / fillUp / fillDown for every column, then logNodePostProb of every node and
+ * maxPostState of every wildcard node (src/sumprod.cpp:58-217, 259-262) - what
+ * AlignColSumProduct::appendAncestralReconstructedColumn and appendAncestralPostProbColumn read
+ * (src/sumprod.cpp:401-426).  No eigen basis: model->evec_*, evec_inv_*, esc_* are not read and may be NULL.
+ * tokens as hx_sumprod_columns.  Outputs, host memory:
+ * best      [n_cols][N] int8: gap -2; a residue node its token; a wildcard node (-1 in `tokens`, leaf or
+ *           internal) the first maximum of its posterior, as std::max_element gives it.
+ * node_post [n_cols][N][A] log posteriors (min(lp, 0) as the reference clamps), or NULL.  Fully defined:
+ *           a gap row is -inf, a residue row is 0 at its token and -inf elsewhere.
+ * col_log_like [n_cols] or NULL.  Same stream contract and error codes as hx_sumprod_columns; no atomics:
+ * two calls on the same input give the same bits, however HX_SUMPROD_SCRATCH_MB chunks the columns. */
+int hx_sumprod_ancestors(const hx_sumprod_model* model, const int8_t* tokens, int64_t n_cols,
+                         double* col_log_like, int8_t* best, double* node_post, void* stream);
+/* Duration of the kernels of the most recent hx_sumprod_columns or hx_sumprod_ancestors call on this thread
+ * (HIP events on its stream). */
 int hx_sumprod_last_kernel_ms(float* ms);
 
 /* -- tree estimation: maximum-likelihood pairwise distances (reference src/model.cpp:506-655) ------
