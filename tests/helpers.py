@@ -181,3 +181,100 @@ def leaf_case(seed, lx, ly, alphabet="ACGT", components=1, jc=True, tl=.1, tr=.1
     if band is not None:
         env = ho.GuideAlignmentEnvelope(left_justified_guide({1: sx, 2: sy}), 1, 2, band)
     return ho.ForwardMatrix(leaf(model, sx, 1, "x"), leaf(model, sy, 2, "y"), hmm, 0, env, fill=False)
+
+
+# ---------------------------------------------------------------------------
+# pairs and profile pairs whose guide alignment is the TRUE alignment of a simulated history: long gap runs,
+# leading / trailing gaps, blocks with no match at all (the envelope geometry a left-justified guide never has)
+# ---------------------------------------------------------------------------
+def evolve(rng, anc, alphabet, events, sub=.15):
+    """Walk `anc`: `events` maps a position to n; +n puts an n-residue insertion before that residue (position len(anc): after
+    the last one), -n deletes n residues starting at it (the position after the run takes its own event: a deletion directly
+    followed by an insertion is a block with no match at all); every other residue is substituted with probability `sub`.
+    -> the true alignment, one (ancestral residue index or None, descendant residue or None) per column."""
+    cols, i = [], 0
+    while i <= len(anc):
+        n = events.get(i, 0)
+        cols += [(None, rng.choice(alphabet)) for _ in range(n)]
+        if i == len(anc):
+            break
+        if n < 0:
+            gone = min(-n, len(anc) - i)
+            cols += [(k, None) for k in range(i, i + gone)]
+            i += gone
+            continue
+        cols.append((i, rng.choice(alphabet) if rng.random() < sub else anc[i]))
+        i += 1
+    return cols
+
+
+def guided_leaf_case(seed, lx, events, band, alphabet="ACGT", components=1, jc=True, tl=.1, tr=.1):
+    """A leaf pair banded round its true alignment: x random, y = evolve(x, events); the guide is that alignment's two rows.
+    Returns the oracle ForwardMatrix (unfilled), with the guide as .guide"""
+    rng = random.Random(seed)
+    model = jc_model(alphabet) if jc else random_reversible_model(rng, alphabet, components)
+    sx = random_seq(rng, alphabet, lx)
+    cols = evolve(rng, sx, alphabet, events)
+    sy = "".join(c for _, c in cols if c is not None)
+    guide = {1: [a is not None for a, _ in cols], 2: [c is not None for _, c in cols]}
+    env = ho.GuideAlignmentEnvelope(guide, 1, 2, band)
+    f = ho.ForwardMatrix(leaf(model, sx, 1, "x"), leaf(model, sy, 2, "y"), make_hmm(model, tl, tr), 0, env, fill=False)
+    f.guide, f.seqs = guide, {1: sx, 2: sy}
+    return f
+
+
+def guided_dag_case(seed, n, events_per_leaf, band, samples, keep_all=False):
+    """Forward DP of two internal profiles over four leaves that evolved from one ancestor, each by its own events; the guide
+    is their true multiple alignment (the ancestor's columns in order, each leaf's insertions in columns of their own).
+    samples = 0: the profiles are the best paths alone, chains of states (with their null states when keep_all)."""
+    rng = random.Random(seed)
+    alphabet = "ACGT"
+    model = jc_model(alphabet) if seed % 2 == 0 else random_reversible_model(rng, alphabet, 1)
+    anc = random_seq(rng, alphabet, n)
+    hist = [evolve(rng, anc, alphabet, ev, .15) for ev in events_per_leaf]
+    assert len(hist) == 4
+    s = ["".join(c for _, c in h if c is not None) for h in hist]
+    # columns: before ancestral residue i (and after the last), leaf 0's insertions, then leaf 1's, ...; then residue i
+    guide = {r: [] for r in range(4)}
+    ptr = [0] * 4
+    for i in range(n + 1):
+        for r in range(4):
+            while ptr[r] < len(hist[r]) and hist[r][ptr[r]][0] is None:
+                for q in range(4):
+                    guide[q].append(q == r)
+                ptr[r] += 1
+        if i == n:
+            break
+        for r in range(4):
+            a, c = hist[r][ptr[r]]
+            assert a == i
+            guide[r].append(c is not None)
+            ptr[r] += 1
+    p1 = internal_profile(model, s[0], s[1], (0, 1), 4, seed * 7 + 1, samples, keep_all=keep_all)
+    p2 = internal_profile(model, s[2], s[3], (2, 3), 5, seed * 7 + 2, samples, keep_all=keep_all)
+    f = ho.ForwardMatrix(p1, p2, make_hmm(model, .2, .05), 6, ho.GuideAlignmentEnvelope(guide, 0, 2, band), fill=False)
+    f.guide, f.seqs = guide, dict(enumerate(s))
+    return f
+
+
+def valid_guide(guide, seqs):
+    """the guide is an alignment of the sequences: equal row lengths, one True per residue, no all-gap column"""
+    cols = {len(r) for r in guide.values()}
+    return (len(cols) == 1 and all(sum(guide[r]) == len(seqs[r]) for r in guide)
+            and all(any(guide[r][c] for r in guide) for c in range(cols.pop())))
+
+
+def with_plateaus(x_env, y_env, spec):
+    """Envelope coordinates (non-decreasing match counts, [0] first) with long gap runs put in: spec = ("x", start, n) holds
+    the x coordinate for n positions from `start`, ("y", start, n) the y coordinate, ("xy", start, nx, ny) an x run of nx
+    directly followed, at the same coordinate, by a y run of ny (a block without a match).  The single steps already there stay."""
+    fx, fy = [list(np.diff(np.asarray(e, dtype=np.int64)) > 0) for e in (x_env, y_env)]
+    if spec[0] in ("x", "xy"):
+        fx[spec[1]:spec[1] + spec[2]] = [False] * len(fx[spec[1]:spec[1] + spec[2]])
+    if spec[0] == "y":
+        fy[spec[1]:spec[1] + spec[2]] = [False] * len(fy[spec[1]:spec[1] + spec[2]])
+    if spec[0] == "xy":
+        v = sum(fx[:spec[1]])
+        c = next(c for c in range(len(fy) + 1) if sum(fy[:c]) == v)
+        fy[c:c + spec[3]] = [False] * len(fy[c:c + spec[3]])
+    return [np.concatenate([[0], np.cumsum(f)]).astype(np.int32) for f in (fx, fy)]

@@ -23,7 +23,7 @@ def engine():
     capi.shutdown()
 
 
-def random_branch(seed, nx, ny, C=1, A=4, band=None, one_hot=False):
+def random_branch(seed, nx, ny, C=1, A=4, band=None, one_hot=False, plateau=None):
     rng = random.Random(seed)
 
     def pwm(n):
@@ -49,6 +49,8 @@ def random_branch(seed, nx, ny, C=1, A=4, band=None, one_hot=False):
         xe = np.concatenate([[0], np.cumsum([rng.random() < .9 for _ in range(nx)])]).astype(np.int32)
         ye = np.concatenate([[0], np.cumsum([rng.random() < .9 for _ in range(ny)])]).astype(np.int32)
         md = band
+        if plateau:       # a long gap run on top of the single steps (H.with_plateaus)
+            xe, ye = H.with_plateaus(xe, ye, plateau)
     return x, bo.pre_multiply(y, log_sub), bo.calc_ins_probs(y, log_ins, log_w), T, xe, ye, md
 
 
@@ -69,7 +71,9 @@ def dense(bm):
 
 CASES = [(11, 5, 7, 1, 4, None, False), (12, 70, 66, 1, 4, None, False), (13, 130, 90, 2, 4, None, False), (14, 64, 65, 1, 20, None, False),
          (15, 200, 180, 1, 4, 6, False), (16, 90, 140, 1, 4, 0, False), (17, 1, 1, 1, 4, None, False), (18, 0, 3, 1, 4, None, False),
-         (19, 150, 150, 1, 20, 10, True), (20, 63, 129, 1, 4, 3, True)]
+         (19, 150, 150, 1, 20, 10, True), (20, 63, 129, 1, 4, 3, True),
+         # envelope coordinates with long plateaus: 100 rows of x, 90 columns of y, 70 rows directly followed by 80 columns
+         (21, 200, 110, 1, 4, 4, False, ("x", 50, 100)), (22, 120, 200, 1, 4, 3, True, ("y", 70, 90)), (23, 190, 200, 1, 4, 5, False, ("xy", 60, 70, 80))]
 
 
 @pytest.mark.parametrize("viterbi", [True, False])
@@ -98,6 +102,7 @@ def test_strips_dealt_to_wavefronts_and_band_windows(monkeypatch, waves, windows
         monkeypatch.setenv("HX_BRANCH_NO_WINDOWS", "1")
     cases = [random_branch(51, 300, 330, 1, 4, 5, False), random_branch(52, 400, 290, 1, 4, 0, True), random_branch(53, 321, 321, 2, 4, 70, False),
              random_branch(54, 257, 300, 1, 4, None, False), random_branch(55, 129, 64, 1, 4, 2, True)]
+    cases += [random_branch(*c) for c in CASES[-3:]]          # the long plateaus
     b = capi.BranchBatch([as_job(c) for c in cases])
     for viterbi in (True, False):
         b.run(viterbi=viterbi)

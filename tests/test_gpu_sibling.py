@@ -42,12 +42,17 @@ CASES = [(11, 5, 7, 1, 4, None, False, True), (12, 70, 66, 1, 4, None, False, Tr
          (14, 64, 65, 1, 20, None, True, True), (15, 65, 200, 1, 4, 3, False, False), (16, 90, 140, 1, 4, 0, False, True),
          (17, 1, 1, 1, 4, None, False, True), (18, 0, 3, 1, 4, None, False, True), (19, 3, 0, 4, 20, 0, True, True),
          (20, 0, 0, 1, 4, None, False, True), (21, 150, 150, 1, 20, 20, True, False), (22, 63, 129, 4, 4, 3, True, True),
-         (23, 200, 130, 1, 4, 20, False, True)]
+         (23, 200, 130, 1, 4, 20, False, True),
+         # envelope coordinates with long plateaus (H.with_plateaus): 100 rows, 90 columns, 70 rows directly followed by 80 columns
+         (24, 200, 110, 1, 4, 4, False, True, ("x", 50, 100)), (25, 120, 200, 1, 4, 3, True, True, ("y", 70, 90)),
+         (26, 190, 200, 1, 4, 5, False, True, ("xy", 60, 70, 80))]
 
 
 def build(c, fill=True):
-    seed, nx, ny, C, A, band, one_hot, sorted_env = c
+    seed, nx, ny, C, A, band, one_hot, sorted_env = c[:8]
     case = sr.random_case(seed, nx, ny, C=C, A=A, band=band, one_hot=one_hot, sorted_env=sorted_env)
+    if len(c) > 8:
+        case["l_env"], case["r_env"] = [[int(v) for v in e] for e in H.with_plateaus(case["l_env"], case["r_env"], c[8])]
     return case, sr.SiblingMatrix(fill=fill, **case)
 
 
@@ -94,7 +99,7 @@ def test_outside_the_envelope_is_minus_infinity_and_runs_repeat(mixed):
 @pytest.mark.parametrize("waves", [1, 3, 16])
 def test_strips_dealt_to_any_number_of_wavefronts(monkeypatch, waves):
     monkeypatch.setenv("HX_SIBLING_WAVES", str(waves))
-    built = [build(c) for c in [(31, 300, 130, 1, 4, 5, False, False), (32, 257, 90, 1, 4, None, True, True), (33, 129, 64, 4, 4, 0, True, True)]]
+    built = [build(c) for c in [(31, 300, 130, 1, 4, 5, False, False), (32, 257, 90, 1, 4, None, True, True), (33, 129, 64, 4, 4, 0, True, True)] + CASES[-3:]]
     b = capi.SiblingBatch([as_job(case, m) for case, m in built])
     b.run()
     lp = b.lp_end()
