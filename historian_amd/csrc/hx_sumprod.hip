@@ -697,12 +697,15 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
     const bool lm = ll_lds + mat_lds <= 96 * 1024;
     const size_t col_lds = ll_lds + (lm ? mat_lds : 0);
 #define HX_SP_GO(TA_, LM_) hipLaunchKernelGGL((k_sumprod_columns<TA_, LM_>), dim3((unsigned)blocks), dim3(tpb), col_lds, st, m, d_tok, d_w, nc, s, lse_tab, d_cll + first, d_p)
-    if (A == 4) { if (lm) HX_SP_GO(4, true); else HX_SP_GO(4, false); }
+    // (A = 4 has its matrices in LDS whatever C <= 128: 512 C + 24 * 16 * min(C, 8) <= 65536 + 3072 < 98304 - no <4, false> form)
+    if (A == 4) HX_SP_GO(4, true);
     else if (A == 20) { if (lm) HX_SP_GO(20, true); else HX_SP_GO(20, false); }
     else { if (lm) HX_SP_GO(0, true); else HX_SP_GO(0, false); }
 #undef HX_SP_GO
     const long long tiles = (nc + HX_SP_TILE - 1) / HX_SP_TILE;
     long long slices = 4096 / ((long long)C * N) + 1;
+    if (const char* e = getenv("HX_SUMPROD_SLICES")) slices = atoll(e);
+    if (slices < 1) slices = 1;
     if (slices > tiles) slices = tiles;
     if (real_basis && sizeof(double) * 2 * (((A + 15) / 16) * 16) * 65 <= 64 * 1024 && !getenv("HX_SUMPROD_NO_MFMA")) {
       const int mp = ((A + 15) / 16) * 16;
