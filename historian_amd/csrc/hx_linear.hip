@@ -3,13 +3,30 @@
 // The reference (src/forward.cpp:68-223, 975-1088) works on log-probabilities and combines them with a table-driven
 // log-sum-exp: 18 table look-ups per cell for a pair of leaf profiles.  The same recursion on the probabilities
 // themselves is 18 multiply-adds.  This kernel keeps every cell as five fp64 mantissas plus ONE integer
-// exponent per cell (p_state = m_state * 2^e), so nothing under- or overflows however long the sequences are,
+// exponent per cell (p_state = m_state * 2^e), so the length of the sequences never makes a cell under- or overflow,
 // runs the recursion with fused multiply-adds, and converts each finished cell to the reference's storage format
 // - five log-probabilities, 40 B/cell, same strip-skewed layout - with an fp64 table-plus-polynomial logarithm
 // (512 intervals, |error| < 2.3e-13) just before the store.  Nothing is approximated beyond fp64 rounding, so the
 // results do NOT carry the reference's truncation of log-sum-exp terms below e^-10: they differ from the reference's by
 // the reference's own approximation error (lpEnd ~3e-6 relative, north_star allows 1e-4), which is
 // why the policy is an explicit opt-in; the bit-exact policy is ExactLse3 in hx_chain.hip.
+//
+// The dynamic range of a cell.  The one exponent follows the cell's LARGEST state, so what is bounded is the distance between
+// the states of one cell: a state that lies d nats below the largest state of its cell is the number m_max * e^-d, and fp64's
+// normal range ends at 2^-1022 = e^-708.  The contract (include/historian_hip.h, tested by tests/test_gpu_param_edges.py):
+//   * a state more than D nats below the largest state of its own cell may be stored as -inf or with reduced precision
+//     (a subnormal mantissa); it is never NaN;
+//   * every other value of the matrix is exact to fp64 rounding - the cells of later rows that such states feed included,
+//     since what was lost is below e^-D of what those cells hold;
+//   * lpEnd and lpStart are exact to fp64 rounding.
+// D = 1001 ln 2 - 7 ln(1 / phi) nats: 2^-1022, less the 2^20 by which a sum must exceed a term that trunc_sum dropped (its
+// low word, below 2^-1042, stays in the sum), less the factor 2 of a renormalised mantissa, less seven steps without a
+// renormalisation (HXL_RENORM_MASK) at the model's smallest per-step factor phi = transition x emission on the best move out
+// of a cell's largest state (derivation: tests/param_edge_cases.py).  Such spreads arise where two states of a cell are the same
+// gap run taken by two routes - IDM and IMI on row 0, IMD and IIW in column 0, and their mirror images in the Backward matrix -
+// and grow by about 2 x indel rate x branch length nats per residue: insertion and deletion rates of 0.1 on branches of
+// length 2 reach D = 662.7 at residue 1657; rates of 0.01-0.02 on branches of 0.1-0.3 need more than 10^4 residues.
+// HX_LSE_EXACT and HX_LSE_FAST work on logarithms and have no such limit.
 //
 // Pipeline structure is that of k_fill_chain (hx_chain.hip): one workgroup per pair, 64-row strips dealt to the
 // waves round-robin, lane <-> row, step <-> anti-diagonal, up/diag neighbours by DPP wave_shr:1, the whole y side in LDS,
@@ -43,7 +60,8 @@ struct L5 { double imm, imd, idm, imi, iiw; int e; };
 #define HXL_EXP_M10 4.5399929762484854e-05      // e^-10
 __device__ __forceinline__ double trunc_sum(double a, double b) {
   const double hi = fmax_plain(a, b), lo = fmin_plain(a, b);
-  // (a dropped term keeps its low word: a number below 2^-1042 that no sum of mantissas scaled to the cell's exponent feels - one select instead of two)
+  // (a dropped term keeps its low word: a number below 2^-1042, which a sum of at least 2^-1002 does not feel - states within
+  // D nats of their cell's largest, see the header - one select instead of two)
   const int keep = lo > hi * HXL_EXP_M10 ? __double2hiint(lo) : 0;
   return hi + __hiloint2double(keep, __double2loint(lo));
 }

@@ -83,7 +83,17 @@ enum { HX_IMM = 0, HX_IMD = 1, HX_IDM = 2, HX_IMI = 3, HX_IIW = 4, HX_STATES = 5
                             (hx_linear.hip).  Exact up to fp64 rounding, so it does NOT reproduce the
                             reference's truncation of terms below e^-10: lpEnd agrees with the reference to
                             ~3e-6 relative (north_star tolerance 1e-4), cells to ~1e-5 per alignment column.
-                            Batches that kernel does not cover run as HX_LSE_FAST.                          */
+                            Batches that kernel does not cover run as HX_LSE_FAST.
+                            Dynamic range (HX_LSE_LINEAR and HX_LSE_TRUNC): a cell is five mantissas under ONE exponent, that of
+                            its largest state.  A state more than D nats below the largest state of its own cell may be stored
+                            as -inf or with reduced precision (never NaN); every other value of the matrix,
+                            the cells that such states feed included, and lp_end / lp_start are exact to fp64 rounding.
+                            D = 1001 ln 2 - 7 ln(1/phi), phi = the model's smallest per-step factor (transition x emission on
+                            the best move out of a cell's largest state; hx_linear.hip): 628 nats for indel rates of
+                            0.01 on branches of 0.1, 662 for rates of 0.1 on branches of 2.  Only the states of one gap run
+                            taken by two routes spread like that (row 0, column 0, their mirror images in the Backward matrix),
+                            by ~2 x rate x branch length nats per residue: the second model reaches D at residue 1657.
+                            HX_LSE_EXACT and HX_LSE_FAST have no such limit.                                 */
 #define HX_LSE_TRUNC 81u  /* HX_LSE_LINEAR with the reference's truncation: the same scaled-probability fills, but every pairwise
                             sum of the reference's left-nested log_sum_exp (src/logsumexp.h:66-100) drops its smaller term when
                             that is at most e^-10 of the larger - what the reference's table does for differences >= 10
