@@ -86,6 +86,11 @@ class HxSumprodModel(C.Structure):
                 ("esc_re", _f64p), ("esc_im", _f64p)]
 
 
+class HxHistoryModel(C.Structure):
+    _fields_ = [("alph_size", C.c_int32), ("components", C.c_int32), ("n_nodes", C.c_int32), ("parent", _i32p),
+                ("ins_prob", _f64p), ("log_cpt_weight", _f64p)]
+
+
 class HxCell(C.Structure):
     _fields_ = [("xpos", C.c_int32), ("ypos", C.c_int32), ("state", C.c_int32), ("pad_", C.c_int32),
                 ("log_post_prob", C.c_double)]
@@ -112,7 +117,9 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_branch_batch_best_paths", "hx_branch_batch_sample_paths", "hx_branch_batch_max_steps", "hx_branch_batch_read_cells",
            "hx_sibling_batch_sample_paths", "hx_sibling_batch_max_steps", "hx_sibling_batch_read_cells",
            "hx_branch_batch_last_walk_ms", "hx_sibling_batch_last_walk_ms",
-           "hx_distance_matrix", "hx_distance_neg_log_like", "hx_distance_last_kernel_ms", "hx_distance_last_products"]
+           "hx_distance_matrix", "hx_distance_neg_log_like", "hx_distance_last_kernel_ms", "hx_distance_last_products",
+           "hx_history_create", "hx_history_destroy", "hx_history_propose", "hx_history_accept", "hx_history_reject",
+           "hx_history_log_like", "hx_history_indel_counts", "hx_history_last_kernel_ms"]
 
 
 class HxError(RuntimeError):
@@ -204,6 +211,14 @@ def load():
     lib.hx_distance_neg_log_like.argtypes = [C.POINTER(HxDistanceModel), _i32p, _f64p, C.c_int32, _f64p, vp]
     lib.hx_distance_last_kernel_ms.argtypes = [C.POINTER(C.c_float)]
     lib.hx_distance_last_products.argtypes = [C.POINTER(C.c_int64)]
+    lib.hx_history_create.argtypes = [C.POINTER(HxHistoryModel), C.POINTER(C.c_int8), C.c_int64, _f64p, vp, C.POINTER(vp)]
+    lib.hx_history_destroy.argtypes = [vp]
+    lib.hx_history_propose.argtypes = [vp, C.c_int32, _i32p, _f64p, _f64p, vp]
+    lib.hx_history_accept.argtypes = [vp]
+    lib.hx_history_reject.argtypes = [vp]
+    lib.hx_history_log_like.argtypes = [vp, C.c_int32, _f64p, _f64p]
+    lib.hx_history_indel_counts.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.hx_history_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.hx_batch_read_matrix_async.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
     lib.hx_batch_indel_counts.argtypes = [vp, C.c_int32, _f64p, _f64p]
@@ -862,6 +877,79 @@ def sumprod_ancestors(parent, ins_prob, log_cpt_weight, branch_sub, tokens, want
     _check(load().hx_sumprod_ancestors(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), n_cols, _p(cll, _f64p), _p(best, C.POINTER(C.c_int8)),
                                        _p(post, _f64p) if post is not None else C.cast(None, _f64p), C.c_void_p(stream or 0)))
     return cll, best, post
+
+
+class History:
+    """hx_history_*: a fixed alignment on a tree whose branch lengths change, resident on the device.  parent [N]; ins_prob
+    [C][A]; log_cpt_weight [C]; tokens [n_cols][N] int8 (-1 wildcard, -2 gap); branch_sub [C][N][A][A].  Creating it
+    evaluates every column (on `stream`; the call returns when that is done)."""
+
+    def __init__(self, parent, ins_prob, log_cpt_weight, tokens, branch_sub, stream=None):
+        self._h = None
+        ins_prob = np.ascontiguousarray(ins_prob, dtype=np.float64)
+        self.c, self.a = ins_prob.shape
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        self.n = parent.size
+        tokens = np.ascontiguousarray(tokens, dtype=np.int8)
+        if tokens.ndim != 2 or tokens.shape[1] != self.n:
+            raise ValueError("tokens must be [n_cols][n_nodes]")
+        self.n_cols = tokens.shape[0]
+        log_cpt_weight = np.ascontiguousarray(log_cpt_weight, dtype=np.float64)
+        branch_sub = np.ascontiguousarray(branch_sub, dtype=np.float64)
+        if log_cpt_weight.shape != (self.c,) or branch_sub.shape != (self.c, self.n, self.a, self.a):
+            raise ValueError("log_cpt_weight must be [C] and branch_sub [C][N][A][A]")
+        m = HxHistoryModel()
+        m.alph_size, m.components, m.n_nodes = self.a, self.c, self.n
+        m.parent, m.ins_prob, m.log_cpt_weight = _p(parent, _i32p), _p(ins_prob, _f64p), _p(log_cpt_weight, _f64p)
+        h = C.c_void_p()
+        _check(load().hx_history_create(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), self.n_cols, _p(branch_sub, _f64p),
+                                        C.c_void_p(stream or 0), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            load().hx_history_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def propose(self, nodes, branch_sub, stream=None):
+        """nodes [n_changed]; branch_sub [n_changed][C][A][A] -> the proposed sum of the column log-likelihoods"""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        branch_sub = np.ascontiguousarray(branch_sub, dtype=np.float64)
+        if nodes.ndim != 1 or branch_sub.shape != (nodes.size, self.c, self.a, self.a):
+            raise ValueError("branch_sub must be [n_changed][C][A][A]")
+        lp = C.c_double()
+        _check(load().hx_history_propose(self._h, nodes.size, _p(nodes, _i32p), _p(branch_sub, _f64p), C.byref(lp), C.c_void_p(stream or 0)))
+        return lp.value
+
+    def accept(self):
+        _check(load().hx_history_accept(self._h))
+
+    def reject(self):
+        _check(load().hx_history_reject(self._h))
+
+    def log_like(self, which=0, want_columns=True):
+        """-> lp_sub, col_log_like [n_cols] (or None) of the current state (0) or the pending proposal (1)"""
+        lp = C.c_double()
+        cll = np.empty(self.n_cols) if want_columns else None
+        _check(load().hx_history_log_like(self._h, which, C.byref(lp), _p(cll, _f64p) if cll is not None else C.cast(None, _f64p)))
+        return lp.value, cll
+
+    def indel_counts(self):
+        """[N][3][4] int64: n[src Start/Match, Insert, Delete][dest Match, Insert, Delete, End] of every node's branch"""
+        out = np.empty((self.n, 3, 4), dtype=np.int64)
+        _check(load().hx_history_indel_counts(self._h, _p(out, C.POINTER(C.c_int64))))
+        return out
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        _check(load().hx_history_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
 
 
 def sumprod_kernel_ms():

@@ -23,7 +23,9 @@
 // CountSubstEvents bit is accepted and ignored, and SumProduct* must be NULL.
 // Sampler: BranchMatrix and the eleven-state SiblingMatrix (hx_host_sibling.cpp: fill on the device through
 // hx_sibling_batch_*, single or as fillBatch; sample / logPostProb / parentSeq over the copy read back) are mirrored here; the
-// sampler's moves (proposeMove, Move::accept, getConditionalPWMs) are not built.
+// sampler's alignment moves and prune-and-regraft (getConditionalPWMs, sampleSeq) are not built; the tree-height moves
+// (NodeHeightMove, RescaleMove), Move::accept, Sampler::sample / run and TreeAlignFuncs::logLikelihood of a whole history are
+// (hx_host_sampler.cpp): the substitution term through the device-resident history hx_history_*, the rest on the host.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -43,6 +45,7 @@ struct hx_quick_batch;
 struct hx_quick_job;
 struct hx_branch_batch;
 struct hx_sibling_batch;
+struct hx_history;
 
 namespace historian {
 
@@ -636,6 +639,17 @@ struct ReconTree {
   void buildByUPGMA(const vguard<string>& leafNames, const vguard<vguard<double>>& distanceMatrix);   // aborts unless ultrametric
   bool isUltrametric(double epsilon = 1e-4) const;
   string toString() const;               // Newick, branch lengths in the stream's default format
+  // hx_host_sampler.cpp: Tree::distanceFromRoot (src/tree.cpp:692-704); a Newick reader (nodes in post-order, children
+  // left to right, the root last; an unnamed node is node<index>)
+  vguard<double> distanceFromRoot() const;
+  static ReconTree parse(const string& newick);
+};
+
+// ---- src/sampler.h:11-16, src/sampler.cpp:9-31: the coalescent prior of a tree-height chain ----------------------
+struct SimpleTreePrior {
+  double populationSize = 1;
+  double coalescenceRate(int lineages) const;
+  LogProb treeLogLikelihood(const ReconTree& tree) const;
 };
 
 struct Reconstructor {
@@ -897,6 +911,23 @@ struct TreeAlignFuncs {
                                       const vguard<LogProb>& logCptWeight);                     // src/sampler.cpp:465-476
   static PosWeightMatrix leafPWM(const FastSeq& seq, const string& alphabet, int components);   // a sequence as certain columns (0 / -inf)
 
+  // hx_host_sampler.cpp: the likelihood of a whole history, tree prior + root + indels + substitutions
+  // (src/sampler.cpp:150-189, 372-450).  The indel term is summed on the host in path order (the reference's bits); the
+  // substitution term is the device's (hx_history_create: every column's fillUp, summed in a fixed order).
+  struct History {
+    vguard<FastSeq> gapped;            // one row per tree node
+    ReconTree tree;
+  };
+  static AlignPath pairPath(const AlignPath& path, TreeNodeIndex node1, TreeNodeIndex node2);
+  static LogProb rootLogLikelihood(const RateModel& model, const History& history);
+  static LogProb indelLogLikelihood(const RateModel& model, const History& history);
+  static LogProb substLogLikelihood(const RateModel& model, const History& history);
+  static LogProb logLikelihood(const SimpleTreePrior& treePrior, const RateModel& model, const History& history, const char* suffix = "");
+  static LogProb logBranchPathLikelihood(const ProbModel& probModel, const AlignPath& path, TreeNodeIndex parent, TreeNodeIndex child);
+  static double rootExtProb(const RateModel& model) { return model.insExtProb; }
+  // not in the reference: the history as hx_history_create takes it (tokens [columns][nodes], exp(R t) of every branch)
+  static hx_history* residentHistory(const RateModel& model, const History& history);
+
   class BranchMatrixBase {
   public:
     struct CellCoords { SeqIdx xpos, ypos; unsigned int state; };
@@ -947,7 +978,69 @@ struct Refiner : TreeAlignFuncs {
 };
 
 struct Sampler : TreeAlignFuncs {
-  class BranchMatrix : public BranchMatrixBase {          // src/sampler.cpp:1034-1160 (the sampling moves are not built)
+  // ---- src/sampler.h:326-470, src/sampler.cpp:478-557, 927-1003, 1608-1746 (hx_host_sampler.cpp): the chain ----
+  // Moves with rate 0 here: BranchAlign, NodeAlign, PruneAndRegraft (not built).  A move's tree arithmetic and its draws
+  // from the generator are the reference's, std::mt19937 and the standard distributions where it uses them - including
+  // random_element's generator BY VALUE (src/util.h:165-173): drawing the node does not advance the caller's generator.
+  // The current history is resident on the device (hx_history_*): a move proposes its changed branches there, and
+  // sample() accepts or rejects the proposal.
+  typedef std::mt19937 random_engine;
+  struct Move {
+    enum Type { BranchAlign = 0, NodeAlign = 1, PruneAndRegraft = 2, NodeHeight = 3, Rescale = 4, TotalMoveTypes = 5 };
+    Type type = TotalMoveTypes;
+    TreeNodeIndex node = -1, parent = -1, leftChild = -1, rightChild = -1;
+    History oldHistory, newHistory;
+    LogProb oldLogLikelihood = 0, newLogLikelihood = 0, logForwardProposal = 0, logReverseProposal = 0, logJacobian = 0;
+    LogProb logAcceptProb = -std::numeric_limits<double>::infinity();
+    bool nullified = false;
+    string samplerName, comment;
+    vguard<TreeNodeIndex> changed;     // not in the reference: the nodes whose branch length differs in newHistory
+    Move() = default;
+    Move(Type type, const History& history, LogProb oldLogLikelihood, const string& samplerName);
+    void initNewHistory(const ReconTree& tree, const vguard<FastSeq>& gapped);
+    void initRatio(const Sampler& sampler);
+    void nullify(const char* reason);
+    bool accept(random_engine& generator) const;
+    static const char* typeName(Type t);
+    static size_t typeNameWidth() { return 20; }
+  };
+  struct NodeHeightMove : Move {
+    NodeHeightMove(const History& history, LogProb oldLogLikelihood, const Sampler& sampler, random_engine& generator);
+    // the move without its likelihood (host only): picks the node, changes `tree`; -> logJacobian
+    static LogProb propose(ReconTree& tree, random_engine& generator, TreeNodeIndex& node, vguard<TreeNodeIndex>& changed);
+  };
+  struct RescaleMove : Move {
+    RescaleMove(const History& history, LogProb oldLogLikelihood, const Sampler& sampler, random_engine& generator);
+    static LogProb propose(ReconTree& tree, random_engine& generator, vguard<TreeNodeIndex>& changed);
+  };
+  const RateModel* model = nullptr;
+  const SimpleTreePrior* treePrior = nullptr;
+  vguard<double> moveRate;
+  vguard<int> movesProposed, movesAccepted;
+  vguard<double> moveNanosecs;
+  string name;
+  History currentHistory, bestHistory;
+  LogProb currentLogLikelihood = 0, bestLogLikelihood = 0;
+  bool isUltrametric = false;
+  vguard<Move> moveLog;                // not in the reference: every move of sample(), in order (histories dropped)
+  bool keepMoveLog = false;
+  Sampler() = default;
+  Sampler(const RateModel& model, const SimpleTreePrior& treePrior);
+  static TreeNodeIndex randomInternalNode(const ReconTree& tree, random_engine& generator);
+  static size_t randomIndex(const vguard<double>& weights, random_engine& generator);      // random_index (src/util.h:188-201)
+  Move proposeMove(const History& oldHistory, LogProb oldLogLikelihood, random_engine& generator) const;
+  void initialize(const History& initialHistory, const string& samplerName);
+  void fixAlignment();
+  void sample(random_engine& generator);
+  static void run(vguard<Sampler>& samplers, random_engine& generator, unsigned int nSamples);
+  string moveStats() const;
+  LogProb logLikelihood(const History& history, const char* suffix = "") const;
+  // the four terms of the pending proposal on the resident history: tree, root, indels, substitutions
+  void proposedTerms(const Move& move, LogProb terms[4]) const;
+  LogProb currentTerms[4] = {0, 0, 0, 0};
+  std::shared_ptr<hx_history> resident;
+
+  class BranchMatrix : public BranchMatrixBase {          // src/sampler.cpp:1034-1160
   public:
     typedef std::mt19937 random_engine;
     AlignPath sample(random_engine& generator) const;     // src/sampler.cpp:1088-1120
@@ -965,7 +1058,7 @@ struct Sampler : TreeAlignFuncs {
   // hx_sibling_batch_sample_paths / read_cells, the matrices of a fillBatch share their batch (sampleBatch walks them in one
   // launch), and the dense copy is read on the first cell() call only.  HX_HOST_WALKS=1 keeps the host walks over the copy.
   // fillBatch fills several matrices in one device batch (a move fills two, a sweep of moves many).  The sampler's
-  // moves (proposeMove, Move::accept, getConditionalPWMs) are not built.  Parity of this lattice is pinned by enumeration
+  // alignment moves (getConditionalPWMs, sampleSeq) are not built.  Parity of this lattice is pinned by enumeration
   // (tests/test_oracle_sibling.py), not by a reference fixture: none holds a sibling matrix.
   class SiblingMatrix {
   public:

@@ -19,12 +19,17 @@
 //   hxtest walktime <pair.fa> <model.json> <tl> <tr> <n> [band]   timing (tools/walks_bench.py): fillBatch of n copies of the
 //                                                  pair's sibling matrix, then - timed apart - what a walk needs first (the dense
 //                                                  copies with HX_HOST_WALKS=1, nothing otherwise), sampleBatch and logPostProb
+//   hxtest treemoves <rows.fa> <tree.nh> <model.json> <steps> <seed>   a tree-height chain on a fixed alignment (node-height and
+//                                                  rescale moves, hx_host_sampler.cpp): the four likelihood parts of the initial
+//                                                  history, one line per step, the final tree
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include "../hx_host.h"
 using namespace historian;
 
@@ -298,6 +303,57 @@ int distances(int nArgs, char** args) {
   return 0;
 }
 
+// treemoves <rows.fa> <tree.nh> <model.json> <steps> <seed>: a tree-height chain on a fixed alignment (one gapped row per tree
+// node, named as the Newick string names it).  Prints "parts <tree> <root> <indels> <substitutions>" of the initial history as
+// hex floats; per step "step <k> <type> <node or -1> <logAcceptProb> <accepted> <logJacobian> <new log-likelihood>" and
+// "proposed <branch length of every node>" (hex floats); then "final <branch lengths>", "newick <tree>" and moveStats' counts
+// as "moves <type> <proposed> <accepted>".
+int treeMoves(int, char** args) {
+  vguard<FastSeq> rows = readFastSeqs(args[0]);
+  std::ifstream treeFile(args[1]);
+  Require(treeFile.good(), "Couldn't open %s", args[1]);
+  std::stringstream newick;
+  newick << treeFile.rdbuf();
+  RateModel rates;
+  rates.readFile(args[2]);
+  const unsigned steps = (unsigned)atoi(args[3]);
+  TreeAlignFuncs::History history;
+  history.tree = ReconTree::parse(newick.str());
+  for (TreeNodeIndex n = 0; n < history.tree.nodes(); ++n) {
+    const auto row = std::find_if(rows.begin(), rows.end(), [&](const FastSeq& fs) { return fs.name == history.tree.nodeName[n]; });
+    Require(row != rows.end(), "No row for tree node %s", history.tree.nodeName[n].c_str());
+    history.gapped.push_back(*row);
+  }
+  const SimpleTreePrior prior;
+  vguard<Sampler> samplers(1, Sampler(rates, prior));
+  Sampler& sampler = samplers[0];
+  sampler.keepMoveLog = true;
+  sampler.initialize(history, "treemoves");
+  sampler.fixAlignment();
+  printf("parts %a %a %a %a\n", sampler.currentTerms[0], sampler.currentTerms[1], sampler.currentTerms[2], sampler.currentTerms[3]);
+  printf("whole %a\n", TreeAlignFuncs::logLikelihood(prior, rates, history));
+  Sampler::random_engine generator((unsigned)atoi(args[4]));
+  Sampler::run(samplers, generator, steps);
+  for (size_t k = 0; k < sampler.moveLog.size(); ++k) {
+    const Sampler::Move& m = sampler.moveLog[k];
+    string type = Sampler::Move::typeName(m.type);
+    std::replace(type.begin(), type.end(), ' ', '_');
+    printf("step %zu %s %d %a %d %a %a\nproposed", k, type.c_str(), m.node, m.logAcceptProb, (int)(m.comment == "accepted"), m.logJacobian, m.newLogLikelihood);
+    for (double d : m.newHistory.tree.branchLen) printf(" %a", d);
+    printf("\n");
+  }
+  printf("final");
+  for (double d : sampler.currentHistory.tree.branchLen) printf(" %a", d);
+  printf("\nnewick %s\ncurrent %a best %a\n", sampler.currentHistory.tree.toString().c_str(), sampler.currentLogLikelihood, sampler.bestLogLikelihood);
+  for (int t = 0; t < (int)Sampler::Move::TotalMoveTypes; ++t) {
+    string type = Sampler::Move::typeName((Sampler::Move::Type)t);
+    std::replace(type.begin(), type.end(), ' ', '_');
+    printf("moves %s %d %d\n", type.c_str(), sampler.movesProposed[t], sampler.movesAccepted[t]);
+  }
+  std::cerr << sampler.moveStats();
+  return 0;
+}
+
 const Command commands[] = {
     {"logsumexp", 0, 1, "[-slow|-fast]", lseGrid},
     {"seqprofile", 2, 2, "<alphabet> <sequence>", leafProfileJson},
@@ -308,6 +364,7 @@ const Command commands[] = {
     {"walks", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", pairWalks},
     {"walktime", 5, 6, "<seqfile> <modelfile> <left time> <right time> <matrices> [band]", walkTiming},
     {"distances", 2, 4, "<alignfile> <modelfile> [max iterations [host pairs]]", distances},
+    {"treemoves", 5, 5, "<rows.fa> <tree.nh> <modelfile> <steps> <seed>", treeMoves},
 };
 
 }  // namespace

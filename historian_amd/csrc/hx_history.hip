@@ -1,0 +1,520 @@
+// A history resident on the device: what a tree-height MCMC on a fixed alignment accepts or rejects its moves on - the
+// substitution log-likelihood of TreeAlignFuncs::substLogLikelihood (reference src/sampler.cpp:394-407), SumProduct::fillUp
+// of every column (src/sumprod.cpp:99-161) - kept between proposals, and the indel transition counts of every branch
+// (indelLogLikelihood's pairPath walk, src/sampler.cpp:150-189, 382-392, as twelve integers per branch).
+//
+// k_history_columns is the way up of k_ancestor_columns (hx_ancestors.hip): a lane per column, a wave per mixture component,
+// exp(R t) of the branch at hand in LDS.  What differs: the tokens (transposed: [node][column]), the tree, the branch
+// matrices and the messages E, logE of every (column, component, node) stay on the device, every node in TWO slots.  A
+// proposal names the nodes whose branch changed; the kernel walks only those and their ancestors, in post order, reads a
+// node outside that set from its current slot and writes to the other slot; accepting flips the slot of the walked nodes
+// (host bookkeeping, no copy), rejecting does nothing.  A column whose root lies outside the walked set keeps its
+// likelihood.  A gap's message is all ones and is neither stored nor read.  The full evaluation is the proposal that walks
+// every node, so both run the same instructions on the same operands: the same bits.
+//
+// k_history_sum adds the column likelihoods in one workgroup, a fixed order for a given number of columns, whatever the
+// grid of the column kernel and whichever columns were recomputed.  No atomics anywhere.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <new>
+#include <vector>
+#include "../../include/historian_hip.h"
+#include "hx_lse.h"
+#include "hx_policy.h"
+#include "hx_kernels.h"
+#include "hx_sumprod.h"
+
+namespace hx {
+
+namespace {
+
+struct HsArgs {
+  int A, C, N, n_walk;
+  long long n_cols, ncp;           // ncp: the columns rounded up to whole blocks of 64
+  long long e_slot, lg_slot;       // doubles between the two slots of E and of logE
+  const signed char* tok;          // [N][ncp] -2 gap, -1 wildcard, else the residue's token
+  const int* root;                 // [ncp] the column's root, -1 in a column of gaps
+  const int* child;                // [N][2] children or -1
+  const int* walk;                 // [n_walk] the nodes to recompute, ascending (children before parents)
+  const int* info;                 // [N] bit 0: the slot of the node's messages in this evaluation (read and, if walked,
+                                   //     written); bit 1: the slot of its matrix; bit 2: walked
+  const double* ins_prob;          // [C][A]
+  const double* log_cpt_weight;    // [C]
+  const double* mats;              // [2][C][N][A][A] exp(R t)
+  double* E;                       // [2][block][cpt][node][A' / 2][64][2]
+  double* logE;                    // [2][block][cpt][node][64]
+  const double* cll_cur;           // [ncp]
+  double* cll_new;                 // [ncp]
+};
+
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// TA: the alphabet size at compile time (even) or 0 for any alphabet up to 64 symbols (vectors in private memory)
+template <int TA>
+__global__ void __launch_bounds__(512) k_history_columns(const HsArgs h, const double* __restrict__ lse_tab) {
+  constexpr int AX = TA ? TA : 64;
+  const int A = TA ? TA : h.A, C = h.C, N = h.N, AA = A * A, AP = (A + 1) & ~1;
+#define HROW(slot, cpt, r) (h.E + (slot) * h.e_slot + ((cb * C + (cpt)) * N + (r)) * (long long)(AP * 64) + lane * 2)
+#define HLG(slot, cpt, r) h.logE[(slot) * h.lg_slot + ((cb * C + (cpt)) * N + (r)) * 64 + lane]
+  extern __shared__ double sh_ll[];                 // [C][64], then per wave [A * A]: exp(R t)
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, Wb = (int)blockDim.x >> 6;
+  HX_LDS double* Lsub = (HX_LDS double*)(sh_ll + 64 * C + AA * wave);
+  for (long long base = (long long)blockIdx.x * 64; base < h.n_cols; base += (long long)gridDim.x * 64) {
+    const bool busy = base + lane < h.n_cols;
+    const long long col = base + lane;               // (< ncp: the token and root arrays hold whole blocks)
+    const long long cb = base >> 6;
+    const int root = h.root[col];
+    // the column's likelihood changes when its root was walked (a column of gaps: the constant is written anew)
+    const bool redo = busy && (root < 0 || (h.info[root] & 4));
+    auto get_row = [&](const double* rp, double (&v)[AX]) {
+      if constexpr (TA != 0) {
+#pragma unroll
+        for (int q = 0; q < TA / 2; ++q) {
+          const sp_d2 t2 = *reinterpret_cast<const sp_d2*>(rp + q * 128);
+          v[2 * q] = t2.x; v[2 * q + 1] = t2.y;
+        }
+      } else {
+        for (int a = 0; a < A; ++a) v[a] = rp[(a >> 1) * 128 + (a & 1)];
+      }
+    };
+    for (int cpt = wave; cpt < C; cpt += Wb) {
+      double cpt_ll = 0.;
+      CMat ins = cmat(h.ins_prob + cpt * A);
+      for (int k = 0; k < h.n_walk; ++k) {
+        const int r = h.walk[k], inf = h.info[r];
+        const int tk = busy ? h.tok[r * h.ncp + col] : -2;
+        if (!__any(tk != -2)) continue;              // (the whole wave: nobody needs this branch)
+        if (r != N - 1) {
+          const double* mg = h.mats + ((((long long)(inf >> 1) & 1) * C + cpt) * N + r) * AA;
+          wave_lds_sync();                           // (the reads of the previous node's matrix are done)
+          for (int q = lane; q < AA; q += 64) Lsub[q] = mg[q];
+          wave_lds_sync();
+        }
+        if (tk == -2) continue;                      // a gap: its message to the parent is all ones, and nobody reads it
+        const int c0 = h.child[2 * r], c1 = h.child[2 * r + 1];
+        const bool g0 = c0 >= 0 && h.tok[c0 * h.ncp + col] != -2, g1 = c1 >= 0 && h.tok[c1 * h.ncp + col] != -2;
+        const int s0 = g0 ? h.info[c0] & 1 : 0, s1 = g1 ? h.info[c1] & 1 : 0, sr = inf & 1;
+        double lf = (g0 ? HLG(s0, cpt, c0) : 0.) + (g1 ? HLG(s1, cpt, c1) : 0.);
+        if (tk >= 0) {
+          // a residue: F is one-hot, E a column of the matrix
+          double f = (g0 ? HROW(s0, cpt, c0)[(tk >> 1) * 128 + (tk & 1)] : 1.) * (g1 ? HROW(s1, cpt, c1)[(tk >> 1) * 128 + (tk & 1)] : 1.);
+          if (f < HX_SP_RESCALE) { lf += log(f); f = 1.; }
+          if (r == root) { cpt_ll = lf + log(f * h.ins_prob[cpt * A + tk]); continue; }
+          HLG(sr, cpt, r) = lf;
+          double* rp = HROW(sr, cpt, r);
+          if constexpr (TA != 0) {
+#pragma unroll
+            for (int q = 0; q < TA / 2; ++q)
+              *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{Lsub[2 * q * A + tk] * f, Lsub[(2 * q + 1) * A + tk] * f};
+          } else {
+            for (int a = 0; a < A; ++a) rp[(a >> 1) * 128 + (a & 1)] = Lsub[a * A + tk] * f;
+          }
+          continue;
+        }
+        // a wildcard: the full vector, rescaled as the reference does (src/sumprod.cpp:120-124)
+        double f[AX];
+        {
+          double e1[AX];
+          double fmax = 0.;
+#pragma unroll
+          for (int a = 0; a < A; ++a) f[a] = e1[a] = 1.;
+          if (g0) get_row(HROW(s0, cpt, c0), f);
+          if (g1) get_row(HROW(s1, cpt, c1), e1);
+#pragma unroll
+          for (int a = 0; a < A; ++a) {
+            f[a] *= e1[a];
+            fmax = f[a] > fmax ? f[a] : fmax;
+          }
+          if (fmax < HX_SP_RESCALE) {
+#pragma unroll
+            for (int a = 0; a < A; ++a) f[a] /= fmax;
+            lf += log(fmax);
+          }
+        }
+        if (r == root) {
+          double ip = 0.;
+#pragma unroll
+          for (int a = 0; a < A; ++a) ip += f[a] * ins[a];
+          cpt_ll = lf + log(ip);
+          continue;
+        }
+        HLG(sr, cpt, r) = lf;
+        double* rp = HROW(sr, cpt, r);
+        if constexpr (TA != 0) {
+          lds_mat_vec<AX>(Lsub, f, [&](const int q, const double ea, const double eb) { *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{ea, eb}; });
+        } else {
+          for (int a = 0; a < A; ++a) {
+            double e = 0.;
+            for (int b = 0; b < A; ++b) e += Lsub[a * A + b] * f[b];
+            rp[(a >> 1) * 128 + (a & 1)] = e;
+          }
+        }
+      }
+      sh_ll[cpt * 64 + lane] = cpt_ll;
+    }
+    __syncthreads();
+    if (wave == 0 && busy) {
+      double cll = h.cll_cur[col];
+      if (redo) {
+        cll = HX_NEG_INF;
+        for (int cpt = 0; cpt < C; ++cpt) cll = lse(cll, h.log_cpt_weight[cpt] + sh_ll[cpt * 64 + lane], lse_tab);
+      }
+      h.cll_new[col] = cll;
+    }
+    __syncthreads();            // (sh_ll is rewritten by the next block of columns)
+  }
+#undef HROW
+#undef HLG
+}
+
+// One workgroup of 1024 threads: thread t adds the columns t, t + 1024, ... in that order, then the 1024 partial sums are
+// added pairwise, neighbours first.  The order depends on the number of columns alone.
+__global__ void __launch_bounds__(1024) k_history_sum(const double* __restrict__ cll, const long long n_cols, double* __restrict__ out) {
+  __shared__ double part[1024];
+  const int t = (int)threadIdx.x;
+  double s = 0.;
+  for (long long c = t; c < n_cols; c += 1024) s += cll[c];
+  part[t] = s;
+  __syncthreads();
+  for (int step = 1; step < 1024; step <<= 1) {
+    if ((t & (2 * step - 1)) == 0) part[t] += part[t + step];
+    __syncthreads();
+  }
+  if (t == 0) *out = part[0];
+}
+
+// The new matrices of a proposal, uploaded as one block [k][cpt][A][A], to the slot the current matrix of each changed node
+// is not in (bit 1 of its info word): a workgroup per (changed node, component).
+__global__ void __launch_bounds__(256) k_history_scatter(const double* __restrict__ stage, const int* __restrict__ changed, const int* __restrict__ info,
+                                                         const int C, const int N, const int AA, double* __restrict__ mats) {
+  const int k = (int)blockIdx.x / C, cpt = (int)blockIdx.x - k * C, r = changed[k];
+  double* dst = mats + ((((long long)(info[r] >> 1) & 1) * C + cpt) * N + r) * AA;
+  const double* src = stage + ((long long)k * C + cpt) * AA;
+  for (int q = (int)threadIdx.x; q < AA; q += (int)blockDim.x) dst[q] = src[q];
+}
+
+// The indel transition counts of every branch: a wave per node, a lane per column of a block of 64, blocks in order.
+// pairPath (src/sampler.cpp:150-189) drops the columns empty in both rows and defers deletions, so between two Match
+// columns the path holds all its Insert columns, then all its Delete columns: a stretch of k inserts and m deletes that
+// ends in X (Match or End) adds
+//   k > 0: n[S][I] 1, n[I][I] k - 1, then m > 0: n[I][D] 1, n[D][D] m - 1, n[D][X] 1; m = 0: n[I][X] 1
+//   k = 0: m > 0: n[S][D] 1, n[D][D] m - 1, n[D][X] 1; m = 0: n[S][X] 1
+// with S the Start/Match row.  The lane of a Match column counts its stretch from the ballots of its block plus what
+// earlier blocks left open (k_open, m_open: the same in every lane); integers, so the order of the additions is free.
+__global__ void __launch_bounds__(256) k_history_indels(const signed char* __restrict__ tok, const int* __restrict__ parent, const int N,
+                                                        const long long n_cols, const long long ncp, long long* __restrict__ counts) {
+  __shared__ long long sh_n[4][64][12];
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+  const int r = (int)blockIdx.x * 4 + wave;
+  if (r >= N) return;                               // (whole waves; no workgroup barrier below)
+  const int p = parent[r];
+  long long n[12];
+  for (int k = 0; k < 12; ++k) n[k] = 0;
+  auto stretch = [&](const long long k, const long long m, const int x) {       // x: 0 Match, 3 End
+    if (k > 0) {
+      n[0 * 4 + 1] += 1; n[1 * 4 + 1] += k - 1;
+      if (m > 0) { n[1 * 4 + 2] += 1; n[2 * 4 + 2] += m - 1; n[2 * 4 + x] += 1; }
+      else n[1 * 4 + x] += 1;
+    } else if (m > 0) { n[0 * 4 + 2] += 1; n[2 * 4 + 2] += m - 1; n[2 * 4 + x] += 1; }
+    else n[0 * 4 + x] += 1;
+  };
+  if (p >= 0) {
+    long long k_open = 0, m_open = 0;
+    for (long long base = 0; base < n_cols; base += 64) {
+      const long long col = base + lane;
+      const bool in = col < n_cols;
+      const bool c1 = in && tok[p * ncp + col] != -2, c2 = in && tok[r * ncp + col] != -2;
+      const unsigned long long mat = __ballot(c1 && c2), ins = __ballot(!c1 && c2), del = __ballot(c1 && !c2);
+      const unsigned long long below = (1ull << lane) - 1;
+      if (c1 && c2) {
+        const unsigned long long before = mat & below;                  // the Match columns of this block before mine
+        // the columns of my stretch: after the last Match before mine
+        const unsigned long long span = before ? below & ~((2ull << (63 - __builtin_clzll(before))) - 1) : below;
+        stretch(__builtin_popcountll(ins & span) + (before ? 0 : k_open), __builtin_popcountll(del & span) + (before ? 0 : m_open), 0);
+      }
+      if (mat) {
+        const int last = 63 - __builtin_clzll(mat);
+        const unsigned long long after = last == 63 ? 0ull : ~((2ull << last) - 1);
+        k_open = __builtin_popcountll(ins & after);
+        m_open = __builtin_popcountll(del & after);
+      } else {
+        k_open += __builtin_popcountll(ins);
+        m_open += __builtin_popcountll(del);
+      }
+    }
+    if (lane == 0) stretch(k_open, m_open, 3);
+  }
+  for (int k = 0; k < 12; ++k) sh_n[wave][lane][k] = n[k];
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if (lane < 12) {
+    long long s = 0;
+    for (int l = 0; l < 64; ++l) s += sh_n[wave][l][lane];
+    counts[r * 12 + lane] = s;
+  }
+}
+
+}  // namespace
+
+}  // namespace hx
+
+using namespace hx;
+
+// (file scope: the opaque type of include/historian_hip.h)
+struct hx_history {
+  int A = 0, C = 0, N = 0, device = 0;
+  long long n_cols = 0, ncp = 0;
+  std::vector<int> parent, child;
+  std::vector<unsigned char> eslot, mslot;           // per node: the current slot of its messages and of its matrix
+  std::vector<int> changed, walked;                  // of the pending proposal
+  bool pending = false, have_counts = false;
+  int cur = 0;                                       // which of d_cll / d_sum is current
+  SpBuf tok, ints, model, mats, stage, E, logE, cll, sum, counts;
+  int *d_root = nullptr, *d_child = nullptr, *d_parent = nullptr, *d_walk = nullptr, *d_info = nullptr;
+  double *d_ins = nullptr, *d_lcw = nullptr;
+  long long e_slot = 0, lg_slot = 0;
+  int tpb = 64;
+  size_t lds = 0;
+  float ms = 0.f;
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  ~hx_history() {
+    if (ev_a) (void)hipEventDestroy(ev_a);
+    if (ev_b) (void)hipEventDestroy(ev_b);
+  }
+};
+
+namespace {
+
+// One evaluation: the slots of this proposal to the device, the column kernel over `walked`, the sum.  Returns when done.
+// new_mats: [changed][C][A][A] on the host, or null when the matrices are in place already (the first evaluation).
+int history_run(hx_history* h, const std::vector<int>& changed, const std::vector<int>& walked, const double* new_mats, hipStream_t st, double* lp_sub) {
+  const double* lse_tab = device_lse_table(h->device);
+  if (!lse_tab) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_history: hx_init has not been called for the history's device");
+  const int N = h->N;
+  std::vector<int> info(N + walked.size() + (new_mats ? changed.size() : 0));
+  std::vector<unsigned char> is_changed(N, 0), is_walked(N, 0);
+  for (int r : changed) is_changed[r] = 1;
+  for (int r : walked) is_walked[r] = 1;
+  for (int r = 0; r < N; ++r)
+    info[r] = (is_walked[r] ? (h->eslot[r] ^ 1) : h->eslot[r]) | ((is_changed[r] ? (h->mslot[r] ^ 1) : h->mslot[r]) << 1) | (is_walked[r] << 2);
+  std::copy(walked.begin(), walked.end(), info.begin() + N);
+  if (new_mats) std::copy(changed.begin(), changed.end(), info.begin() + N + walked.size());
+  // (the info words, the walk and the changed nodes are adjacent on the device: one copy; the matrices: another)
+  const size_t CAA = (size_t)h->C * h->A * h->A;
+  if (hipMemcpy(h->d_info, info.data(), info.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      (new_mats && hipMemcpy(h->stage.p, new_mats, changed.size() * CAA * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
+    return api_fail(HX_ERR_HIP, "hx_history: copy failed");
+  HsArgs a;
+  a.A = h->A; a.C = h->C; a.N = N; a.n_walk = (int)walked.size();
+  a.n_cols = h->n_cols; a.ncp = h->ncp; a.e_slot = h->e_slot; a.lg_slot = h->lg_slot;
+  a.tok = static_cast<const signed char*>(h->tok.p);
+  a.root = h->d_root; a.child = h->d_child; a.walk = h->d_walk; a.info = h->d_info;
+  a.ins_prob = h->d_ins; a.log_cpt_weight = h->d_lcw;
+  a.mats = static_cast<const double*>(h->mats.p);
+  a.E = static_cast<double*>(h->E.p); a.logE = static_cast<double*>(h->logE.p);
+  double* cll = static_cast<double*>(h->cll.p);
+  double* sum = static_cast<double*>(h->sum.p);
+  a.cll_cur = cll + h->cur * h->ncp;
+  a.cll_new = cll + (h->cur ^ 1) * h->ncp;
+  const long long blocks64 = h->ncp / 64;
+  const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
+  (void)hipEventRecord(h->ev_a, st);
+  if (new_mats)
+    hipLaunchKernelGGL(k_history_scatter, dim3((unsigned)(changed.size() * h->C)), dim3(256), 0, st, static_cast<const double*>(h->stage.p),
+                       h->d_walk + walked.size(), h->d_info, h->C, N, h->A * h->A, static_cast<double*>(h->mats.p));
+  if (h->A == 4) hipLaunchKernelGGL(k_history_columns<4>, dim3(blocks), dim3(h->tpb), h->lds, st, a, lse_tab);
+  else if (h->A == 20) hipLaunchKernelGGL(k_history_columns<20>, dim3(blocks), dim3(h->tpb), h->lds, st, a, lse_tab);
+  else hipLaunchKernelGGL(k_history_columns<0>, dim3(blocks), dim3(h->tpb), h->lds, st, a, lse_tab);
+  hipLaunchKernelGGL(k_history_sum, dim3(1), dim3(1024), 0, st, a.cll_new, h->n_cols, sum + (h->cur ^ 1));
+  (void)hipEventRecord(h->ev_b, st);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return api_fail(HX_ERR_HIP, "hx_history: kernel launch or execution failed");
+  (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
+  if (lp_sub && hipMemcpy(lp_sub, sum + (h->cur ^ 1), sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return api_fail(HX_ERR_HIP, "hx_history: copy failed");
+  return HX_OK;
+}
+
+void history_commit(hx_history* h, const std::vector<int>& changed, const std::vector<int>& walked) {
+  for (int r : changed) h->mslot[r] ^= 1;
+  for (int r : walked) h->eslot[r] ^= 1;
+  h->cur ^= 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t n_cols, const double* branch_sub, void* stream, hx_history** out) {
+  if (!out) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument");
+  *out = nullptr;
+  if (!hm || !tokens || !branch_sub || n_cols <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument or no columns");
+  const int A = hm->alph_size, C = hm->components, N = hm->n_nodes, AA = A * A;
+  if (A <= 0 || C <= 0 || N <= 0 || !hm->parent || !hm->ins_prob || !hm->log_cpt_weight)
+    return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: incomplete model");
+  if (A > 64) return api_fail(HX_ERR_RANGE, "hx_history_create: alphabets of more than 64 symbols are not supported");
+  if (C > 128) return api_fail(HX_ERR_RANGE, "hx_history_create: more than 128 mixture components are not supported");
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) return api_fail(HX_ERR_NO_DEVICE, "no HIP device");
+  if (!device_lse_table(device)) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_init has not been called for the current device");
+  // children from parents; binary, children before parents, the root last
+  std::vector<int> child(2 * (size_t)N, -1);
+  for (int r = 0; r < N; ++r) {
+    const int p = hm->parent[r];
+    if (r == N - 1) {
+      if (p >= 0) return api_fail(HX_ERR_NOT_TOPOSORTED, "hx_history_create: the last node is not the root");
+      continue;
+    }
+    if (p <= r || p >= N) return api_fail(HX_ERR_NOT_TOPOSORTED, "hx_history_create: a node precedes its child, or a second root");
+    if (child[2 * p] < 0) child[2 * p] = r;
+    else if (child[2 * p + 1] < 0) child[2 * p + 1] = r;
+    else return api_fail(HX_ERR_RANGE, "hx_history_create: a node has more than two children");
+  }
+  // tokens index the alphabet on the device: refuse anything else here, not with a fault there; transpose; find the roots
+  const long long ncp = (n_cols + 63) & ~63LL;
+  std::vector<signed char> tokT((size_t)N * ncp, (signed char)-2);
+  std::vector<int> root((size_t)ncp, -1);
+  for (int64_t c = 0; c < n_cols; ++c) {
+    const int8_t* t = tokens + c * N;
+    int roots = 0;
+    for (int r = 0; r < N; ++r) {
+      if (t[r] < -2 || t[r] >= A) return api_fail(HX_ERR_RANGE, "hx_history_create: a token outside -2 .. alphabet size - 1");
+      tokT[(size_t)r * ncp + c] = t[r];
+      if (t[r] != -2 && (r == N - 1 || t[hm->parent[r]] == -2)) { root[c] = r; ++roots; }
+    }
+    if (roots > 1) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: the ungapped nodes of a column do not form one subtree");
+  }
+  // the LDS plans, checked before anything is allocated: a wave per mixture component, up to eight, as many as keep the
+  // components' likelihoods and the waves' matrices within 96 KB (one wave's always fit: 64 KB + 32 KB)
+  const size_t ll_lds = sizeof(double) * 64 * (size_t)C, mat_lds = sizeof(double) * (size_t)AA;
+  int waves = C < 8 ? C : 8;
+  while (waves > 1 && ll_lds + waves * mat_lds > 96 * 1024) --waves;
+  const size_t col_lds = ll_lds + waves * mat_lds, sum_lds = sizeof(double) * 1024, indel_lds = sizeof(long long) * 4 * 64 * 12;
+  if (col_lds > HX_LDS_LIMIT || sum_lds > HX_LDS_LIMIT || indel_lds > HX_LDS_LIMIT)
+    return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: the LDS plan exceeds the LDS of a CU");
+  hx_history* h = new (std::nothrow) hx_history;
+  if (!h) return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_history_create: out of host memory");
+  struct Guard { hx_history* h; ~Guard() { delete h; } } guard{h};
+  h->A = A; h->C = C; h->N = N; h->device = device; h->n_cols = n_cols; h->ncp = ncp;
+  h->parent.assign(hm->parent, hm->parent + N);
+  h->child = child;
+  h->eslot.assign(N, 0);
+  h->mslot.assign(N, 1);                             // (the first evaluation "changes" every branch: its matrices go to slot 0)
+  h->tpb = 64 * waves;
+  h->lds = col_lds;
+  const int AP = (A + 1) & ~1;
+  h->e_slot = (ncp / 64) * (long long)C * N * AP * 64;
+  h->lg_slot = (ncp / 64) * (long long)C * N * 64;
+  const size_t n_int = (size_t)ncp + 2 * (size_t)N + N + 3 * (size_t)N, n_dbl = (size_t)C * A + C, n_mat = (size_t)C * N * AA;
+  if (hipMalloc(&h->tok.p, (size_t)N * ncp) != hipSuccess || hipMalloc(&h->ints.p, n_int * sizeof(int)) != hipSuccess ||
+      hipMalloc(&h->model.p, n_dbl * sizeof(double)) != hipSuccess || hipMalloc(&h->mats.p, 2 * n_mat * sizeof(double)) != hipSuccess || hipMalloc(&h->stage.p, n_mat * sizeof(double)) != hipSuccess ||
+      hipMalloc(&h->E.p, 2 * (size_t)h->e_slot * sizeof(double)) != hipSuccess || hipMalloc(&h->logE.p, 2 * (size_t)h->lg_slot * sizeof(double)) != hipSuccess ||
+      hipMalloc(&h->cll.p, 2 * (size_t)ncp * sizeof(double)) != hipSuccess || hipMalloc(&h->sum.p, 2 * sizeof(double)) != hipSuccess ||
+      hipMalloc(&h->counts.p, (size_t)N * 12 * sizeof(long long)) != hipSuccess)
+    return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_history_create: device allocation failed");
+  h->d_root = static_cast<int*>(h->ints.p);
+  h->d_child = h->d_root + ncp;
+  h->d_parent = h->d_child + 2 * (size_t)N;
+  h->d_info = h->d_parent + N;                       // [N], then the walk [<= N], then the changed nodes [<= N]
+  h->d_walk = h->d_info + N;
+  h->d_ins = static_cast<double*>(h->model.p);
+  h->d_lcw = h->d_ins + (size_t)C * A;
+  // the root's matrix is never read; the caller's [C][N][A][A] goes to slot 0 whole
+  if (hipMemcpy(h->tok.p, tokT.data(), tokT.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_root, root.data(), root.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_child, child.data(), child.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_parent, hm->parent, N * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_ins, hm->ins_prob, (size_t)C * A * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_lcw, hm->log_cpt_weight, C * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->mats.p, branch_sub, n_mat * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(h->cll.p, 0, 2 * (size_t)ncp * sizeof(double)) != hipSuccess)
+    return api_fail(HX_ERR_HIP, "hx_history_create: copy failed");
+  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess) return api_fail(HX_ERR_HIP, "hx_history_create: HIP call failed");
+  // the full evaluation: the proposal that changes and walks every node, accepted
+  std::vector<int> all(N);
+  for (int r = 0; r < N; ++r) all[r] = r;
+  const int rc = history_run(h, all, all, nullptr, static_cast<hipStream_t>(stream), nullptr);
+  if (rc != HX_OK) return rc;
+  history_commit(h, all, all);
+  guard.h = nullptr;
+  *out = h;
+  return HX_OK;
+}
+
+int hx_history_destroy(hx_history* h) {
+  delete h;
+  return HX_OK;
+}
+
+int hx_history_propose(hx_history* h, int32_t n_changed, const int32_t* nodes, const double* branch_sub, double* lp_sub, void* stream) {
+  if (!h || !nodes || !branch_sub || n_changed <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_propose: null argument or no nodes");
+  if (h->pending) return api_fail(HX_ERR_STATE, "hx_history_propose: a proposal is pending (accept or reject it first)");
+  const int N = h->N;
+  std::vector<unsigned char> mark(N, 0);
+  std::vector<int> changed;
+  for (int k = 0; k < n_changed; ++k) {
+    if (nodes[k] < 0 || nodes[k] >= N - 1) return api_fail(HX_ERR_RANGE, "hx_history_propose: a node outside 0 .. N - 2 (the root has no branch)");
+    if (mark[nodes[k]]) return api_fail(HX_ERR_INVALID_ARG, "hx_history_propose: a node named twice");
+    mark[nodes[k]] = 1;
+    changed.push_back(nodes[k]);
+  }
+  // the nodes to recompute: the changed ones and their ancestors, ascending (children before parents)
+  for (int r : changed)
+    for (int p = h->parent[r]; p >= 0 && !mark[p]; p = h->parent[p]) mark[p] = 2;
+  std::vector<int> walked;
+  for (int r = 0; r < N; ++r)
+    if (mark[r]) walked.push_back(r);
+  // (the new matrices go to the slot the current ones are not in: history_run)
+  const int rc = history_run(h, changed, walked, branch_sub, static_cast<hipStream_t>(stream), lp_sub);
+  if (rc != HX_OK) return rc;
+  h->changed.swap(changed);
+  h->walked.swap(walked);
+  h->pending = true;
+  return HX_OK;
+}
+
+int hx_history_accept(hx_history* h) {
+  if (!h) return api_fail(HX_ERR_INVALID_ARG, "hx_history_accept: null argument");
+  if (!h->pending) return api_fail(HX_ERR_STATE, "hx_history_accept: no proposal is pending");
+  history_commit(h, h->changed, h->walked);
+  h->pending = false;
+  return HX_OK;
+}
+
+int hx_history_reject(hx_history* h) {
+  if (!h) return api_fail(HX_ERR_INVALID_ARG, "hx_history_reject: null argument");
+  if (!h->pending) return api_fail(HX_ERR_STATE, "hx_history_reject: no proposal is pending");
+  h->pending = false;
+  return HX_OK;
+}
+
+int hx_history_log_like(hx_history* h, int32_t which, double* lp_sub, double* col_log_like) {
+  if (!h || (which != 0 && which != 1)) return api_fail(HX_ERR_INVALID_ARG, "hx_history_log_like: null argument, or `which` not 0 or 1");
+  if (which == 1 && !h->pending) return api_fail(HX_ERR_STATE, "hx_history_log_like: no proposal is pending");
+  const int s = h->cur ^ which;
+  if ((lp_sub && hipMemcpy(lp_sub, static_cast<double*>(h->sum.p) + s, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (col_log_like && hipMemcpy(col_log_like, static_cast<double*>(h->cll.p) + s * h->ncp, (size_t)h->n_cols * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+    return api_fail(HX_ERR_HIP, "hx_history_log_like: copy failed");
+  return HX_OK;
+}
+
+int hx_history_indel_counts(hx_history* h, int64_t* counts) {
+  if (!h || !counts) return api_fail(HX_ERR_INVALID_ARG, "hx_history_indel_counts: null argument");
+  if (!h->have_counts) {                             // (the alignment is fixed: counted once, on the null stream)
+    hipLaunchKernelGGL(k_history_indels, dim3((unsigned)((h->N + 3) / 4)), dim3(256), 0, (hipStream_t) nullptr, static_cast<const signed char*>(h->tok.p),
+                       h->d_parent, h->N, h->n_cols, h->ncp, static_cast<long long*>(h->counts.p));
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+      return api_fail(HX_ERR_HIP, "hx_history_indel_counts: kernel launch or execution failed");
+    h->have_counts = true;
+  }
+  if (hipMemcpy(counts, h->counts.p, (size_t)h->N * 12 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess)
+    return api_fail(HX_ERR_HIP, "hx_history_indel_counts: copy failed");
+  return HX_OK;
+}
+
+int hx_history_last_kernel_ms(hx_history* h, float* ms) {
+  if (!h || !ms) return api_fail(HX_ERR_INVALID_ARG, "hx_history_last_kernel_ms: null argument");
+  *ms = h->ms;
+  return HX_OK;
+}
+
+}  // extern "C"

@@ -23,8 +23,8 @@
  *   - Asynchronous on the caller's stream (they return once the work is queued): hx_batch_forward, hx_batch_backward on a
  *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
  *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
- *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix and hx_distance_neg_log_like run their kernels on `stream` and return when they
- *     are done.
+ *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix, hx_distance_neg_log_like, hx_history_create and
+ *     hx_history_propose run their kernels on `stream` and return when they are done.
  *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
  *     Forward launch (an event), with no host synchronisation.
  *   - Readers (results, matrices, cells, tracebacks, walks, counts) synchronise with the batch's LAST stream only - the stream
@@ -424,6 +424,50 @@ int hx_sumprod_ancestors(const hx_sumprod_model* model, const int8_t* tokens, in
 /* Duration of the kernels of the most recent hx_sumprod_columns or hx_sumprod_ancestors call on this thread
  * (HIP events on its stream). */
 int hx_sumprod_last_kernel_ms(float* ms);
+
+/* -- a history resident on the device: the likelihood a tree-height MCMC accepts its moves on ------
+ * TreeAlignFuncs::substLogLikelihood (reference src/sampler.cpp:394-407: SumProduct::fillUp of every column, the column
+ * log-likelihoods and their sum) of a FIXED alignment on a tree whose branch lengths change, and the indel transition
+ * counts of every branch (indelLogLikelihood's walk of pairPath, src/sampler.cpp:150-189, 382-392).  The tokens, the
+ * tree, the branch matrices and the messages of every (column, component, node) stay on the device; a proposal names
+ * the nodes whose branch changed and recomputes those and their ancestors only; accept keeps the result, reject
+ * drops it.  The sum over columns is taken on the device in an order that depends on n_cols alone: a proposal's
+ * lp_sub and col_log_like have exactly the bits of a history created with the same matrices.  No atomics. */
+typedef struct hx_history_model {
+  int32_t alph_size;             /* A <= 64                                                               */
+  int32_t components;            /* C <= 128 mixture components                                           */
+  int32_t n_nodes;               /* N tree nodes, children before parents, the root last (and only it has parent -1) */
+  const int32_t* parent;         /* [N]; at most two children per node                                    */
+  const double* ins_prob;        /* [C][A] RateModel::insProb                                             */
+  const double* log_cpt_weight;  /* [C] log RateModel::cptWeight                                          */
+} hx_history_model;
+typedef struct hx_history hx_history;   /* opaque */
+/* tokens [n_cols][N] as hx_sumprod_columns (copied); branch_sub [C][N][A][A] exp(R t) of every branch (the root's is not
+ * read).  Evaluates every column on `stream` and returns when that is done.  Refused before anything is launched:
+ * HX_ERR_NOT_TOPOSORTED (a node precedes its child; the last node is not the only root), HX_ERR_RANGE (a token >= A or
+ * < -2, a third child, A > 64, C > 128), HX_ERR_INVALID_ARG (a null pointer, n_cols <= 0, a column whose ungapped nodes
+ * are not one subtree).  Device memory: 2 C N (A' + 1) doubles per column (A' = A rounded up to even), columns rounded
+ * up to a multiple of 64.  The history lives on the calling thread's current device; later calls on it are made with that
+ * device current. */
+int hx_history_create(const hx_history_model* model, const int8_t* tokens, int64_t n_cols, const double* branch_sub,
+                      void* stream, hx_history** out);
+int hx_history_destroy(hx_history* h);
+/* nodes [n_changed]: the nodes whose branch (to their parent) has a new matrix, each in 0 .. N - 2 and once;
+ * branch_sub [n_changed][C][A][A].  Runs on `stream`, returns when done; lp_sub: the proposed sum over columns.  The
+ * current state is untouched until hx_history_accept.  n_changed = N - 1 recomputes everything (a rescale move).
+ * HX_ERR_RANGE: a node outside 0 .. N - 2; HX_ERR_STATE: a proposal is pending.  Nothing is launched then. */
+int hx_history_propose(hx_history* h, int32_t n_changed, const int32_t* nodes, const double* branch_sub, double* lp_sub,
+                       void* stream);
+/* HX_ERR_STATE without a pending proposal. */
+int hx_history_accept(hx_history* h);
+int hx_history_reject(hx_history* h);
+/* which: 0 the current state, 1 the pending proposal (HX_ERR_STATE without one).  lp_sub, col_log_like [n_cols]: either may be NULL. */
+int hx_history_log_like(hx_history* h, int32_t which, double* lp_sub, double* col_log_like);
+/* counts [N][3][4]: per node's branch to its parent n[src][dest], src Start/Match, Insert, Delete; dest Match, Insert,
+ * Delete, End, of pairPath(parent, node); the root's row is zero.  Exact integers.  Runs on the null stream. */
+int hx_history_indel_counts(hx_history* h, int64_t* counts);
+/* Duration of the kernels of the most recent evaluation (create or propose) of this history. */
+int hx_history_last_kernel_ms(hx_history* h, float* ms);
 
 /* -- tree estimation: maximum-likelihood pairwise distances (reference src/model.cpp:506-655) ------
  * RateModel::distanceMatrix for the rows of a gapped alignment: per pair of rows the counts of aligned residue
