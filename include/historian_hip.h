@@ -455,7 +455,8 @@ int hx_history_destroy(hx_history* h);
 /* nodes [n_changed]: the nodes whose branch (to their parent) has a new matrix, each in 0 .. N - 2 and once;
  * branch_sub [n_changed][C][A][A].  Runs on `stream`, returns when done; lp_sub: the proposed sum over columns.  The
  * current state is untouched until hx_history_accept.  n_changed = N - 1 recomputes everything (a rescale move).
- * HX_ERR_RANGE: a node outside 0 .. N - 2; HX_ERR_STATE: a proposal is pending.  Nothing is launched then. */
+ * HX_ERR_RANGE: a node outside 0 .. N - 2; HX_ERR_STATE: a proposal is pending; HX_ERR_INVALID_ARG: a null pointer,
+ * n_changed <= 0, a node named twice.  Nothing is launched then, and the stored state is unchanged. */
 int hx_history_propose(hx_history* h, int32_t n_changed, const int32_t* nodes, const double* branch_sub, double* lp_sub,
                        void* stream);
 /* HX_ERR_STATE without a pending proposal. */

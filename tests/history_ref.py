@@ -117,6 +117,24 @@ def _sum_in_order(values):
     return s
 
 
+def history_sum(cll):
+    """k_history_sum (hx_history.hip) restated: 1024 partial sums, thread t adding the columns t, t + 1024, ... in that
+    order from 0., then added pairwise, neighbours first (strides 1, 2, 4 ... 512).  The same bits as the device's lp_sub
+    for the same column likelihoods.  (The padding of the last round adds +0., which changes no bit of a sum begun at +0.)"""
+    cll = np.asarray(cll, dtype=np.float64)
+    rounds = -(-cll.size // 1024)
+    padded = np.zeros(rounds * 1024)
+    padded[:cll.size] = cll
+    part = np.zeros(1024)
+    for row in padded.reshape(rounds, 1024):
+        part = part + row
+    step = 1
+    while step < 1024:
+        part[::2 * step] = part[::2 * step] + part[step::2 * step]
+        step *= 2
+    return float(part[0])
+
+
 def ultrametric_tree(rng, leaves, rate=4.):
     """parent / branch length arrays of a random ultrametric binary tree, children before parents, root last: pairs of
     live lineages joined at increasing heights"""
