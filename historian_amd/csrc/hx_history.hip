@@ -3,7 +3,8 @@
 // of every column (src/sumprod.cpp:99-161) - kept between proposals, and the indel transition counts of every branch
 // (indelLogLikelihood's pairPath walk, src/sampler.cpp:150-189, 382-392, as twelve integers per branch).
 //
-// k_history_columns is the way up of k_ancestor_columns (hx_ancestors.hip): a lane per column, a wave per mixture component,
+// k_history_columns is the way up of the column sum-product, through the steps of hx_sumprod.h that k_sumprod_columns and
+// k_ancestor_columns run (the same bits where the launch plans agree): a lane per column, a wave per mixture component,
 // exp(R t) of the branch at hand in LDS.  What differs: the tokens (transposed: [node][column]), the tree, the branch
 // matrices and the messages E, logE of every (column, component, node) stay on the device, every node in TWO slots.  A
 // proposal names the nodes whose branch changed; the kernel walks only those and their ancestors, in post order, reads a
@@ -47,36 +48,22 @@ struct HsArgs {
   double* cll_new;                 // [ncp]
 };
 
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// TA: the alphabet size at compile time (even) or 0 for any alphabet up to 64 symbols (vectors in private memory)
+// TA: the alphabet size at compile time (even) or 0 for any alphabet up to 64 symbols (see hx_sumprod.h); the matrices
+// are always in LDS (hx_history_create sheds waves until they fit)
 template <int TA>
 __global__ void __launch_bounds__(512) k_history_columns(const HsArgs h, const double* __restrict__ lse_tab) {
-  constexpr int AX = TA ? TA : 64;
-  const int A = TA ? TA : h.A, C = h.C, N = h.N, AA = A * A, AP = (A + 1) & ~1;
-#define HROW(slot, cpt, r) (h.E + (slot) * h.e_slot + ((cb * C + (cpt)) * N + (r)) * (long long)(AP * 64) + lane * 2)
-#define HLG(slot, cpt, r) h.logE[(slot) * h.lg_slot + ((cb * C + (cpt)) * N + (r)) * 64 + lane]
+  constexpr int AX = sp_ax<TA>;
+  const int A = TA ? TA : h.A, C = h.C, N = h.N, AA = A * A;
   extern __shared__ double sh_ll[];                 // [C][64], then per wave [A * A]: exp(R t)
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, Wb = (int)blockDim.x >> 6;
   HX_LDS double* Lsub = (HX_LDS double*)(sh_ll + 64 * C + AA * wave);
   for (long long base = (long long)blockIdx.x * 64; base < h.n_cols; base += (long long)gridDim.x * 64) {
     const bool busy = base + lane < h.n_cols;
     const long long col = base + lane;               // (< ncp: the token and root arrays hold whole blocks)
-    const long long cb = base >> 6;
+    const SpBlock blk{base >> 6, C, N, (A + 1) & ~1, lane};
     const int root = h.root[col];
     // the column's likelihood changes when its root was walked (a column of gaps: the constant is written anew)
     const bool redo = busy && (root < 0 || (h.info[root] & 4));
-    auto get_row = [&](const double* rp, double (&v)[AX]) {
-      if constexpr (TA != 0) {
-#pragma unroll
-        for (int q = 0; q < TA / 2; ++q) {
-          const sp_d2 t2 = *reinterpret_cast<const sp_d2*>(rp + q * 128);
-          v[2 * q] = t2.x; v[2 * q + 1] = t2.y;
-        }
-      } else {
-        for (int a = 0; a < A; ++a) v[a] = rp[(a >> 1) * 128 + (a & 1)];
-      }
-    };
     for (int cpt = wave; cpt < C; cpt += Wb) {
       double cpt_ll = 0.;
       CMat ins = cmat(h.ins_prob + cpt * A);
@@ -85,86 +72,40 @@ __global__ void __launch_bounds__(512) k_history_columns(const HsArgs h, const d
         const int tk = busy ? h.tok[r * h.ncp + col] : -2;
         if (!__any(tk != -2)) continue;              // (the whole wave: nobody needs this branch)
         if (r != N - 1) {
-          const double* mg = h.mats + ((((long long)(inf >> 1) & 1) * C + cpt) * N + r) * AA;
           wave_lds_sync();                           // (the reads of the previous node's matrix are done)
-          for (int q = lane; q < AA; q += 64) Lsub[q] = mg[q];
+          lds_stage<false>(Lsub, h.mats + ((((long long)(inf >> 1) & 1) * C + cpt) * N + r) * AA, A, lane);
           wave_lds_sync();
         }
         if (tk == -2) continue;                      // a gap: its message to the parent is all ones, and nobody reads it
+        // a node's two slots are two bases of the same block layout
         const int c0 = h.child[2 * r], c1 = h.child[2 * r + 1];
         const bool g0 = c0 >= 0 && h.tok[c0 * h.ncp + col] != -2, g1 = c1 >= 0 && h.tok[c1 * h.ncp + col] != -2;
         const int s0 = g0 ? h.info[c0] & 1 : 0, s1 = g1 ? h.info[c1] & 1 : 0, sr = inf & 1;
-        double lf = (g0 ? HLG(s0, cpt, c0) : 0.) + (g1 ? HLG(s1, cpt, c1) : 0.);
+        const long long at0 = blk.node(cpt, c0), at1 = blk.node(cpt, c1), at = blk.node(cpt, r);
+        const double* e0 = blk.row(h.E + s0 * h.e_slot, at0);
+        const double* e1 = blk.row(h.E + s1 * h.e_slot, at1);
+        double* rp = blk.row(h.E + sr * h.e_slot, at);
+        double lf = (g0 ? blk.lg(h.logE + s0 * h.lg_slot, at0) : 0.) + (g1 ? blk.lg(h.logE + s1 * h.lg_slot, at1) : 0.);
         if (tk >= 0) {
-          // a residue: F is one-hot, E a column of the matrix
-          double f = (g0 ? HROW(s0, cpt, c0)[(tk >> 1) * 128 + (tk & 1)] : 1.) * (g1 ? HROW(s1, cpt, c1)[(tk >> 1) * 128 + (tk & 1)] : 1.);
-          if (f < HX_SP_RESCALE) { lf += log(f); f = 1.; }
+          // a residue: E is a column of the matrix
+          const double f = residue_f(g0, e0, g1, e1, tk, lf);
           if (r == root) { cpt_ll = lf + log(f * h.ins_prob[cpt * A + tk]); continue; }
-          HLG(sr, cpt, r) = lf;
-          double* rp = HROW(sr, cpt, r);
-          if constexpr (TA != 0) {
-#pragma unroll
-            for (int q = 0; q < TA / 2; ++q)
-              *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{Lsub[2 * q * A + tk] * f, Lsub[(2 * q + 1) * A + tk] * f};
-          } else {
-            for (int a = 0; a < A; ++a) rp[(a >> 1) * 128 + (a & 1)] = Lsub[a * A + tk] * f;
-          }
+          blk.lg(h.logE + sr * h.lg_slot, at) = lf;
+          put_row<TA>(rp, A, [&](const int a) { return Lsub[a * A + tk] * f; });
           continue;
         }
-        // a wildcard: the full vector, rescaled as the reference does (src/sumprod.cpp:120-124)
         double f[AX];
-        {
-          double e1[AX];
-          double fmax = 0.;
-#pragma unroll
-          for (int a = 0; a < A; ++a) f[a] = e1[a] = 1.;
-          if (g0) get_row(HROW(s0, cpt, c0), f);
-          if (g1) get_row(HROW(s1, cpt, c1), e1);
-#pragma unroll
-          for (int a = 0; a < A; ++a) {
-            f[a] *= e1[a];
-            fmax = f[a] > fmax ? f[a] : fmax;
-          }
-          if (fmax < HX_SP_RESCALE) {
-#pragma unroll
-            for (int a = 0; a < A; ++a) f[a] /= fmax;
-            lf += log(fmax);
-          }
-        }
-        if (r == root) {
-          double ip = 0.;
-#pragma unroll
-          for (int a = 0; a < A; ++a) ip += f[a] * ins[a];
-          cpt_ll = lf + log(ip);
-          continue;
-        }
-        HLG(sr, cpt, r) = lf;
-        double* rp = HROW(sr, cpt, r);
-        if constexpr (TA != 0) {
-          lds_mat_vec<AX>(Lsub, f, [&](const int q, const double ea, const double eb) { *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{ea, eb}; });
-        } else {
-          for (int a = 0; a < A; ++a) {
-            double e = 0.;
-            for (int b = 0; b < A; ++b) e += Lsub[a * A + b] * f[b];
-            rp[(a >> 1) * 128 + (a & 1)] = e;
-          }
-        }
+        wild_f<TA>(g0, e0, g1, e1, A, f, lf);
+        if (r == root) { cpt_ll = wild_root_ll<TA>(f, ins, A, lf); continue; }
+        blk.lg(h.logE + sr * h.lg_slot, at) = lf;
+        mat_vec_store<TA, true, false>(Lsub, CMat(), A, f, rp);
       }
       sh_ll[cpt * 64 + lane] = cpt_ll;
     }
     __syncthreads();
-    if (wave == 0 && busy) {
-      double cll = h.cll_cur[col];
-      if (redo) {
-        cll = HX_NEG_INF;
-        for (int cpt = 0; cpt < C; ++cpt) cll = lse(cll, h.log_cpt_weight[cpt] + sh_ll[cpt * 64 + lane], lse_tab);
-      }
-      h.cll_new[col] = cll;
-    }
+    if (wave == 0 && busy) h.cll_new[col] = redo ? combine_components(sh_ll, h.log_cpt_weight, C, lane, lse_tab) : h.cll_cur[col];
     __syncthreads();            // (sh_ll is rewritten by the next block of columns)
   }
-#undef HROW
-#undef HLG
 }
 
 // One workgroup of 1024 threads: thread t adds the columns t, t + 1024, ... in that order, then the 1024 partial sums are
@@ -268,9 +209,11 @@ struct hx_history {
   std::vector<int> changed, walked;                  // of the pending proposal
   bool pending = false, have_counts = false;
   int cur = 0;                                       // which of d_cll / d_sum is current
-  SpBuf tok, ints, model, mats, stage, E, logE, cll, sum, counts;
-  int *d_root = nullptr, *d_child = nullptr, *d_parent = nullptr, *d_walk = nullptr, *d_info = nullptr;
-  double *d_ins = nullptr, *d_lcw = nullptr;
+  SpUpload model;                                    // the roots, the tree, the info words, the walk and the changed nodes, the mixture
+  SpBuf tok, mats, stage, E, logE, cll, sum, counts;
+  const int *d_root = nullptr, *d_child = nullptr, *d_parent = nullptr;
+  int *d_walk = nullptr, *d_info = nullptr;
+  const double *d_ins = nullptr, *d_lcw = nullptr;
   long long e_slot = 0, lg_slot = 0;
   int tpb = 64;
   size_t lds = 0;
@@ -348,28 +291,14 @@ int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t 
   if (!out) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument");
   *out = nullptr;
   if (!hm || !tokens || !branch_sub || n_cols <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument or no columns");
+  const char* fn = "hx_history_create";
   const int A = hm->alph_size, C = hm->components, N = hm->n_nodes, AA = A * A;
-  if (A <= 0 || C <= 0 || N <= 0 || !hm->parent || !hm->ins_prob || !hm->log_cpt_weight)
-    return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: incomplete model");
-  if (A > 64) return api_fail(HX_ERR_RANGE, "hx_history_create: alphabets of more than 64 symbols are not supported");
-  if (C > 128) return api_fail(HX_ERR_RANGE, "hx_history_create: more than 128 mixture components are not supported");
   int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return api_fail(HX_ERR_NO_DEVICE, "no HIP device");
-  if (!device_lse_table(device)) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_init has not been called for the current device");
-  // children from parents; binary, children before parents, the root last
-  std::vector<int> child(2 * (size_t)N, -1);
-  for (int r = 0; r < N; ++r) {
-    const int p = hm->parent[r];
-    if (r == N - 1) {
-      if (p >= 0) return api_fail(HX_ERR_NOT_TOPOSORTED, "hx_history_create: the last node is not the root");
-      continue;
-    }
-    if (p <= r || p >= N) return api_fail(HX_ERR_NOT_TOPOSORTED, "hx_history_create: a node precedes its child, or a second root");
-    if (child[2 * p] < 0) child[2 * p] = r;
-    else if (child[2 * p + 1] < 0) child[2 * p + 1] = r;
-    else return api_fail(HX_ERR_RANGE, "hx_history_create: a node has more than two children");
-  }
-  // tokens index the alphabet on the device: refuse anything else here, not with a fault there; transpose; find the roots
+  const double* lse_tab = nullptr;
+  std::vector<int> child;
+  if (int rc = sp_check_model(fn, A > 0 && C > 0 && N > 0 && hm->parent && hm->ins_prob && hm->log_cpt_weight, A, C, HX_ERR_RANGE, &device, &lse_tab)) return rc;
+  if (int rc = sp_children(fn, hm->parent, N, true, HX_ERR_RANGE, child)) return rc;
+  // the token check in the same pass over the tokens as the transpose and the search for the roots
   const long long ncp = (n_cols + 63) & ~63LL;
   std::vector<signed char> tokT((size_t)N * ncp, (signed char)-2);
   std::vector<int> root((size_t)ncp, -1);
@@ -377,58 +306,49 @@ int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t 
     const int8_t* t = tokens + c * N;
     int roots = 0;
     for (int r = 0; r < N; ++r) {
-      if (t[r] < -2 || t[r] >= A) return api_fail(HX_ERR_RANGE, "hx_history_create: a token outside -2 .. alphabet size - 1");
+      if (!sp_token_ok(t[r], A)) return sp_fail(HX_ERR_RANGE, fn, "a token outside -2 .. alphabet size - 1");
       tokT[(size_t)r * ncp + c] = t[r];
       if (t[r] != -2 && (r == N - 1 || t[hm->parent[r]] == -2)) { root[c] = r; ++roots; }
     }
-    if (roots > 1) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: the ungapped nodes of a column do not form one subtree");
+    if (roots > 1) return sp_fail(HX_ERR_INVALID_ARG, fn, "the ungapped nodes of a column do not form one subtree");
   }
-  // the LDS plans, checked before anything is allocated: a wave per mixture component, up to eight, as many as keep the
-  // components' likelihoods and the waves' matrices within 96 KB (one wave's always fit: 64 KB + 32 KB)
-  const size_t ll_lds = sizeof(double) * 64 * (size_t)C, mat_lds = sizeof(double) * (size_t)AA;
-  int waves = C < 8 ? C : 8;
-  while (waves > 1 && ll_lds + waves * mat_lds > 96 * 1024) --waves;
-  const size_t col_lds = ll_lds + waves * mat_lds, sum_lds = sizeof(double) * 1024, indel_lds = sizeof(long long) * 4 * 64 * 12;
-  if (col_lds > HX_LDS_LIMIT || sum_lds > HX_LDS_LIMIT || indel_lds > HX_LDS_LIMIT)
-    return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: the LDS plan exceeds the LDS of a CU");
+  // the LDS plans, checked before anything is allocated
+  const SpPlan plan = sp_column_plan(A, C, 1, true);
+  const size_t sum_lds = sizeof(double) * 1024, indel_lds = sizeof(long long) * 4 * 64 * 12;
+  if (plan.lds > HX_LDS_LIMIT || sum_lds > HX_LDS_LIMIT || indel_lds > HX_LDS_LIMIT) return sp_fail(HX_ERR_INVALID_ARG, fn, "the LDS plan exceeds the LDS of a CU");
   hx_history* h = new (std::nothrow) hx_history;
-  if (!h) return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_history_create: out of host memory");
+  if (!h) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "out of host memory");
   struct Guard { hx_history* h; ~Guard() { delete h; } } guard{h};
   h->A = A; h->C = C; h->N = N; h->device = device; h->n_cols = n_cols; h->ncp = ncp;
   h->parent.assign(hm->parent, hm->parent + N);
   h->child = child;
   h->eslot.assign(N, 0);
   h->mslot.assign(N, 1);                             // (the first evaluation "changes" every branch: its matrices go to slot 0)
-  h->tpb = 64 * waves;
-  h->lds = col_lds;
+  h->tpb = 64 * plan.waves;
+  h->lds = plan.lds;
   const int AP = (A + 1) & ~1;
   h->e_slot = (ncp / 64) * (long long)C * N * AP * 64;
   h->lg_slot = (ncp / 64) * (long long)C * N * 64;
-  const size_t n_int = (size_t)ncp + 2 * (size_t)N + N + 3 * (size_t)N, n_dbl = (size_t)C * A + C, n_mat = (size_t)C * N * AA;
-  if (hipMalloc(&h->tok.p, (size_t)N * ncp) != hipSuccess || hipMalloc(&h->ints.p, n_int * sizeof(int)) != hipSuccess ||
-      hipMalloc(&h->model.p, n_dbl * sizeof(double)) != hipSuccess || hipMalloc(&h->mats.p, 2 * n_mat * sizeof(double)) != hipSuccess || hipMalloc(&h->stage.p, n_mat * sizeof(double)) != hipSuccess ||
+  const size_t n_mat = (size_t)C * N * AA;
+  SpUpload& up = h->model;
+  if (hipMalloc(&h->tok.p, (size_t)N * ncp) != hipSuccess ||
+      !up.alloc(SpUpload::room((size_t)ncp * sizeof(int)) + sp_tree_room(A, C, N, false) + SpUpload::room(3 * (size_t)N * sizeof(int))) ||
+      hipMalloc(&h->mats.p, 2 * n_mat * sizeof(double)) != hipSuccess || hipMalloc(&h->stage.p, n_mat * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->E.p, 2 * (size_t)h->e_slot * sizeof(double)) != hipSuccess || hipMalloc(&h->logE.p, 2 * (size_t)h->lg_slot * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->cll.p, 2 * (size_t)ncp * sizeof(double)) != hipSuccess || hipMalloc(&h->sum.p, 2 * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->counts.p, (size_t)N * 12 * sizeof(long long)) != hipSuccess)
-    return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_history_create: device allocation failed");
-  h->d_root = static_cast<int*>(h->ints.p);
-  h->d_child = h->d_root + ncp;
-  h->d_parent = h->d_child + 2 * (size_t)N;
-  h->d_info = h->d_parent + N;                       // [N], then the walk [<= N], then the changed nodes [<= N]
+    return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+  h->d_root = up.put(root.data(), root.size());
+  const SpTree tr = sp_put_tree(up, A, C, N, hm->parent, child, hm->ins_prob, hm->log_cpt_weight, nullptr);
+  h->d_child = tr.child; h->d_parent = tr.parent; h->d_ins = tr.ins_prob; h->d_lcw = tr.log_cpt_weight;
+  h->d_info = up.reserve<int>(3 * (size_t)N);        // [N], then the walk [<= N], then the changed nodes [<= N]
   h->d_walk = h->d_info + N;
-  h->d_ins = static_cast<double*>(h->model.p);
-  h->d_lcw = h->d_ins + (size_t)C * A;
   // the root's matrix is never read; the caller's [C][N][A][A] goes to slot 0 whole
-  if (hipMemcpy(h->tok.p, tokT.data(), tokT.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_root, root.data(), root.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_child, child.data(), child.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_parent, hm->parent, N * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_ins, hm->ins_prob, (size_t)C * A * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_lcw, hm->log_cpt_weight, C * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+  if (!up.copied || hipMemcpy(h->tok.p, tokT.data(), tokT.size(), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->mats.p, branch_sub, n_mat * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(h->cll.p, 0, 2 * (size_t)ncp * sizeof(double)) != hipSuccess)
-    return api_fail(HX_ERR_HIP, "hx_history_create: copy failed");
-  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess) return api_fail(HX_ERR_HIP, "hx_history_create: HIP call failed");
+    return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
   // the full evaluation: the proposal that changes and walks every node, accepted
   std::vector<int> all(N);
   for (int r = 0; r < N; ++r) all[r] = r;

@@ -5,7 +5,7 @@
 // In the reference one SumProduct object walks the columns one after the other (AlignColSumProduct, and once per
 // posterior-weighted DP cell in BackwardMatrix::getCounts).  Columns and mixture components are independent, so here a
 // (column, component) is a thread (k_sumprod_columns): every thread runs the tip-to-root and root-to-tip passes of its column - tiny tree recursions,
-// A x A matrix-vector products per branch and mixture component - with its messages E, F, G in a global scratch laid out
+// A x A matrix-vector products per branch and mixture component, the steps of hx_sumprod.h - with its messages E, F, G in a global scratch laid out
 // in blocks of 64 columns ([block][.][64 lanes], two vector entries per lane and access), then turns the messages of every branch
 // into the eigen basis (D_k, U_l).  The reference adds weight x D_k J_kl U_l to the count matrix column by column; J_kl
 // (eigenSubCount of the branch) does not depend on the column, so the sum over columns is an outer-product sum
@@ -58,28 +58,16 @@ struct SpModel {
 // [block][cpt][node][Ur, Dr, (Ui, Di)][a][64]
 struct SpScratch { double* E; double* G; double* logE; double* logF; double* logG; double* maxU; double* Froot; double* rootc; double* basis; };
 
-// TA: the alphabet size as a compile-time constant (message vectors live in registers, loops unrolled), or 0 for any
-// alphabet of up to 64 symbols (vectors in private memory).
-// LM: a wave keeps the matrices it multiplies with in LDS - exp(R t) of the branch at hand (re-staged per node), the real
-// parts of the eigenvectors and of their inverse (per component) - and reads their entries as LDS broadcasts; without it
-// they come through the scalar cache, which the 3 KB per matrix-vector product overrun (2.9 TFLOP/s, one FMA per ~100 cycles).
+// TA, LM: see hx_sumprod.h.  With LM a wave keeps three matrices in LDS - exp(R t) of the branch at hand (re-staged per
+// node), the real parts of the eigenvectors and of their inverse (per component); through the scalar cache the 3 KB per
+// matrix-vector product overrun it (2.9 TFLOP/s, one FMA per ~100 cycles).
 template <int TA, bool LM>
 __global__ void __launch_bounds__(512, HX_SP_WAVES_PER_SIMD) k_sumprod_columns(const SpModel m, const signed char* __restrict__ tok, const double* __restrict__ weight,
                                                          const long long n_cols, const SpScratch s, const double* __restrict__ lse_tab,
                                                          double* __restrict__ col_log_like, double* __restrict__ root_post) {
-  constexpr int AX = TA ? TA : 64;
-  const int A = TA ? TA : m.A, C = m.C, N = m.N, AA = A * A, AP = (A + 1) & ~1;
+  constexpr int AX = sp_ax<TA>;
+  const int A = TA ? TA : m.A, C = m.C, N = m.N, AA = A * A;
   const int parts = m.real_basis ? 2 : 4;
-  // Scratch layout: blocks of 64 columns, [block][.][64] - everything a wavefront touches in a pass lies in one
-  // contiguous stretch (a few hundred KB) instead of one 512-byte piece per row of a [.][all columns] array, rows
-  // n_cols * 8 bytes apart (two thousand pages per wavefront).  `cb`: this wave's block, `cl` = the lane.
-  // Inside a block a message vector is stored two entries per lane and row, [a / 2][64][2]: a lane moves 16 bytes per
-  // memory instruction (8-byte accesses run at 0.5-0.7 of the 16-byte rate).  AP = A rounded up to even.
-#define ROWP(P, idx) ((P) + (idx) * (long long)(AP * 64) + cl * 2)
-#define AT(P, cpt, r, a) ROWP(P, (cb * C + (cpt)) * N + (r))[((a) >> 1) * 128 + ((a) & 1)]
-#define LG(P, cpt, r) P[((cb * C + (cpt)) * N + (r)) * 64 + cl]
-#define BS(cpt, r, part, l) ROWP(s.basis, ((cb * C + (cpt)) * N + (r)) * parts + (part))[((l) >> 1) * 128 + ((l) & 1)]
-#define FR(cpt, a) s.Froot[((cb * C + (cpt)) * A + (a)) * 64 + cl]
   // a wavefront is 64 columns of one mixture component (the component is uniform over the wave, so the model's matrices
   // still come through scalar loads); the waves of a workgroup share the columns and split the components.  They meet
   // twice: for the column likelihood (through LDS) and for the root posterior (through the scratch).
@@ -88,270 +76,163 @@ __global__ void __launch_bounds__(512, HX_SP_WAVES_PER_SIMD) k_sumprod_columns(c
   HX_LDS double* Lsub = (HX_LDS double*)(sh_ll + 64 * C + (LM ? 3 * AA * wave : 0));
   HX_LDS double* Linv = Lsub + AA;
   HX_LDS double* Lvec = Linv + AA;
-  auto wave_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
   for (long long base = (long long)blockIdx.x * 64; base < n_cols; base += (long long)gridDim.x * 64) {
     const bool busy = base + lane < n_cols;
     const long long col = busy ? base + lane : 0;
-    const long long cb = base >> 6;
-    const int cl = lane;
-    // a whole row of the scratch, 16 bytes per access when the alphabet size is a compile-time even number
-    auto put_row = [&](double* rp, auto&& gen) {
-      if constexpr (TA != 0 && TA % 2 == 0) {
-#pragma unroll
-        for (int q = 0; q < TA / 2; ++q) *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{gen(2 * q), gen(2 * q + 1)};
-      } else {
-        for (int a = 0; a < A; ++a) rp[(a >> 1) * 128 + (a & 1)] = gen(a);
-      }
-    };
-    auto get_row = [&](const double* rp, double (&v)[AX]) {
-      if constexpr (TA != 0 && TA % 2 == 0) {
-#pragma unroll
-        for (int q = 0; q < TA / 2; ++q) {
-          const sp_d2 t2 = *reinterpret_cast<const sp_d2*>(rp + q * 128);
-          v[2 * q] = t2.x; v[2 * q + 1] = t2.y;
-        }
-      } else {
-        for (int a = 0; a < A; ++a) v[a] = rp[(a >> 1) * 128 + (a & 1)];
-      }
-    };
-#define EROW(P, cpt, r) ROWP(P, (cb * C + (cpt)) * N + (r))
-#define BROW(cpt, r, part) ROWP(s.basis, ((cb * C + (cpt)) * N + (r)) * parts + (part))
+    const SpBlock blk{base >> 6, C, N, (A + 1) & ~1, lane};
+    // the bases of a node: parts rows, U then D (real, then imaginary); F at the root and the root-count terms [cpt][a][64]
+    auto basis = [&](const long long at, const int part) { return blk.row(s.basis, at * parts + part); };
+    auto froot = [&](const int cpt, const int a) -> double& { return s.Froot[((blk.cb * C + cpt) * A + a) * 64 + lane]; };
     const signed char* t = tok + col * N;       // -2 gap, -1 wildcard, else the residue's token
     const double w = weight ? weight[col] : 1.;
-    int root = -1;
-    for (int r = 0; r < N; ++r)
-      if (t[r] != -2 && (m.parent[r] < 0 || t[m.parent[r]] == -2)) root = r;     // (one root per column: the caller's contract)
-    double cll = HX_NEG_INF;
+    const int root = column_root(t, m.parent, N);
     // ---- tip-to-root (src/sumprod.cpp:99-161); U of every branch in the eigen basis on the way (src/sumprod.cpp:318-340) ----
     for (int cpt = wave; cpt < C; cpt += Wb) {
       double cpt_ll = 0.;
       CMat ins = cmat(m.ins_prob + cpt * A);
+      const double* invg = m.einv_re + (long long)cpt * AA;
+      CMat ii = cmat(m.einv_im + (long long)cpt * AA);
       if (LM) {
-        wave_sync();
-        for (int k = lane; k < AA; k += 64) {
-          Linv[k] = m.einv_re[(long long)cpt * AA + k];
-          // (the root-to-tip pass multiplies with the transposed matrices: staged transposed where the row routine is used)
-          if constexpr (TA != 0 && TA % 2 == 0) Lvec[(k % A) * A + k / A] = m.evec_re[(long long)cpt * AA + k];
-          else Lvec[k] = m.evec_re[(long long)cpt * AA + k];
-        }
+        wave_lds_sync();
+        lds_stage<false>(Linv, invg, A, lane);
+        lds_stage<sp_rows<TA>>(Lvec, m.evec_re + (long long)cpt * AA, A, lane);     // (the root-to-tip pass multiplies with the transposed matrices)
       }
       for (int r = 0; r < N; ++r) {
+        const double* subg = m.branch_sub + ((long long)cpt * N + r) * AA;
         if (LM && m.parent[r] >= 0) {
-          wave_sync();                               // (the reads of the previous node's matrix are done)
-          for (int k = lane; k < AA; k += 64) Lsub[k] = m.branch_sub[((long long)cpt * N + r) * AA + k];
-          wave_sync();
+          wave_lds_sync();                               // (the reads of the previous node's matrix are done)
+          lds_stage<false>(Lsub, subg, A, lane);
+          wave_lds_sync();
         }
         if (!busy) continue;
         const int c0 = m.child[2 * r], c1 = m.child[2 * r + 1];
-        double lf = (c0 >= 0 ? LG(s.logE, cpt, c0) : 0.) + (c1 >= 0 ? LG(s.logE, cpt, c1) : 0.);
+        const long long at = blk.node(cpt, r), at0 = blk.node(cpt, c0), at1 = blk.node(cpt, c1);
+        double lf = (c0 >= 0 ? blk.lg(s.logE, at0) : 0.) + (c1 >= 0 ? blk.lg(s.logE, at1) : 0.);
         const int tk = t[r];
         if (tk == -2) {
           // a gap: its message to the parent is all ones, and no counts on the branch above it
-          put_row(EROW(s.E, cpt, r), [](int) { return 1.; });
-          LG(s.logE, cpt, r) = 0.;
-          LG(s.logF, cpt, r) = lf;
-          put_row(BROW(cpt, r, 0), [](int) { return 0.; });
+          put_row<TA>(blk.row(s.E, at), A, [](int) { return 1.; });
+          blk.lg(s.logE, at) = 0.;
+          blk.lg(s.logF, at) = lf;
+          put_row<TA>(basis(at, 0), A, [](int) { return 0.; });
           if (parts == 4)
-            for (int l = 0; l < A; ++l) BS(cpt, r, 2, l) = 0.;
+            for (int l = 0; l < A; ++l) sp_at(basis(at, 2), l) = 0.;
           continue;
         }
-        CMat sub_s = cmat(m.branch_sub + ((long long)cpt * N + r) * AA);
-        CMat ir_s = cmat(m.einv_re + (long long)cpt * AA);
-        CMat ii = cmat(m.einv_im + (long long)cpt * AA);
-        auto sub = [&](const int k) -> double { return LM ? Lsub[k] : sub_s[k]; };
-        auto ir = [&](const int k) -> double { return LM ? Linv[k] : ir_s[k]; };
         if (tk >= 0) {
-          // a residue: F is one-hot, E and U are columns of the matrices
-          double f = (c0 >= 0 ? AT(s.E, cpt, c0, tk) : 1.) * (c1 >= 0 ? AT(s.E, cpt, c1, tk) : 1.);
-          if (f < HX_SP_RESCALE) { lf += log(f); f = 1.; }
-          LG(s.logF, cpt, r) = lf;
+          // a residue: E and U are columns of the matrices
+          const double f = residue_f(c0 >= 0, blk.row(s.E, at0), c1 >= 0, blk.row(s.E, at1), tk, lf);
+          blk.lg(s.logF, at) = lf;
           if (r == root) {
 #pragma unroll
-            for (int a = 0; a < A; ++a) FR(cpt, a) = a == tk ? f : 0.;
+            for (int a = 0; a < A; ++a) froot(cpt, a) = a == tk ? f : 0.;
             cpt_ll += lf + log(f * m.ins_prob[cpt * A + tk]);
           } else {
-            LG(s.logE, cpt, r) = lf;
-            LG(s.maxU, cpt, r) = f;
-            const double* subg = m.branch_sub + ((long long)cpt * N + r) * AA;
-            put_row(EROW(s.E, cpt, r), [&](const int a) { return (LM ? Lsub[a * A + tk] : subg[a * A + tk]) * f; });
-            put_row(BROW(cpt, r, 0), [&](const int l) { return (LM ? Linv[l * A + tk] : m.einv_re[(long long)cpt * AA + l * A + tk]) * (f / f); });
+            blk.lg(s.logE, at) = lf;
+            blk.lg(s.maxU, at) = f;
+            put_row<TA>(blk.row(s.E, at), A, [&](const int a) { return (LM ? Lsub[a * A + tk] : subg[a * A + tk]) * f; });
+            put_row<TA>(basis(at, 0), A, [&](const int l) { return (LM ? Linv[l * A + tk] : invg[l * A + tk]) * (f / f); });
             if (parts == 4)
-              for (int l = 0; l < A; ++l) BS(cpt, r, 2, l) = m.einv_im[(long long)cpt * AA + l * A + tk] * (f / f);
+              for (int l = 0; l < A; ++l) sp_at(basis(at, 2), l) = m.einv_im[(long long)cpt * AA + l * A + tk] * (f / f);
           }
           continue;
         }
-        // a wildcard: the full vector
         double f[AX];
-        double fmax = 0.;
-        {
-          double e1[AX];
-#pragma unroll
-          for (int a = 0; a < A; ++a) f[a] = e1[a] = 1.;
-          if (c0 >= 0) get_row(EROW(s.E, cpt, c0), f);
-          if (c1 >= 0) get_row(EROW(s.E, cpt, c1), e1);
-#pragma unroll
-          for (int a = 0; a < A; ++a) {
-            f[a] *= e1[a];
-            fmax = f[a] > fmax ? f[a] : fmax;
-          }
-        }
-        if (fmax < HX_SP_RESCALE) {
-#pragma unroll
-          for (int a = 0; a < A; ++a) f[a] /= fmax;
-          lf += log(fmax);
-          fmax = 1.;
-        }
-        LG(s.logF, cpt, r) = lf;
+        const double fmax = wild_f<TA>(c0 >= 0, blk.row(s.E, at0), c1 >= 0, blk.row(s.E, at1), A, f, lf);
+        blk.lg(s.logF, at) = lf;
         if (r == root) {
-          double ip = 0.;
 #pragma unroll
-          for (int a = 0; a < A; ++a) {
-            FR(cpt, a) = f[a];
-            ip += f[a] * ins[a];
-          }
-          cpt_ll += lf + log(ip);
+          for (int a = 0; a < A; ++a) froot(cpt, a) = f[a];
+          cpt_ll += wild_root_ll<TA>(f, ins, A, lf);
           continue;
         }
-        LG(s.logE, cpt, r) = lf;
-        LG(s.maxU, cpt, r) = fmax;
-        if constexpr (LM && TA != 0 && TA % 2 == 0) {
-          {
-            double* rp = EROW(s.E, cpt, r);
-            lds_mat_vec<AX>(Lsub, f, [&](const int q, const double ea, const double eb) { *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{ea, eb}; });
-          }
+        blk.lg(s.logE, at) = lf;
+        blk.lg(s.maxU, at) = fmax;
+        mat_vec_store<TA, LM, false>(Lsub, cmat(subg), A, f, blk.row(s.E, at));
+        // U = evecInv F / max F (the row routine multiplies with the inverse; the loop divides, as it always did)
+        if constexpr (LM && sp_rows<TA>) {
           const double inv_fmax = 1. / fmax;
 #pragma unroll
           for (int a = 0; a < A; ++a) f[a] *= inv_fmax;
-          {
-            double* rp = BROW(cpt, r, 0);
-            lds_mat_vec<AX>(Linv, f, [&](const int q, const double ua, const double ub) { *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{ua, ub}; });
-          }
         } else {
 #pragma unroll
-          for (int a = 0; a < A; ++a) {
-            double e = 0.;
-#pragma unroll
-            for (int b = 0; b < A; ++b) e += sub(a * A + b) * f[b];
-            AT(s.E, cpt, r, a) = e;
-          }
-#pragma unroll
           for (int a = 0; a < A; ++a) f[a] /= fmax;
-#pragma unroll
-          for (int l = 0; l < A; ++l) {
-            double ur = 0.;
-#pragma unroll
-            for (int b = 0; b < A; ++b) ur += ir(l * A + b) * f[b];
-            BS(cpt, r, 0, l) = ur;
-          }
         }
+        mat_vec_store<TA, LM, false>(Linv, cmat(invg), A, f, basis(at, 0));
         if (parts == 4)
           for (int l = 0; l < A; ++l) {
             double ui = 0.;
 #pragma unroll
             for (int b = 0; b < A; ++b) ui += ii[l * A + b] * f[b];
-            BS(cpt, r, 2, l) = ui;
+            sp_at(basis(at, 2), l) = ui;
           }
       }
       sh_ll[cpt * 64 + lane] = cpt_ll;
     }
     __syncthreads();
-    for (int cpt = 0; cpt < C; ++cpt) cll = lse(cll, m.log_cpt_weight[cpt] + sh_ll[cpt * 64 + lane], lse_tab);
+    const double cll = combine_components(sh_ll, m.log_cpt_weight, C, lane, lse_tab);
     if (wave == 0 && busy) col_log_like[col] = cll;
     // ---- root-to-tip (src/sumprod.cpp:163-198); D of every branch in the eigen basis on the way (src/sumprod.cpp:341-360) ----
     for (int cpt = wave; cpt < C; cpt += Wb) {
       CMat ins = cmat(m.ins_prob + cpt * A);
       if (LM && C > Wb) {                            // (with a wave per component the eigenvectors are still there)
-        wave_sync();
-        for (int k = lane; k < AA; k += 64) {
-          if constexpr (TA != 0 && TA % 2 == 0) Lvec[(k % A) * A + k / A] = m.evec_re[(long long)cpt * AA + k];
-          else Lvec[k] = m.evec_re[(long long)cpt * AA + k];
-        }
+        wave_lds_sync();
+        lds_stage<sp_rows<TA>>(Lvec, m.evec_re + (long long)cpt * AA, A, lane);
       }
       for (int r = N - 1; r >= 0; --r) {
         if (LM && m.parent[r] >= 0) {
-          wave_sync();
-          for (int k = lane; k < AA; k += 64) {
-            if constexpr (TA != 0 && TA % 2 == 0) Lsub[(k % A) * A + k / A] = m.branch_sub[((long long)cpt * N + r) * AA + k];
-            else Lsub[k] = m.branch_sub[((long long)cpt * N + r) * AA + k];
-          }
-          wave_sync();
+          wave_lds_sync();
+          lds_stage<sp_rows<TA>>(Lsub, m.branch_sub + ((long long)cpt * N + r) * AA, A, lane);
+          wave_lds_sync();
         }
         if (!busy) continue;
+        const long long at = blk.node(cpt, r);
         if (t[r] == -2 || r == root) {
           if (r == root) {
-            put_row(EROW(s.G, cpt, r), [&](const int a) { return ins[a]; });
-            LG(s.logG, cpt, r) = 0.;
-            put_row(BROW(cpt, r, 0), [](int) { return 0.; });         // no branch above the root: U was not written on the way up
+            put_row<TA>(blk.row(s.G, at), A, [&](const int a) { return ins[a]; });
+            blk.lg(s.logG, at) = 0.;
+            put_row<TA>(basis(at, 0), A, [](int) { return 0.; });         // no branch above the root: U was not written on the way up
             if (parts == 4)
-              for (int l = 0; l < A; ++l) BS(cpt, r, 2, l) = 0.;
+              for (int l = 0; l < A; ++l) sp_at(basis(at, 2), l) = 0.;
           }
-          put_row(BROW(cpt, r, 1), [](int) { return 0.; });
+          put_row<TA>(basis(at, 1), A, [](int) { return 0.; });
           if (parts == 4)
-            for (int l = 0; l < A; ++l) BS(cpt, r, 3, l) = 0.;
+            for (int l = 0; l < A; ++l) sp_at(basis(at, 3), l) = 0.;
           continue;
         }
         const int p = m.parent[r];
         const int sib = m.child[2 * p] == r ? m.child[2 * p + 1] : m.child[2 * p];
-        const double le_sib = sib >= 0 ? LG(s.logE, cpt, sib) : 0.;
-        const double lg_p = LG(s.logG, cpt, p);
-        LG(s.logG, cpt, r) = lg_p + le_sib;
+        const long long atp = blk.node(cpt, p), ats = blk.node(cpt, sib);
+        const double le_sib = sib >= 0 ? blk.lg(s.logE, ats) : 0.;
+        const double lg_p = blk.lg(s.logG, atp);
+        blk.lg(s.logG, at) = lg_p + le_sib;
+        // (the matrices' addresses are formed here, per node: formed once per component, above the loop over the nodes, they
+        // cost the A = 4 form ten registers and its third wave per SIMD)
         CMat sub_s = cmat(m.branch_sub + ((long long)cpt * N + r) * AA);
         CMat vr_s = cmat(m.evec_re + (long long)cpt * AA);
         CMat vi = cmat(m.evec_im + (long long)cpt * AA);
-        auto sub = [&](const int k) -> double { return LM ? Lsub[k] : sub_s[k]; };
-        auto vr = [&](const int k) -> double { return LM ? Lvec[k] : vr_s[k]; };
         // what flows down the branch: the parent's outside message times the sibling's subtree
         double d[AX];
-        double max_d = 0.;
-        {
-          double es[AX];
-#pragma unroll
-          for (int a = 0; a < A; ++a) es[a] = 1.;
-          get_row(EROW(s.G, cpt, p), d);
-          if (sib >= 0) get_row(EROW(s.E, cpt, sib), es);
-#pragma unroll
-          for (int a = 0; a < A; ++a) {
-            d[a] *= es[a];
-            max_d = d[a] > max_d ? d[a] : max_d;
-          }
-        }
-        if constexpr (LM && TA != 0 && TA % 2 == 0) {
-          double* rp = EROW(s.G, cpt, r);
-          lds_mat_vec<AX>(Lsub, d, [&](const int q, const double ga, const double gb) { *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{ga, gb}; });
-        } else {
-#pragma unroll
-          for (int b = 0; b < A; ++b) {
-            double g = 0.;
-#pragma unroll
-            for (int a = 0; a < A; ++a) g += d[a] * sub(a * A + b);
-            AT(s.G, cpt, r, b) = g;
-          }
-        }
-        const double norm = exp(cll - m.log_cpt_weight[cpt] - LG(s.logF, cpt, r) - lg_p - le_sib) / (LG(s.maxU, cpt, r) * max_d);
+        const double max_d = row_product<TA>(true, blk.row(s.G, atp), sib >= 0, blk.row(s.E, ats), A, d);
+        mat_vec_store<TA, LM, true>(Lsub, sub_s, A, d, blk.row(s.G, at));
+        const double norm = exp(cll - m.log_cpt_weight[cpt] - blk.lg(s.logF, at) - lg_p - le_sib) / (blk.lg(s.maxU, at) * max_d);
         const double scale = w / norm;
-        if constexpr (LM && TA != 0 && TA % 2 == 0) {
+        // D = (d / max d) evec, weighted
+        if constexpr (LM && sp_rows<TA>) {
           const double inv_max = 1. / max_d;
 #pragma unroll
           for (int a = 0; a < A; ++a) d[a] *= inv_max;
-          double* rp = BROW(cpt, r, 1);
-          lds_mat_vec<AX>(Lvec, d, [&](const int q, const double da, const double db) { *reinterpret_cast<sp_d2*>(rp + q * 128) = sp_d2{da * scale, db * scale}; });
         } else {
 #pragma unroll
           for (int a = 0; a < A; ++a) d[a] /= max_d;
-#pragma unroll
-          for (int k = 0; k < A; ++k) {
-            double dr = 0.;
-#pragma unroll
-            for (int a = 0; a < A; ++a) dr += vr(a * A + k) * d[a];
-            BS(cpt, r, 1, k) = dr * scale;
-          }
         }
+        mat_vec_store<TA, LM, true>(Lvec, vr_s, A, d, basis(at, 1), [&](int, const double dr) { return dr * scale; });
         if (parts == 4)
           for (int k = 0; k < A; ++k) {
             double di = 0.;
 #pragma unroll
             for (int a = 0; a < A; ++a) di += vi[a * A + k] * d[a];
-            BS(cpt, r, 3, k) = di * scale;
+            sp_at(basis(at, 3), k) = di * scale;
           }
       }
     }
@@ -361,26 +242,20 @@ __global__ void __launch_bounds__(512, HX_SP_WAVES_PER_SIMD) k_sumprod_columns(c
       for (int a = 0; a < A; ++a) {
         double lp = HX_NEG_INF;
         if (root >= 0)
-          for (int cpt = 0; cpt < C; ++cpt)
-            lp = lse(lp, m.log_cpt_weight[cpt] + LG(s.logF, cpt, root) + log(FR(cpt, a)) + LG(s.logG, cpt, root) +
-                             log(AT(s.G, cpt, root, a)) - cll, lse_tab);
+          for (int cpt = 0; cpt < C; ++cpt) {
+            const long long at = blk.node(cpt, root);
+            lp = lse(lp, m.log_cpt_weight[cpt] + blk.lg(s.logF, at) + log(froot(cpt, a)) + blk.lg(s.logG, at) + log(sp_at(blk.row(s.G, at), a)) - cll, lse_tab);
+          }
         root_post[col * A + a] = lp < 0. ? lp : 0.;
       }
     // ---- this column's terms of the root counts (src/sumprod.cpp:264-271) ----
     for (int cpt = wave; cpt < C && busy; cpt += Wb) {
-      const double norm = root >= 0 ? exp(m.log_cpt_weight[cpt] + LG(s.logF, cpt, root) - cll) : 0.;
+      const double norm = root >= 0 ? exp(m.log_cpt_weight[cpt] + blk.lg(s.logF, blk.node(cpt, root)) - cll) : 0.;
       for (int a = 0; a < A; ++a)
-        s.rootc[((cb * C + cpt) * A + a) * 64 + cl] = root >= 0 ? w * m.ins_prob[cpt * A + a] * FR(cpt, a) * norm : 0.;
+        s.rootc[((blk.cb * C + cpt) * A + a) * 64 + lane] = root >= 0 ? w * m.ins_prob[cpt * A + a] * froot(cpt, a) * norm : 0.;
     }
     __syncthreads();
   }
-#undef AT
-#undef ROWP
-#undef EROW
-#undef BROW
-#undef LG
-#undef BS
-#undef FR
 }
 
 // eigenCounts[cpt][k][l] += J[cpt][node][k][l] * sum over this chunk's columns of D_k(col) U_l(col)   (src/sumprod.cpp:361-370)
@@ -566,8 +441,6 @@ __global__ void __launch_bounds__(256) k_row_sums(const double* __restrict__ row
   if (threadIdx.x == 0) atomicAdd(&out[blockIdx.x], part[0]);
 }
 
-typedef SpBuf Buf;
-
 }  // namespace
 
 thread_local float g_sp_ms = 0.f;
@@ -583,81 +456,46 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
                        double* root_counts, double* eigen_re, double* eigen_im, double* root_post, void* stream) {
   if (!hm || !tokens || n_cols <= 0 || !col_log_like || !root_counts || !eigen_re || !eigen_im)
     return api_fail(HX_ERR_INVALID_ARG, "hx_sumprod_columns: null argument or no columns");
+  const char* fn = "hx_sumprod_columns";
   const int A = hm->alph_size, C = hm->components, N = hm->n_nodes, AA = A * A;
-  if (A <= 0 || C <= 0 || N <= 0 || !hm->parent || !hm->ins_prob || !hm->log_cpt_weight || !hm->branch_sub || !hm->evec_re || !hm->evec_im ||
-      !hm->evec_inv_re || !hm->evec_inv_im || !hm->esc_re || !hm->esc_im)
-    return api_fail(HX_ERR_INVALID_ARG, "hx_sumprod_columns: incomplete model");
-  if (AA > 256 * HX_SP_PAIRS) return api_fail(HX_ERR_INVALID_ARG, "hx_sumprod_columns: alphabets of more than 64 symbols are not supported");
-  if (C > 128) return api_fail(HX_ERR_INVALID_ARG, "hx_sumprod_columns: more than 128 mixture components are not supported");
+  const bool complete = A > 0 && C > 0 && N > 0 && hm->parent && hm->ins_prob && hm->log_cpt_weight && hm->branch_sub && hm->evec_re && hm->evec_im &&
+                        hm->evec_inv_re && hm->evec_inv_im && hm->esc_re && hm->esc_im;
   int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return api_fail(HX_ERR_NO_DEVICE, "no HIP device");
-  const double* lse_tab = device_lse_table(device);
-  if (!lse_tab) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_init has not been called for the current device");
-  // children from parents; binary, children before parents
-  std::vector<int> child(2 * (size_t)N, -1);
-  for (int r = 0; r < N; ++r) {
-    const int p = hm->parent[r];
-    if (p < 0) continue;
-    if (p <= r || p >= N) return api_fail(HX_ERR_NOT_TOPOSORTED, "hx_sumprod_columns: a node precedes its child");
-    if (child[2 * p] < 0) child[2 * p] = r;
-    else if (child[2 * p + 1] < 0) child[2 * p + 1] = r;
-    else return api_fail(HX_ERR_INVALID_ARG, "hx_sumprod_columns: a node has more than two children");
-  }
-  // tokens index the alphabet on the device: refuse anything else here, not with a fault there
-  for (int64_t k = 0; k < n_cols * N; ++k)
-    if (tokens[k] < -2 || tokens[k] >= A) return api_fail(HX_ERR_RANGE, "hx_sumprod_columns: a token outside -2 .. alphabet size - 1");
+  const double* lse_tab = nullptr;
+  std::vector<int> child;
+  if (int rc = sp_check_model(fn, complete, A, C, HX_ERR_INVALID_ARG, &device, &lse_tab)) return rc;
+  if (int rc = sp_children(fn, hm->parent, N, false, HX_ERR_INVALID_ARG, child)) return rc;
+  if (int rc = sp_check_tokens(fn, tokens, n_cols * N, A)) return rc;
   bool real_basis = true;
   for (size_t k = 0; k < (size_t)C * AA && real_basis; ++k) real_basis = hm->evec_im[k] == 0. && hm->evec_inv_im[k] == 0.;
   for (size_t k = 0; k < (size_t)C * N * AA && real_basis; ++k) real_basis = hm->esc_im[k] == 0.;
   const int parts = real_basis ? 2 : 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  Buf b_int, b_dbl, b_tok, b_w, b_scr, b_out;
-  const size_t dbls = (size_t)C * A + C + (size_t)C * N * AA + 4 * (size_t)C * AA + 2 * (size_t)C * N * AA;
-  if (hipMalloc(&b_int.p, 3 * (size_t)N * sizeof(int)) != hipSuccess || hipMalloc(&b_dbl.p, dbls * sizeof(double)) != hipSuccess ||
-      hipMalloc(&b_tok.p, (size_t)n_cols * N) != hipSuccess)
-    return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_sumprod_columns: device allocation failed");
-  int* d_int = static_cast<int*>(b_int.p);
-#define UP(dst, src, n) if (hipMemcpy(dst, src, (n), hipMemcpyHostToDevice) != hipSuccess) return api_fail(HX_ERR_HIP, "hx_sumprod_columns: copy failed")
-  UP(d_int, hm->parent, N * sizeof(int));
-  UP(d_int + N, child.data(), 2 * N * sizeof(int));
+  SpUpload up;
+  SpBuf b_tok, b_w, b_scr, b_out;
+  const size_t eig = SpUpload::room((size_t)C * AA * sizeof(double)), esc = SpUpload::room((size_t)C * N * AA * sizeof(double));
+  if (!up.alloc(sp_tree_room(A, C, N, true) + 4 * eig + 2 * esc) || hipMalloc(&b_tok.p, (size_t)n_cols * N) != hipSuccess ||
+      (weight && hipMalloc(&b_w.p, n_cols * sizeof(double)) != hipSuccess))
+    return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+  const SpTree tr = sp_put_tree(up, A, C, N, hm->parent, child, hm->ins_prob, hm->log_cpt_weight, hm->branch_sub);
   SpModel m;
-  m.A = A; m.C = C; m.N = N; m.real_basis = real_basis; m.parent = d_int; m.child = d_int + N;
-  double* q = static_cast<double*>(b_dbl.p);
-  bool copied = true;
-  auto put = [&](const double* src, size_t n) -> const double* {
-    double* at = q;
-    q += n;
-    copied = copied && hipMemcpy(at, src, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    return at;
-  };
-  m.ins_prob = put(hm->ins_prob, (size_t)C * A);
-  m.log_cpt_weight = put(hm->log_cpt_weight, C);
-  m.branch_sub = put(hm->branch_sub, (size_t)C * N * AA);
-  m.evec_re = put(hm->evec_re, (size_t)C * AA);
-  m.evec_im = put(hm->evec_im, (size_t)C * AA);
-  m.einv_re = put(hm->evec_inv_re, (size_t)C * AA);
-  m.einv_im = put(hm->evec_inv_im, (size_t)C * AA);
-  m.esc_re = put(hm->esc_re, (size_t)C * N * AA);
-  m.esc_im = put(hm->esc_im, (size_t)C * N * AA);
-  if (!copied) return api_fail(HX_ERR_HIP, "hx_sumprod_columns: copy failed");
-  UP(b_tok.p, tokens, (size_t)n_cols * N);
-  if (weight) {
-    if (hipMalloc(&b_w.p, n_cols * sizeof(double)) != hipSuccess) return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_sumprod_columns: device allocation failed");
-    UP(b_w.p, weight, n_cols * sizeof(double));
-  }
-#undef UP
-  // columns per chunk: the scratch of a chunk stays within the budget (HX_SUMPROD_SCRATCH_MB, default 16 GiB)
+  m.A = A; m.C = C; m.N = N; m.real_basis = real_basis; m.parent = tr.parent; m.child = tr.child;
+  m.ins_prob = tr.ins_prob; m.log_cpt_weight = tr.log_cpt_weight; m.branch_sub = tr.branch_sub;
+  m.evec_re = up.put(hm->evec_re, (size_t)C * AA);
+  m.evec_im = up.put(hm->evec_im, (size_t)C * AA);
+  m.einv_re = up.put(hm->evec_inv_re, (size_t)C * AA);
+  m.einv_im = up.put(hm->evec_inv_im, (size_t)C * AA);
+  m.esc_re = up.put(hm->esc_re, (size_t)C * N * AA);
+  m.esc_im = up.put(hm->esc_im, (size_t)C * N * AA);
+  if (!up.copied || hipMemcpy(b_tok.p, tokens, (size_t)n_cols * N, hipMemcpyHostToDevice) != hipSuccess ||
+      (weight && hipMemcpy(b_w.p, weight, n_cols * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
+    return sp_fail(HX_ERR_HIP, fn, "copy failed");
   const int AP = (A + 1) & ~1;                     // message vectors are stored in pairs of entries
   const size_t per_col = (2 + (size_t)parts) * C * N * AP + 4 * (size_t)C * N + 2 * (size_t)C * A;
-  size_t budget = (size_t)16 << 30;
-  if (const char* e = getenv("HX_SUMPROD_SCRATCH_MB")) budget = (size_t)atoll(e) << 20;
-  long long chunk = (long long)(budget / (per_col * sizeof(double)));
-  chunk &= ~63LL;                                   // whole blocks of 64 columns
-  if (chunk < 64) chunk = 64;
-  if (chunk > n_cols) chunk = n_cols;
+  const long long chunk = sp_chunk(per_col, n_cols);
   const size_t n_out = (size_t)n_cols * (1 + (root_post ? A : 0)) + (size_t)C * A + 2 * (size_t)C * AA;
   if (hipMalloc(&b_scr.p, per_col * (((size_t)chunk + 63) & ~(size_t)63) * sizeof(double)) != hipSuccess || hipMalloc(&b_out.p, n_out * sizeof(double)) != hipSuccess)
-    return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_sumprod_columns: device allocation failed");
+    return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
   double* out = static_cast<double*>(b_out.p);
   double* d_cll = out;
   double* d_post = root_post ? out + n_cols : nullptr;
@@ -665,16 +503,13 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
   double* d_re = d_root + (size_t)C * A;
   double* d_im = d_re + (size_t)C * AA;
   if (hipMemsetAsync(d_root, 0, ((size_t)C * A + 2 * (size_t)C * AA) * sizeof(double), st) != hipSuccess)
-    return api_fail(HX_ERR_HIP, "hx_sumprod_columns: HIP call failed");
+    return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
   const size_t lds = sizeof(double) * (size_t)parts * A * (HX_SP_TILE + 1);
-  if (lds > HX_LDS_LIMIT) return api_fail(HX_ERR_INVALID_ARG, "hx_sumprod_columns: basis tile exceeds the LDS of a CU");
-  struct Events {                                   // destroyed on every way out
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } ev;
-  if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return api_fail(HX_ERR_HIP, "hx_sumprod_columns: HIP call failed");
-  const hipEvent_t e0 = ev.a, e1 = ev.b;
-  (void)hipEventRecord(e0, st);
+  if (lds > HX_LDS_LIMIT) return sp_fail(HX_ERR_INVALID_ARG, fn, "basis tile exceeds the LDS of a CU");
+  const SpPlan plan = sp_column_plan(A, C, 3, false);           // exp(R t), evecInv, evec
+  SpEvents ev;
+  if (!ev.create()) return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
+  (void)hipEventRecord(ev.a, st);
   for (long long first = 0; first < n_cols; first += chunk) {
     const long long nc = n_cols - first < chunk ? n_cols - first : chunk;
     double* scr = static_cast<double*>(b_scr.p);
@@ -686,21 +521,16 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
     s.Froot = s.maxU + lg;
     s.rootc = s.Froot + (size_t)C * A * nc64;
     s.basis = s.rootc + (size_t)C * A * nc64;
-    const int tpb = 64 * (C < 8 ? C : 8);            // a wave per mixture component, up to eight
     long long blocks = (nc + 63) / 64;
     if (blocks > 65535) blocks = 65535;
-    const size_t ll_lds = sizeof(double) * 64 * (size_t)C;
     const signed char* d_tok = static_cast<const signed char*>(b_tok.p) + first * N;
     const double* d_w = b_w.p ? static_cast<const double*>(b_w.p) + first : nullptr;
     double* d_p = d_post ? d_post + first * A : nullptr;
-    const size_t mat_lds = sizeof(double) * 3 * (size_t)AA * (tpb / 64);
-    const bool lm = ll_lds + mat_lds <= 96 * 1024;
-    const size_t col_lds = ll_lds + (lm ? mat_lds : 0);
-#define HX_SP_GO(TA_, LM_) hipLaunchKernelGGL((k_sumprod_columns<TA_, LM_>), dim3((unsigned)blocks), dim3(tpb), col_lds, st, m, d_tok, d_w, nc, s, lse_tab, d_cll + first, d_p)
+#define HX_SP_GO(TA_, LM_) hipLaunchKernelGGL((k_sumprod_columns<TA_, LM_>), dim3((unsigned)blocks), dim3(64 * plan.waves), plan.lds, st, m, d_tok, d_w, nc, s, lse_tab, d_cll + first, d_p)
     // (A = 4 has its matrices in LDS whatever C <= 128: 512 C + 24 * 16 * min(C, 8) <= 65536 + 3072 < 98304 - no <4, false> form)
     if (A == 4) HX_SP_GO(4, true);
-    else if (A == 20) { if (lm) HX_SP_GO(20, true); else HX_SP_GO(20, false); }
-    else { if (lm) HX_SP_GO(0, true); else HX_SP_GO(0, false); }
+    else if (A == 20) { if (plan.lm) HX_SP_GO(20, true); else HX_SP_GO(20, false); }
+    else { if (plan.lm) HX_SP_GO(0, true); else HX_SP_GO(0, false); }
 #undef HX_SP_GO
     const long long tiles = (nc + HX_SP_TILE - 1) / HX_SP_TILE;
     long long slices = 4096 / ((long long)C * N) + 1;
@@ -729,18 +559,13 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
       hipLaunchKernelGGL(k_row_sums, dim3((unsigned)(C * A), (unsigned)rs), dim3(256), 0, st, s.rootc, nc, d_root);
     }
   }
-  (void)hipEventRecord(e1, st);
-  int rc = HX_OK;
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = HX_ERR_HIP;
-  if (rc == HX_OK) (void)hipEventElapsedTime(&g_sp_ms, e0, e1);
-  if (rc != HX_OK) return api_fail(rc, "hx_sumprod_columns: kernel launch or execution failed");
-#define DOWN(dst, src, n) if (hipMemcpy(dst, src, (n) * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return api_fail(HX_ERR_HIP, "hx_sumprod_columns: copy failed")
-  DOWN(col_log_like, d_cll, (size_t)n_cols);
-  if (root_post) DOWN(root_post, d_post, (size_t)n_cols * A);
-  DOWN(root_counts, d_root, (size_t)C * A);
-  DOWN(eigen_re, d_re, (size_t)C * AA);
-  DOWN(eigen_im, d_im, (size_t)C * AA);
-#undef DOWN
+  (void)hipEventRecord(ev.b, st);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
+  (void)hipEventElapsedTime(&g_sp_ms, ev.a, ev.b);
+  auto down = [](double* dst, const double* src, const size_t n) { return hipMemcpy(dst, src, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess; };
+  if (!down(col_log_like, d_cll, (size_t)n_cols) || (root_post && !down(root_post, d_post, (size_t)n_cols * A)) || !down(root_counts, d_root, (size_t)C * A) ||
+      !down(eigen_re, d_re, (size_t)C * AA) || !down(eigen_im, d_im, (size_t)C * AA))
+    return sp_fail(HX_ERR_HIP, fn, "copy failed");
   return HX_OK;
 }
 

@@ -6,8 +6,8 @@ yardstick without a device: every case takes the launch plan it names, the resca
 proposals, the random walk covers what it is there for) and by tests/test_gpu_history_edges.py.
 
 Models, trees, columns and the 64 symbols are those of tests/sumprod_edge_cases.py; the oracle side is
-tests/test_gpu_history.py's Case.  `history_plan` restates hx_history_create's decisions (historian_amd/csrc/hx_history.hip);
-the line numbers next to it are that file's."""
+tests/test_gpu_history.py's Case.  `history_plan` restates hx_history_create's decisions (historian_amd/csrc/hx_history.hip,
+sp_column_plan in hx_sumprod.h); the names next to it are the functions and kernels it restates."""
 import copy
 import functools
 import math
@@ -23,15 +23,15 @@ from tests.test_gpu_sumprod import _random_tree
 
 def history_plan(a, c):
     """hx_history_create: the kernel, the waves of a workgroup, the components a wave takes in turn, the dynamic LDS"""
-    waves = min(c, 8)                                                    # :389
-    while waves > 1 and 512 * c + waves * 8 * a * a > 96 * 1024:         # :390 ll_lds + waves * mat_lds
+    waves = min(c, 8)                                                    # sp_column_plan: waves
+    while waves > 1 and 512 * c + waves * 8 * a * a > 96 * 1024:         # sp_column_plan(shed_waves): ll_lds + waves mat_lds
         waves -= 1
-    return dict(ta=a if a in (4, 20) else 0, waves=waves, turns=-(-c // waves),       # :324-326; :80 cpt += Wb
-                lds=512 * c + waves * 8 * a * a)                         # :391
+    return dict(ta=a if a in (4, 20) else 0, waves=waves, turns=-(-c // waves),       # history_run's launch; k_history_columns: cpt += Wb
+                lds=512 * c + waves * 8 * a * a)                         # sp_column_plan: lds
 
 
 def sum_plan(n_cols):
-    """k_history_sum (:172-184): the additions of a thread, fewest and most; the blocks of the column kernel"""
+    """k_history_sum: the additions of a thread, fewest and most; the blocks of the column kernel"""
     return dict(per_thread=(n_cols // 1024, -(-n_cols // 1024)), blocks=-(-n_cols // 64))
 
 
@@ -116,7 +116,7 @@ def case(name):
 # ---- proposals ----
 
 def walked_nodes(parent, nodes):
-    """hx_history_propose (:460-465): the changed nodes and their ancestors, ascending"""
+    """hx_history_propose: the changed nodes and their ancestors, ascending"""
     out = set()
     for r in nodes:
         while r >= 0 and r not in out:

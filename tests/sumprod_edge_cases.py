@@ -5,7 +5,8 @@ on them: the rescaling does fire, the oracle itself does not underflow, every ca
 tests/test_gpu_sumprod_edges.py and tests/test_gpu_ancestors_edges.py.
 
 `counts_plan` and `ancestors_plan` restate the launchers' decisions (hx_sumprod_columns in historian_amd/csrc/hx_sumprod.hip,
-hx_sumprod_ancestors in hx_ancestors.hip); the line numbers next to them are those launchers'.
+hx_sumprod_ancestors in hx_ancestors.hip; sp_column_plan and sp_chunk in hx_sumprod.h); the names next to them are
+the functions and kernels they restate.
 
 Alphabets of more than 36 symbols: tokenize_columns and the oracle's tokenizer fold case, and '-', '.', '*' and the
 counts columns' wildcard 'x' have meanings of their own, so the 64 symbols are the lower-case letters without 'x', the
@@ -102,29 +103,29 @@ def deep_columns(rng, parent, alphabet, n_cols, recon=False):
 def counts_plan(a, c, n, n_cols, real_basis, slices=None, no_mfma=False):
     """hx_sumprod_columns (hx_sumprod.hip): what it launches for A symbols, C components, N nodes and one chunk of columns.
     slices, no_mfma: HX_SUMPROD_SLICES, HX_SUMPROD_NO_MFMA."""
-    waves = min(c, 8)                                                    # :689 tpb = 64 min(C, 8)
-    lm = 8 * 64 * c + 8 * 3 * a * a * waves <= 96 * 1024                 # :692, :696-697 ll_lds + mat_lds
+    waves = min(c, 8)                                                    # sp_column_plan: waves
+    lm = 8 * 64 * c + 8 * 3 * a * a * waves <= 96 * 1024                 # sp_column_plan(mats = 3): ll_lds + waves mat_lds
     ap, mp = (a + 1) & ~1, (a + 15) // 16 * 16
-    plan = dict(ta=a if a in (4, 20) else 0, lm=lm, waves=waves, turns=-(-c // waves),        # :701-703; :126, :261 cpt += Wb
+    plan = dict(ta=a if a in (4, 20) else 0, lm=lm, waves=waves, turns=-(-c // waves),        # HX_SP_GO; k_sumprod_columns: cpt += Wb
                 lds=8 * 64 * c + (8 * 3 * a * a * waves if lm else 0),
-                row_slices=min(64, -(-n_cols // 4096)))                  # :727-728
-    if real_basis and 8 * 2 * mp * 65 <= 64 * 1024 and not no_mfma:      # :710
+                row_slices=min(64, -(-n_cols // 4096)))                  # k_row_sums' grid
+    if real_basis and 8 * 2 * mp * 65 <= 64 * 1024 and not no_mfma:      # k_outer_counts_mfma's condition
         blocks = -(-n_cols // 64)
-        sl = 8192 // (c * n) + 1 if slices is None else slices           # :713-716
+        sl = 8192 // (c * n) + 1 if slices is None else slices           # its slices `sl`
         sl = min(max(sl, 1), blocks)
-        plan.update(outer="matrix cores", per=1 if ap <= 4 else 5 if ap <= 20 else 16,         # :719-721
+        plan.update(outer="matrix cores", per=1 if ap <= 4 else 5 if ap <= 20 else 16,         # its PER
                     groups=sl, blocks_per_group=sorted({len(range(g, blocks, sl)) for g in range(sl)}))
     else:
-        tiles = -(-n_cols // 32)                                         # :705
-        s = 4096 // (c * n) + 1 if slices is None else slices            # :706-709
+        tiles = -(-n_cols // 32)                                         # HX_SP_TILE
+        s = 4096 // (c * n) + 1 if slices is None else slices            # k_outer_counts' `slices`
         s = min(max(s, 1), tiles)
-        plan.update(outer="vector units, real" if real_basis else "vector units, complex", pairs=-(-a * a // 256),       # :722-725; :415 q * 256 < A A
+        plan.update(outer="vector units, real" if real_basis else "vector units, complex", pairs=-(-a * a // 256),       # k_outer_counts: q * 256 < A A
                     groups=s, tiles_per_group=sorted({len(range(g, tiles, s)) for g in range(s)}))
     return plan
 
 
 def counts_chunk(a, c, n, n_cols, real_basis, mb):
-    """columns per chunk of hx_sumprod_columns under HX_SUMPROD_SCRATCH_MB = mb   (:651-657)"""
+    """columns per chunk of hx_sumprod_columns under HX_SUMPROD_SCRATCH_MB = mb   (per_col there, sp_chunk)"""
     ap, parts = (a + 1) & ~1, 2 if real_basis else 4
     per_col = 8 * ((2 + parts) * c * n * ap + 4 * c * n + 2 * c * a)
     return min(n_cols, max(64, ((mb << 20) // per_col) & ~63))
@@ -138,10 +139,10 @@ def counts_chunk_mb(a, c, n, real_basis, columns):
 
 def ancestors_plan(a, c):
     """hx_sumprod_ancestors (hx_ancestors.hip)"""
-    waves = min(c, 8)                                                    # :324
-    lm = 8 * 64 * c + 8 * a * a * waves <= 96 * 1024                     # :325-326
-    return dict(ta=a if a in (4, 20) and lm else 0, lm=lm, waves=waves, turns=-(-c // waves),      # :383-386
-                combine_waves=4 if a <= 20 else 1)                       # :328
+    waves = min(c, 8)                                                    # sp_column_plan: waves
+    lm = 8 * 64 * c + 8 * a * a * waves <= 96 * 1024                     # sp_column_plan(mats = 1)
+    return dict(ta=a if a in (4, 20) and lm else 0, lm=lm, waves=waves, turns=-(-c // waves),      # HX_AN_GO
+                combine_waves=4 if a <= 20 else 1)                       # cwaves
 
 
 # ---- the cases ----

@@ -9,7 +9,8 @@ round of the column kernel's grid, columns of gaps, a node with one child, a nod
 Against the oracle: the bounds of tests/test_gpu_history.py, unchanged (column_bound, Case.check's bound of the sum).
 Device against device, bit for bit: two histories of the same inputs; a proposal and a history created on the proposed
 matrices; the columns whose root a proposal does not walk; lp_sub and tests/history_ref.py's restatement of
-k_history_sum over the device's own column likelihoods."""
+k_history_sum over the device's own column likelihoods; the history and hx_sumprod_ancestors, which run the same way up
+(hx_sumprod.h), on the same inputs."""
 import numpy as np
 import pytest
 
@@ -292,3 +293,27 @@ def test_a_node_named_twice_is_refused_and_nothing_ran():
     new.check(*got, what="after the refusal")
     assert same(h.log_like(0), state)
     h.close()
+
+
+# ---- g. one way up: the history and hx_sumprod_ancestors on the same inputs ----
+
+@pytest.mark.parametrize("name", ["anc cat64 mix12", "anc bal64 prot4", "anc alphabet 21 x 9"])
+def test_the_history_and_the_ancestors_kernel_share_the_way_up(name):
+    """Both kernels run the tip-to-root steps of hx_sumprod.h; where their launchers pick the same form (the alphabet's
+    kernel, the matrices in LDS) the column likelihoods are the same bits, and lp_sub is their sum in k_history_sum's
+    order.  70 columns each (a ragged second block): 4 symbols x 12 components on a caterpillar of 64 leaves under
+    wildcards (two turns of a wave, rescaling), 20 x 4 on a balanced 64-leaf tree, 21 x 9 on seven leaves (the general
+    kernel, two turns).  46 x 6 and 64 x 3 are not here: there the ancestors' matrices come through the scalar cache and
+    the history sheds a wave, and the two forms add in different orders by design."""
+    s = EC.spec(name)
+    c = HE.case(name) if name in HE.HISTORY else TH.Case(s.js, s.parent, s.length, s.rows)
+    hp, ap = HE.history_plan(c.a, c.c), EC.ancestors_plan(c.a, c.c)
+    assert s.n_cols == 70 and ap["lm"] and hp["waves"] == ap["waves"] == min(c.c, 8) and hp["ta"] == ap["ta"]
+    assert hp["lds"] == 512 * c.c + 8 * c.a * c.a * min(c.c, 8)       # every wave's matrix in LDS, as lm says of the ancestors' plan
+    h = c.history()
+    lp, cll = h.log_like()
+    h.close()
+    got = capi.sumprod_ancestors(c.parent, c.ins_prob, c.log_cpt_weight, c.branch_sub, c.tokens)[0]
+    differ = np.flatnonzero(cll != got)
+    assert cll.tobytes() == got.tobytes(), "first differing column %d: %r, %r" % (differ[0], cll[differ[0]], got[differ[0]])
+    assert lp == HR.history_sum(got)
