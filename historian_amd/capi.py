@@ -119,7 +119,9 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_branch_batch_last_walk_ms", "hx_sibling_batch_last_walk_ms",
            "hx_distance_matrix", "hx_distance_neg_log_like", "hx_distance_last_kernel_ms", "hx_distance_last_products",
            "hx_history_create", "hx_history_destroy", "hx_history_propose", "hx_history_accept", "hx_history_reject",
-           "hx_history_log_like", "hx_history_indel_counts", "hx_history_last_kernel_ms"]
+           "hx_history_log_like", "hx_history_indel_counts", "hx_history_last_kernel_ms", "hx_history_set_rates",
+           "hx_history_propose_lengths", "hx_history_create_from_lengths", "hx_history_branch_matrix", "hx_expm_shape",
+           "hx_history_last_expm_ms"]
 
 
 class HxError(RuntimeError):
@@ -219,6 +221,12 @@ def load():
     lib.hx_history_log_like.argtypes = [vp, C.c_int32, _f64p, _f64p]
     lib.hx_history_indel_counts.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.hx_history_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hx_history_set_rates.argtypes = [vp, _f64p]
+    lib.hx_history_last_expm_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hx_history_propose_lengths.argtypes = [vp, C.c_int32, _i32p, _f64p, _f64p, vp]
+    lib.hx_history_create_from_lengths.argtypes = [C.POINTER(HxHistoryModel), C.POINTER(C.c_int8), C.c_int64, _f64p, _f64p, vp, C.POINTER(vp)]
+    lib.hx_history_branch_matrix.argtypes = [vp, C.c_int32, C.c_int32, _f64p]
+    lib.hx_expm_shape.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p]
     lib.hx_batch_read_matrix_async.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
     lib.hx_batch_indel_counts.argtypes = [vp, C.c_int32, _f64p, _f64p]
@@ -882,9 +890,36 @@ def sumprod_ancestors(parent, ins_prob, log_cpt_weight, branch_sub, tokens, want
 class History:
     """hx_history_*: a fixed alignment on a tree whose branch lengths change, resident on the device.  parent [N]; ins_prob
     [C][A]; log_cpt_weight [C]; tokens [n_cols][N] int8 (-1 wildcard, -2 gap); branch_sub [C][N][A][A].  Creating it
-    evaluates every column (on `stream`; the call returns when that is done)."""
+    evaluates every column (on `stream`; the call returns when that is done).  History.from_lengths takes the rate matrices
+    [C][A][A] and the branch lengths [N] instead of branch_sub: exp(R t) is then computed on the device, there and in every
+    propose_lengths."""
 
     def __init__(self, parent, ins_prob, log_cpt_weight, tokens, branch_sub, stream=None):
+        m, tokens = self._model(parent, ins_prob, log_cpt_weight, tokens)
+        branch_sub = np.ascontiguousarray(branch_sub, dtype=np.float64)
+        if branch_sub.shape != (self.c, self.n, self.a, self.a):
+            raise ValueError("branch_sub must be [C][N][A][A]")
+        h = C.c_void_p()
+        _check(load().hx_history_create(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), self.n_cols, _p(branch_sub, _f64p),
+                                        C.c_void_p(stream or 0), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_lengths(cls, parent, ins_prob, log_cpt_weight, tokens, rate, lengths, stream=None):
+        """hx_history_create_from_lengths: rate [C][A][A]; lengths [N] (the root's is not read)"""
+        self = cls.__new__(cls)
+        m, tokens = self._model(parent, ins_prob, log_cpt_weight, tokens)
+        rate, lengths = self._rate_array(rate), np.ascontiguousarray(lengths, dtype=np.float64)
+        if lengths.shape != (self.n,):
+            raise ValueError("lengths must be [N]")
+        h = C.c_void_p()
+        _check(load().hx_history_create_from_lengths(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), self.n_cols, _p(rate, _f64p),
+                                                     _p(lengths, _f64p), C.c_void_p(stream or 0), C.byref(h)))
+        self._h = h
+        return self
+
+    def _model(self, parent, ins_prob, log_cpt_weight, tokens):
+        """the sizes of the history, the model as the C ABI takes it (it points into self._keep) and the tokens"""
         self._h = None
         ins_prob = np.ascontiguousarray(ins_prob, dtype=np.float64)
         self.c, self.a = ins_prob.shape
@@ -895,16 +930,39 @@ class History:
             raise ValueError("tokens must be [n_cols][n_nodes]")
         self.n_cols = tokens.shape[0]
         log_cpt_weight = np.ascontiguousarray(log_cpt_weight, dtype=np.float64)
-        branch_sub = np.ascontiguousarray(branch_sub, dtype=np.float64)
-        if log_cpt_weight.shape != (self.c,) or branch_sub.shape != (self.c, self.n, self.a, self.a):
-            raise ValueError("log_cpt_weight must be [C] and branch_sub [C][N][A][A]")
+        if log_cpt_weight.shape != (self.c,):
+            raise ValueError("log_cpt_weight must be [C]")
         m = HxHistoryModel()
         m.alph_size, m.components, m.n_nodes = self.a, self.c, self.n
         m.parent, m.ins_prob, m.log_cpt_weight = _p(parent, _i32p), _p(ins_prob, _f64p), _p(log_cpt_weight, _f64p)
-        h = C.c_void_p()
-        _check(load().hx_history_create(C.byref(m), _p(tokens, C.POINTER(C.c_int8)), self.n_cols, _p(branch_sub, _f64p),
-                                        C.c_void_p(stream or 0), C.byref(h)))
-        self._h = h
+        self._keep = (parent, ins_prob, log_cpt_weight)           # (the arrays the model points into, alive until the call is made)
+        return m, tokens
+
+    def _rate_array(self, rate):
+        rate = np.ascontiguousarray(rate, dtype=np.float64)
+        if rate.shape != (self.c, self.a, self.a):
+            raise ValueError("rate must be [C][A][A]")
+        return rate
+
+    def set_rates(self, rate):
+        """rate [C][A][A]: what propose_lengths takes exp(R t) of from now on"""
+        _check(load().hx_history_set_rates(self._h, _p(self._rate_array(rate), _f64p)))
+
+    def propose_lengths(self, nodes, lengths, stream=None):
+        """nodes [n_changed]; lengths [n_changed] -> the proposed sum of the column log-likelihoods"""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.float64)
+        if nodes.ndim != 1 or lengths.shape != nodes.shape:
+            raise ValueError("lengths must be [n_changed]")
+        lp = C.c_double()
+        _check(load().hx_history_propose_lengths(self._h, nodes.size, _p(nodes, _i32p), _p(lengths, _f64p), C.byref(lp), C.c_void_p(stream or 0)))
+        return lp.value
+
+    def branch_matrix(self, node, which=0):
+        """[C][A][A]: exp(R t) of the node's branch in the current state (0) or in the pending proposal (1)"""
+        out = np.empty((self.c, self.a, self.a))
+        _check(load().hx_history_branch_matrix(self._h, which, node, _p(out, _f64p)))
+        return out
 
     def close(self):
         if self._h is not None:
@@ -950,6 +1008,19 @@ class History:
         ms = C.c_float()
         _check(load().hx_history_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def expm_ms(self):
+        """k_branch_expm's share of kernel_ms() (0 when the last evaluation brought its matrices)"""
+        ms = C.c_float()
+        _check(load().hx_history_last_expm_ms(self._h, C.byref(ms)))
+        return ms.value
+
+
+def expm_shape(max_abs_rate, t):
+    """hx_expm_shape (host only): (terms, squarings, shrink) of the series of exp(R t), max |R_ij| = max_abs_rate"""
+    terms, squarings, shrink = C.c_int32(), C.c_int32(), C.c_double()
+    _check(load().hx_expm_shape(max_abs_rate, t, C.byref(terms), C.byref(squarings), C.byref(shrink)))
+    return terms.value, squarings.value, shrink.value
 
 
 def sumprod_kernel_ms():

@@ -5,7 +5,10 @@
 // Host code: the prior, the root term, pairPath and the indel term added in path order (the reference's bits), the moves'
 // tree arithmetic and their draws from std::mt19937.  Device: the substitution term.  The current history is resident
 // there (hx_history.hip through hx_history_*); a move proposes the branches it changed, and sample() accepts or rejects.
-// exp(R t) of a branch is ProbModel(model, t).subMat, as in SumProduct's constructor (src/sumprod.cpp:37-43).
+// exp(R t) of a branch is ProbModel(model, t).subMat, as in SumProduct's constructor (src/sumprod.cpp:37-43): the history
+// takes the rate matrices once and computes it on the device from the branch lengths (hx_history_create_from_lengths,
+// hx_history_propose_lengths), bit for bit RateModel::getSubProbMatrix; HX_HISTORY_HOST_EXPM=1 computes it with
+// getSubProbMatrix on the host and uploads the matrices (hx_history_create, hx_history_propose) - the same output.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -178,6 +181,11 @@ void flatMatrices(const RateModel& model, double t, double* out) {           // 
       for (size_t j = 0; j < A; ++j) out[(c * A + i) * A + j] = sub[c][i][j];
 }
 
+bool hostExpm() {
+  const char* e = getenv("HX_HISTORY_HOST_EXPM");
+  return e && atoi(e) != 0;
+}
+
 }  // namespace
 
 LogProb TreeAlignFuncs::indelLogLikelihood(const RateModel& model, const History& history) {
@@ -198,15 +206,11 @@ hx_history* TreeAlignFuncs::residentHistory(const RateModel& model, const Histor
     }
   }
   vguard<int32_t> parent(N);
-  vguard<double> insProb(C * A), logCptWeight(C), branchSub(C * N * A * A, 0.), one(C * A * A);
+  vguard<double> insProb(C * A), logCptWeight(C);
   for (size_t r = 0; r < N; ++r) parent[r] = (int32_t)tree.parent[r];
   for (size_t c = 0; c < C; ++c) {
     logCptWeight[c] = log(model.cptWeight[c]);
     for (size_t i = 0; i < A; ++i) insProb[c * A + i] = model.insProb[c][i];
-  }
-  for (size_t r = 0; r + 1 < N; ++r) {
-    flatMatrices(model, tree.branchLength((TreeNodeIndex)r), one.data());
-    for (size_t c = 0; c < C; ++c) std::copy(one.begin() + c * A * A, one.begin() + (c + 1) * A * A, branchSub.begin() + (c * N + r) * A * A);
   }
   hx_history_model m = {};
   m.alph_size = (int32_t)A;
@@ -217,7 +221,21 @@ hx_history* TreeAlignFuncs::residentHistory(const RateModel& model, const Histor
   m.log_cpt_weight = logCptWeight.data();
   hx_history* h = nullptr;
   detail::ensureDevice();
-  detail::check(hx_history_create(&m, tokens.data(), (int64_t)cols, branchSub.data(), nullptr, &h), "hx_history_create");
+  if (hostExpm()) {
+    vguard<double> branchSub(C * N * A * A, 0.), one(C * A * A);
+    for (size_t r = 0; r + 1 < N; ++r) {
+      flatMatrices(model, tree.branchLength((TreeNodeIndex)r), one.data());
+      for (size_t c = 0; c < C; ++c) std::copy(one.begin() + c * A * A, one.begin() + (c + 1) * A * A, branchSub.begin() + (c * N + r) * A * A);
+    }
+    detail::check(hx_history_create(&m, tokens.data(), (int64_t)cols, branchSub.data(), nullptr, &h), "hx_history_create");
+    return h;
+  }
+  vguard<double> rate(C * A * A), lengths(N, 0.);
+  for (size_t c = 0; c < C; ++c)
+    for (size_t i = 0; i < A; ++i)
+      for (size_t j = 0; j < A; ++j) rate[(c * A + i) * A + j] = model.subRate[c][i][j];
+  for (size_t r = 0; r + 1 < N; ++r) lengths[r] = tree.branchLength((TreeNodeIndex)r);
+  detail::check(hx_history_create_from_lengths(&m, tokens.data(), (int64_t)cols, rate.data(), lengths.data(), nullptr, &h), "hx_history_create_from_lengths");
   return h;
 }
 
@@ -401,15 +419,19 @@ void Sampler::proposedTerms(const Move& move, LogProb terms[4]) const {
   const History& h = move.newHistory;
   const size_t A = model->alphabetSize(), C = (size_t)model->components(), n = move.changed.size();
   vguard<int32_t> nodes(n);
-  vguard<double> mats(n * C * A * A);
-  for (size_t k = 0; k < n; ++k) {
-    nodes[k] = (int32_t)move.changed[k];
-    flatMatrices(*model, h.tree.branchLength(move.changed[k]), &mats[k * C * A * A]);
-  }
+  for (size_t k = 0; k < n; ++k) nodes[k] = (int32_t)move.changed[k];
   terms[0] = treePrior->treeLogLikelihood(h.tree);
   terms[1] = currentTerms[1];                         // (the alignment is fixed: the root's row does not change)
   terms[2] = indelLogLikelihood(*model, h);
-  detail::check(hx_history_propose(resident.get(), (int32_t)n, nodes.data(), mats.data(), &terms[3], nullptr), "hx_history_propose");
+  if (hostExpm()) {
+    vguard<double> mats(n * C * A * A);
+    for (size_t k = 0; k < n; ++k) flatMatrices(*model, h.tree.branchLength(move.changed[k]), &mats[k * C * A * A]);
+    detail::check(hx_history_propose(resident.get(), (int32_t)n, nodes.data(), mats.data(), &terms[3], nullptr), "hx_history_propose");
+    return;
+  }
+  vguard<double> lengths(n);
+  for (size_t k = 0; k < n; ++k) lengths[k] = h.tree.branchLength(move.changed[k]);
+  detail::check(hx_history_propose_lengths(resident.get(), (int32_t)n, nodes.data(), lengths.data(), &terms[3], nullptr), "hx_history_propose_lengths");
 }
 
 void Sampler::initialize(const History& initialHistory, const string& samplerName) {

@@ -4,6 +4,7 @@
 //   hxtest seqprofile <alphabet> <sequence>        leaf Profile as JSON (Makefile:239-240)
 //   hxtest quickalign <pair.fa> <model.json> <t>   guide-alignment Viterbi of two sequences as gapped FASTA (Makefile:278-279)
 //   hxtest expm <model.json> <t>                   exp(R t) of every mixture component as hex floats, row by row
+//   hxtest expmtime <model.json> <t> <calls>       the host clock around <calls> calls of getSubProbMatrix near t
 //   hxtest branch <pair.fa> <model.json> <t>       the two sequences as parent and child of one branch (next row N4): Viterbi
 //                                                  and Forward log-likelihoods as hex floats, then the best alignment
 //   hxtest sibling <pair.fa> <model.json> <tl> <tr> [band]   the two sequences as left and right child of an unobserved parent
@@ -82,6 +83,21 @@ int substitutionMatrix(int, char** args) {
       printf("\n");
     }
   return 0;
+}
+
+// expmtime <modelfile> <time> <calls>: the host clock around <calls> calls of getSubProbMatrix(time * (1 + k / calls)), every
+// component each; prints "expmtime <calls> <components> <ms in all>" (tools/history_bench.py's host-side figure)
+int substitutionMatrixTime(int, char** args) {
+  RateModel rates;
+  rates.readFile(args[0]);
+  const double t = atof(args[1]);
+  const int calls = atoi(args[2]);
+  double keep = 0;
+  const auto start = std::chrono::steady_clock::now();
+  for (int k = 0; k < calls; ++k) keep += rates.getSubProbMatrix(t * (1. + (double)k / calls))[0][0][0];
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - start).count();
+  printf("expmtime %d %d %.6f\n", calls, rates.components(), ms);
+  return keep > 0 ? 0 : 1;
 }
 
 int branchPair(int, char** args) {
@@ -359,6 +375,7 @@ const Command commands[] = {
     {"seqprofile", 2, 2, "<alphabet> <sequence>", leafProfileJson},
     {"quickalign", 3, 3, "<seqfile> <modelfile> <time>", guidePair},
     {"expm", 2, 2, "<modelfile> <time>", substitutionMatrix},
+    {"expmtime", 3, 3, "<modelfile> <time> <calls>", substitutionMatrixTime},
     {"branch", 3, 3, "<seqfile> <modelfile> <time>", branchPair},
     {"sibling", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", siblingPair},
     {"walks", 4, 5, "<seqfile> <modelfile> <left time> <right time> [band]", pairWalks},

@@ -13,10 +13,15 @@
 // likelihood.  A gap's message is all ones and is neither stored nor read.  The full evaluation is the proposal that walks
 // every node, so both run the same instructions on the same operands: the same bits.
 //
+// A proposal brings its new matrices (k_history_scatter puts the upload in place) or only its new branch lengths: then
+// k_branch_expm (hx_expm.hip) computes exp(R t) from the rate matrices the history was given once, straight into the idle
+// slots, with the bits of the host mirror's RateModel::getSubProbMatrix.
+//
 // k_history_sum adds the column likelihoods in one workgroup, a fixed order for a given number of columns, whatever the
 // grid of the column kernel and whichever columns were recomputed.  No atomics anywhere.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstring>
 #include <new>
 #include <vector>
 #include "../../include/historian_hip.h"
@@ -24,6 +29,7 @@
 #include "hx_policy.h"
 #include "hx_kernels.h"
 #include "hx_sumprod.h"
+#include "hx_expm.h"
 
 namespace hx {
 
@@ -210,38 +216,63 @@ struct hx_history {
   bool pending = false, have_counts = false;
   int cur = 0;                                       // which of d_cll / d_sum is current
   SpUpload model;                                    // the roots, the tree, the info words, the walk and the changed nodes, the mixture
-  SpBuf tok, mats, stage, E, logE, cll, sum, counts;
+  SpBuf tok, mats, stage, E, logE, cll, sum, counts, rate;
+  std::vector<double> max_abs;                       // [C] the largest |element| of each rate matrix; empty: no rates are set
+  ExpmPlan expm = {};                                // k_branch_expm's workgroup, made when the rates were set
   const int *d_root = nullptr, *d_child = nullptr, *d_parent = nullptr;
   int *d_walk = nullptr, *d_info = nullptr;
   const double *d_ins = nullptr, *d_lcw = nullptr;
   long long e_slot = 0, lg_slot = 0;
   int tpb = 64;
   size_t lds = 0;
-  float ms = 0.f;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  float ms = 0.f, expm_ms = 0.f;                      // of the last evaluation: all its kernels; k_branch_expm alone
+  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
   ~hx_history() {
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);
+    if (ev_c) (void)hipEventDestroy(ev_c);
   }
 };
 
 namespace {
 
 // One evaluation: the slots of this proposal to the device, the column kernel over `walked`, the sum.  Returns when done.
-// new_mats: [changed][C][A][A] on the host, or null when the matrices are in place already (the first evaluation).
-int history_run(hx_history* h, const std::vector<int>& changed, const std::vector<int>& walked, const double* new_mats, hipStream_t st, double* lp_sub) {
+// new_mats: [changed][C][A][A] on the host, or null; lengths: [changed] the new branch lengths (the root's is not read), or
+// null: the matrices are computed in place from the history's rates.  Both null: the matrices are in place already.
+int history_run(hx_history* h, const std::vector<int>& changed, const std::vector<int>& walked, const double* new_mats, const double* lengths, hipStream_t st,
+                double* lp_sub) {
   const double* lse_tab = device_lse_table(h->device);
   if (!lse_tab) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_history: hx_init has not been called for the history's device");
   const int N = h->N;
-  std::vector<int> info(N + walked.size() + (new_mats ? changed.size() : 0));
+  // the nodes whose matrix arrives: all the changed ones of an upload; of a proposal of lengths, those with a branch
+  std::vector<int> arriving;
+  if (new_mats) arriving = changed;
+  else if (lengths)
+    for (int r : changed)
+      if (r != N - 1) arriving.push_back(r);
+  // the words, then (8-byte aligned) the shape of the series of every (arriving node, component)
+  const size_t n_words = (N + walked.size() + arriving.size() + 1) & ~(size_t)1;
+  const size_t n_shapes = lengths ? arriving.size() * (size_t)h->C : 0;
+  static_assert(sizeof(ExpmShape) == 6 * sizeof(int), "ExpmShape is counted in words below and in hx_history_create");
+  std::vector<int> info(n_words + 6 * n_shapes);
   std::vector<unsigned char> is_changed(N, 0), is_walked(N, 0);
   for (int r : changed) is_changed[r] = 1;
   for (int r : walked) is_walked[r] = 1;
   for (int r = 0; r < N; ++r)
     info[r] = (is_walked[r] ? (h->eslot[r] ^ 1) : h->eslot[r]) | ((is_changed[r] ? (h->mslot[r] ^ 1) : h->mslot[r]) << 1) | (is_walked[r] << 2);
   std::copy(walked.begin(), walked.end(), info.begin() + N);
-  if (new_mats) std::copy(changed.begin(), changed.end(), info.begin() + N + walked.size());
-  // (the info words, the walk and the changed nodes are adjacent on the device: one copy; the matrices: another)
+  std::copy(arriving.begin(), arriving.end(), info.begin() + N + walked.size());
+  if (lengths) {
+    size_t q = 0;
+    for (size_t k = 0; k < changed.size(); ++k) {
+      if (changed[k] == N - 1) continue;
+      for (int cpt = 0; cpt < h->C; ++cpt, ++q) {
+        const ExpmShape s = expm_shape(h->max_abs[cpt], lengths[k]);
+        memcpy(info.data() + n_words + 6 * q, &s, sizeof s);
+      }
+    }
+  }
+  // (the info words, the walk, the arriving nodes and the shapes are adjacent on the device: one copy; the matrices: another)
   const size_t CAA = (size_t)h->C * h->A * h->A;
   if (hipMemcpy(h->d_info, info.data(), info.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
       (new_mats && hipMemcpy(h->stage.p, new_mats, changed.size() * CAA * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
@@ -261,6 +292,10 @@ int history_run(hx_history* h, const std::vector<int>& changed, const std::vecto
   const long long blocks64 = h->ncp / 64;
   const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
   (void)hipEventRecord(h->ev_a, st);
+  if (lengths && launch_branch_expm(h->expm, static_cast<const double*>(h->rate.p), reinterpret_cast<const ExpmShape*>(h->d_info + n_words), h->d_walk + walked.size(),
+                                    h->d_info, (int)arriving.size(), h->A, h->C, N, static_cast<double*>(h->mats.p), st) != 0)
+    return api_fail(HX_ERR_INVALID_ARG, launch_error());
+  if (lengths) (void)hipEventRecord(h->ev_c, st);
   if (new_mats)
     hipLaunchKernelGGL(k_history_scatter, dim3((unsigned)(changed.size() * h->C)), dim3(256), 0, st, static_cast<const double*>(h->stage.p),
                        h->d_walk + walked.size(), h->d_info, h->C, N, h->A * h->A, static_cast<double*>(h->mats.p));
@@ -272,6 +307,8 @@ int history_run(hx_history* h, const std::vector<int>& changed, const std::vecto
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_history: kernel launch or execution failed");
   (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
+  h->expm_ms = 0.f;
+  if (lengths) (void)hipEventElapsedTime(&h->expm_ms, h->ev_a, h->ev_c);
   if (lp_sub && hipMemcpy(lp_sub, sum + (h->cur ^ 1), sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_history: copy failed");
   return HX_OK;
@@ -283,21 +320,52 @@ void history_commit(hx_history* h, const std::vector<int>& changed, const std::v
   h->cur ^= 1;
 }
 
-}  // namespace
+// The rate matrices [C][A][A] to the device and the largest |element| of each to the host.  max_abs: checked by the caller
+// (history_check_rates) before anything is allocated.
+int history_put_rates(hx_history* h, const char* fn, const double* rate, const std::vector<double>& max_abs, const ExpmPlan& plan) {
+  const size_t bytes = (size_t)h->C * h->A * h->A * sizeof(double);
+  if (!h->rate.p && hipMalloc(&h->rate.p, bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+  if (hipMemcpy(h->rate.p, rate, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    h->max_abs.clear();                              // (what the buffer holds is unknown: no rates are set)
+    return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  }
+  h->max_abs = max_abs;
+  h->expm = plan;
+  return HX_OK;
+}
 
-extern "C" {
+int history_check_rates(const char* fn, const double* rate, const int A, const int C, std::vector<double>& max_abs, ExpmPlan& plan) {
+  max_abs.assign(C, 0.);
+  for (int cpt = 0; cpt < C; ++cpt)
+    if (!expm_max_abs(rate + (size_t)cpt * A * A, A * A, &max_abs[cpt])) return sp_fail(HX_ERR_RANGE, fn, "a rate that is NaN or infinite");
+  if (!branch_expm_plan(A, &plan)) return sp_fail(HX_ERR_INVALID_ARG, fn, "the LDS plan of k_branch_expm exceeds the LDS of a CU");
+  return HX_OK;
+}
 
-int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t n_cols, const double* branch_sub, void* stream, hx_history** out) {
-  if (!out) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument");
-  *out = nullptr;
-  if (!hm || !tokens || !branch_sub || n_cols <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument or no columns");
-  const char* fn = "hx_history_create";
+// a length the series of every component can be shaped for
+bool history_length_ok(const std::vector<double>& max_abs, const double t) {
+  if (!expm_length_ok(t)) return false;
+  for (const double m : max_abs)
+    if (!expm_norm_ok(m, t)) return false;
+  return true;
+}
+
+// hx_history_create (branch_sub) and hx_history_create_from_lengths (rate, lengths)
+int history_create(const char* fn, const hx_history_model* hm, const int8_t* tokens, int64_t n_cols, const double* branch_sub, const double* rate,
+                   const double* lengths, void* stream, hx_history** out) {
   const int A = hm->alph_size, C = hm->components, N = hm->n_nodes, AA = A * A;
   int device = 0;
   const double* lse_tab = nullptr;
   std::vector<int> child;
   if (int rc = sp_check_model(fn, A > 0 && C > 0 && N > 0 && hm->parent && hm->ins_prob && hm->log_cpt_weight, A, C, HX_ERR_RANGE, &device, &lse_tab)) return rc;
   if (int rc = sp_children(fn, hm->parent, N, true, HX_ERR_RANGE, child)) return rc;
+  std::vector<double> max_abs;
+  ExpmPlan expm = {};
+  if (rate) {
+    if (int rc = history_check_rates(fn, rate, A, C, max_abs, expm)) return rc;
+    for (int r = 0; r < N - 1; ++r)
+      if (!history_length_ok(max_abs, lengths[r])) return sp_fail(HX_ERR_RANGE, fn, "a branch length that is negative, NaN or infinite");
+  }
   // the token check in the same pass over the tokens as the transpose and the search for the roots
   const long long ncp = (n_cols + 63) & ~63LL;
   std::vector<signed char> tokT((size_t)N * ncp, (signed char)-2);
@@ -330,9 +398,11 @@ int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t 
   h->e_slot = (ncp / 64) * (long long)C * N * AP * 64;
   h->lg_slot = (ncp / 64) * (long long)C * N * 64;
   const size_t n_mat = (size_t)C * N * AA;
+  // [N] info words, the walk [<= N], the arriving nodes [<= N], a word of padding, six words per (node, component) of shapes
+  const size_t n_info = 3 * (size_t)N + 2 + 6 * (size_t)N * C;
   SpUpload& up = h->model;
   if (hipMalloc(&h->tok.p, (size_t)N * ncp) != hipSuccess ||
-      !up.alloc(SpUpload::room((size_t)ncp * sizeof(int)) + sp_tree_room(A, C, N, false) + SpUpload::room(3 * (size_t)N * sizeof(int))) ||
+      !up.alloc(SpUpload::room((size_t)ncp * sizeof(int)) + sp_tree_room(A, C, N, false) + SpUpload::room(n_info * sizeof(int))) ||
       hipMalloc(&h->mats.p, 2 * n_mat * sizeof(double)) != hipSuccess || hipMalloc(&h->stage.p, n_mat * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->E.p, 2 * (size_t)h->e_slot * sizeof(double)) != hipSuccess || hipMalloc(&h->logE.p, 2 * (size_t)h->lg_slot * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->cll.p, 2 * (size_t)ncp * sizeof(double)) != hipSuccess || hipMalloc(&h->sum.p, 2 * sizeof(double)) != hipSuccess ||
@@ -341,23 +411,78 @@ int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t 
   h->d_root = up.put(root.data(), root.size());
   const SpTree tr = sp_put_tree(up, A, C, N, hm->parent, child, hm->ins_prob, hm->log_cpt_weight, nullptr);
   h->d_child = tr.child; h->d_parent = tr.parent; h->d_ins = tr.ins_prob; h->d_lcw = tr.log_cpt_weight;
-  h->d_info = up.reserve<int>(3 * (size_t)N);        // [N], then the walk [<= N], then the changed nodes [<= N]
+  h->d_info = up.reserve<int>(n_info);
   h->d_walk = h->d_info + N;
-  // the root's matrix is never read; the caller's [C][N][A][A] goes to slot 0 whole
+  // the root's matrix is never read; the caller's [C][N][A][A] goes to slot 0 whole, or exp(R t) of every branch is computed there
   if (!up.copied || hipMemcpy(h->tok.p, tokT.data(), tokT.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->mats.p, branch_sub, n_mat * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+      (branch_sub && hipMemcpy(h->mats.p, branch_sub, n_mat * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) ||
       hipMemset(h->cll.p, 0, 2 * (size_t)ncp * sizeof(double)) != hipSuccess)
     return sp_fail(HX_ERR_HIP, fn, "copy failed");
-  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
+  if (rate)
+    if (int rc = history_put_rates(h, fn, rate, max_abs, expm)) return rc;
+  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess || hipEventCreate(&h->ev_c) != hipSuccess)
+    return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
   // the full evaluation: the proposal that changes and walks every node, accepted
   std::vector<int> all(N);
   for (int r = 0; r < N; ++r) all[r] = r;
-  const int rc = history_run(h, all, all, nullptr, static_cast<hipStream_t>(stream), nullptr);
+  const int rc = history_run(h, all, all, nullptr, rate ? lengths : nullptr, static_cast<hipStream_t>(stream), nullptr);
   if (rc != HX_OK) return rc;
   history_commit(h, all, all);
   guard.h = nullptr;
   *out = h;
   return HX_OK;
+}
+
+// hx_history_propose (branch_sub) and hx_history_propose_lengths (lengths): every refusal comes before anything is launched
+int history_propose(const char* fn, hx_history* h, const int n_changed, const int32_t* nodes, const double* branch_sub, const double* lengths, double* lp_sub,
+                    void* stream) {
+  if (h->pending) return sp_fail(HX_ERR_STATE, fn, "a proposal is pending (accept or reject it first)");
+  if (lengths && h->max_abs.empty()) return sp_fail(HX_ERR_STATE, fn, "no rates are set (hx_history_set_rates)");
+  // the nodes to recompute: the changed ones and their ancestors, ascending (children before parents)
+  std::vector<int> changed, walked;
+  switch (history_closure(h->parent, n_changed, nodes, changed, walked)) {
+    case 1: return sp_fail(HX_ERR_RANGE, fn, "a node outside 0 .. N - 2 (the root has no branch)");
+    case 2: return sp_fail(HX_ERR_INVALID_ARG, fn, "a node named twice");
+    default: break;
+  }
+  for (int k = 0; lengths && k < n_changed; ++k)
+    if (!history_length_ok(h->max_abs, lengths[k])) return sp_fail(HX_ERR_RANGE, fn, "a branch length that is negative, NaN or infinite");
+  // (the new matrices go to the slot the current ones are not in: history_run)
+  const int rc = history_run(h, changed, walked, branch_sub, lengths, static_cast<hipStream_t>(stream), lp_sub);
+  if (rc != HX_OK) return rc;
+  h->changed.swap(changed);
+  h->walked.swap(walked);
+  h->pending = true;
+  return HX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hx_history_create(const hx_history_model* hm, const int8_t* tokens, int64_t n_cols, const double* branch_sub, void* stream, hx_history** out) {
+  if (!out) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument");
+  *out = nullptr;
+  if (!hm || !tokens || !branch_sub || n_cols <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create: null argument or no columns");
+  return history_create("hx_history_create", hm, tokens, n_cols, branch_sub, nullptr, nullptr, stream, out);
+}
+
+int hx_history_create_from_lengths(const hx_history_model* hm, const int8_t* tokens, int64_t n_cols, const double* rate, const double* lengths, void* stream,
+                                   hx_history** out) {
+  if (!out) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create_from_lengths: null argument");
+  *out = nullptr;
+  if (!hm || !tokens || !rate || !lengths || n_cols <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_create_from_lengths: null argument or no columns");
+  return history_create("hx_history_create_from_lengths", hm, tokens, n_cols, nullptr, rate, lengths, stream, out);
+}
+
+int hx_history_set_rates(hx_history* h, const double* rate) {
+  const char* fn = "hx_history_set_rates";
+  if (!h || !rate) return sp_fail(HX_ERR_INVALID_ARG, fn, "null argument");
+  if (h->pending) return sp_fail(HX_ERR_STATE, fn, "a proposal is pending (accept or reject it first)");
+  std::vector<double> max_abs;
+  ExpmPlan plan = {};
+  if (int rc = history_check_rates(fn, rate, h->A, h->C, max_abs, plan)) return rc;
+  return history_put_rates(h, fn, rate, max_abs, plan);
 }
 
 int hx_history_destroy(hx_history* h) {
@@ -367,28 +492,25 @@ int hx_history_destroy(hx_history* h) {
 
 int hx_history_propose(hx_history* h, int32_t n_changed, const int32_t* nodes, const double* branch_sub, double* lp_sub, void* stream) {
   if (!h || !nodes || !branch_sub || n_changed <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_propose: null argument or no nodes");
-  if (h->pending) return api_fail(HX_ERR_STATE, "hx_history_propose: a proposal is pending (accept or reject it first)");
-  const int N = h->N;
-  std::vector<unsigned char> mark(N, 0);
-  std::vector<int> changed;
-  for (int k = 0; k < n_changed; ++k) {
-    if (nodes[k] < 0 || nodes[k] >= N - 1) return api_fail(HX_ERR_RANGE, "hx_history_propose: a node outside 0 .. N - 2 (the root has no branch)");
-    if (mark[nodes[k]]) return api_fail(HX_ERR_INVALID_ARG, "hx_history_propose: a node named twice");
-    mark[nodes[k]] = 1;
-    changed.push_back(nodes[k]);
-  }
-  // the nodes to recompute: the changed ones and their ancestors, ascending (children before parents)
-  for (int r : changed)
-    for (int p = h->parent[r]; p >= 0 && !mark[p]; p = h->parent[p]) mark[p] = 2;
-  std::vector<int> walked;
-  for (int r = 0; r < N; ++r)
-    if (mark[r]) walked.push_back(r);
-  // (the new matrices go to the slot the current ones are not in: history_run)
-  const int rc = history_run(h, changed, walked, branch_sub, static_cast<hipStream_t>(stream), lp_sub);
-  if (rc != HX_OK) return rc;
-  h->changed.swap(changed);
-  h->walked.swap(walked);
-  h->pending = true;
+  return history_propose("hx_history_propose", h, n_changed, nodes, branch_sub, nullptr, lp_sub, stream);
+}
+
+int hx_history_propose_lengths(hx_history* h, int32_t n_changed, const int32_t* nodes, const double* lengths, double* lp_sub, void* stream) {
+  if (!h || !nodes || !lengths || n_changed <= 0) return api_fail(HX_ERR_INVALID_ARG, "hx_history_propose_lengths: null argument or no nodes");
+  return history_propose("hx_history_propose_lengths", h, n_changed, nodes, nullptr, lengths, lp_sub, stream);
+}
+
+int hx_history_branch_matrix(hx_history* h, int32_t which, int32_t node, double* out) {
+  const char* fn = "hx_history_branch_matrix";
+  if (!h || !out || (which != 0 && which != 1)) return sp_fail(HX_ERR_INVALID_ARG, fn, "null argument, or `which` not 0 or 1");
+  if (node < 0 || node >= h->N - 1) return sp_fail(HX_ERR_RANGE, fn, "a node outside 0 .. N - 2 (the root has no branch)");
+  if (which == 1 && !h->pending) return sp_fail(HX_ERR_STATE, fn, "no proposal is pending");
+  int slot = h->mslot[node];
+  if (which == 1 && std::find(h->changed.begin(), h->changed.end(), (int)node) != h->changed.end()) slot ^= 1;
+  // the node's C matrices lie N matrices apart
+  const size_t mat = (size_t)h->A * h->A * sizeof(double);
+  const double* src = static_cast<const double*>(h->mats.p) + ((size_t)slot * h->C * h->N + node) * h->A * h->A;
+  if (hipMemcpy2D(out, mat, src, mat * h->N, mat, (size_t)h->C, hipMemcpyDeviceToHost) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
   return HX_OK;
 }
 
@@ -434,6 +556,12 @@ int hx_history_indel_counts(hx_history* h, int64_t* counts) {
 int hx_history_last_kernel_ms(hx_history* h, float* ms) {
   if (!h || !ms) return api_fail(HX_ERR_INVALID_ARG, "hx_history_last_kernel_ms: null argument");
   *ms = h->ms;
+  return HX_OK;
+}
+
+int hx_history_last_expm_ms(hx_history* h, float* ms) {
+  if (!h || !ms) return api_fail(HX_ERR_INVALID_ARG, "hx_history_last_expm_ms: null argument");
+  *ms = h->expm_ms;
   return HX_OK;
 }
 

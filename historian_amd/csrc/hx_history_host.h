@@ -1,0 +1,87 @@
+// The host's share of a branch-length proposal to the resident history (hx_history.hip), free of HIP so that a stand-alone
+// program can run it under a sanitizer on the CPU (host/t/testhistoryhost.cpp): the shape of the series of exp(R t), the
+// validation of the lengths, the closure of the changed nodes over their ancestors, the launch plan of k_branch_expm.
+#pragma once
+#include <cmath>
+#include <vector>
+
+namespace hx {
+
+// What k_branch_expm is told about one (node, component): everything of gsl_linalg_exponential_ss that is not a multiply,
+// an add or 1. / integer.
+struct ExpmShape {
+  double t, shrink;
+  int terms, squarings;
+};
+
+// RateModel::getSubProbMatrix's (terms, squarings, shrink) for a matrix R t whose largest |element| is fl(max_abs_rate * t):
+// rounding is monotone and t >= 0, so max_ij |fl(R_ij t)| == fl(max_ij |R_ij| * t).  The double-precision row of the table
+// in GSL's linalg/exponential.c; the host's libm for log, ceil and exp, as the mirror (hx_host_base.cpp) takes them.
+inline ExpmShape expm_shape(const double max_abs_rate, const double t) {
+  static const int table[6][2] = {{5, 1}, {5, 4}, {7, 5}, {9, 7}, {10, 10}, {8, 14}};
+  static const double below[6] = {0.01, 0.1, 1., 10., 100., 1000.};
+  const double norm = max_abs_rate * t;
+  ExpmShape s;
+  s.t = t;
+  s.terms = table[5][0];
+  s.squarings = -1;
+  for (int r = 0; r < 6 && s.squarings < 0; ++r)
+    if (norm < below[r]) { s.terms = table[r][0]; s.squarings = table[r][1]; }
+  if (s.squarings < 0) s.squarings = table[5][1] + (int)ceil(log(1.01 * norm / 1000.) / log(2.));
+  s.shrink = 1. / exp(log(2.) * s.squarings);
+  return s;
+}
+
+// a branch length the series can be shaped for: not negative, not NaN, not infinite
+inline bool expm_length_ok(const double t) { return t >= 0. && t < INFINITY; }
+// ... and not so large that the table's last row (log(1.01 norm / 1000)) sees an infinite norm
+inline bool expm_norm_ok(const double max_abs_rate, const double t) { return 1.01 * (max_abs_rate * t) < INFINITY; }
+
+// the largest |element| of an A x A rate matrix; false when an element is NaN or infinite
+inline bool expm_max_abs(const double* rate, const int AA, double* max_abs) {
+  double m = 0.;
+  for (int e = 0; e < AA; ++e) {
+    const double v = fabs(rate[e]);
+    if (!(v < INFINITY)) return false;
+    if (v > m) m = v;
+  }
+  *max_abs = m;
+  return true;
+}
+
+// k_branch_expm's workgroup: W waves share the A x A entries, entry e with thread e mod 64 W.  A lone matrix is a chain of
+// dependent products, so the waves are what shortens it: one entry a lane while eight waves allow (A = 20: W = 7, measured
+// against 1, 2, 4 and 8 waves in DESIGN.md section 19), at most 8 entries a lane (A = 64: W = 8).  forced_waves in 1 .. 8 takes that
+// many instead (HX_EXPM_WAVES, a measurement hook) if 8 entries a lane still do.  The result does not depend on W.
+struct ExpmPlan { int waves, per_lane; size_t lds; };
+inline ExpmPlan expm_plan(const int A, const int forced_waves) {
+  const int AA = A * A;
+  ExpmPlan p;
+  p.waves = (AA + 63) / 64 < 8 ? (AA + 63) / 64 : 8;
+  if (forced_waves >= 1 && forced_waves <= 8 && AA <= 512 * forced_waves) p.waves = forced_waves;
+  p.per_lane = (AA + 64 * p.waves - 1) / (64 * p.waves);
+  p.lds = 2 * sizeof(double) * (size_t)AA;
+  return p;
+}
+
+// A proposal's nodes.  0: fine - `changed` holds them in the caller's order, `walked` them and their ancestors ascending
+// (children before parents); 1: a node outside 0 .. N - 2; 2: a node named twice.  parent: [N], children before parents.
+inline int history_closure(const std::vector<int>& parent, const int n_changed, const int* nodes, std::vector<int>& changed, std::vector<int>& walked) {
+  const int N = (int)parent.size();
+  std::vector<unsigned char> mark(N, 0);
+  changed.clear();
+  walked.clear();
+  for (int k = 0; k < n_changed; ++k) {
+    if (nodes[k] < 0 || nodes[k] >= N - 1) return 1;
+    if (mark[nodes[k]]) return 2;
+    mark[nodes[k]] = 1;
+    changed.push_back(nodes[k]);
+  }
+  for (int r : changed)
+    for (int p = parent[r]; p >= 0 && !mark[p]; p = parent[p]) mark[p] = 2;
+  for (int r = 0; r < N; ++r)
+    if (mark[r]) walked.push_back(r);
+  return 0;
+}
+
+}  // namespace hx

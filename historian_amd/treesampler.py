@@ -17,7 +17,8 @@ tree is sum n * log(transProb) over them; the substitution term comes from an in
   evaluator.propose(nodes, lengths)   the sum for the tree in which the branches above `nodes` have the new `lengths`
   evaluator.accept() / reject()       keep or drop that proposal
 
-DeviceEvaluator is the product's: capi.History (hx_history.hip) with model.sub_prob for the changed branches only.  The
+DeviceEvaluator is the product's: capi.History (hx_history.hip), which takes the rate matrices once and the changed
+branches' lengths per proposal (or, given a sub_prob callable, that callable's matrices for the changed branches).  The
 tests inject a CPU evaluator over the sum-product oracle, so the sampler's logic is checked without a GPU.
 
 NOT built: prune-and-regraft and the alignment moves (BranchAlign, NodeAlign).  Their rates are 0 here, where the reference
@@ -178,18 +179,28 @@ class Move:
 
 
 class DeviceEvaluator:
-    """The resident history of hx_history.hip behind the evaluator interface.  sub_prob(t) -> [C] matrices exp(R t);
-    model.sub_prob unless given."""
+    """The resident history of hx_history.hip behind the evaluator interface, in one of two modes.
 
-    def __init__(self, model, parent, length, tokens, sub_prob=None, stream=None):
-        self.sub_prob = sub_prob or model.sub_prob
+    "lengths" (the default when no sub_prob is given): the history takes model.sub_rate once and every proposal is its
+    (node, branch length) pairs; exp(R t) is computed on the device with the bits of the C++ mirror's getSubProbMatrix.
+    "matrices" (the default when sub_prob is given): sub_prob(t) -> [C] matrices exp(R t) on the host for every changed
+    branch (model.sub_prob, scipy's expm, unless given), uploaded with the proposal."""
+
+    def __init__(self, model, parent, length, tokens, sub_prob=None, stream=None, mode=None):
+        self.mode = mode or ("matrices" if sub_prob else "lengths")
+        if self.mode not in ("lengths", "matrices"):
+            raise ValueError("mode must be 'lengths' or 'matrices'")
+        self.sub_prob = (sub_prob or model.sub_prob) if self.mode == "matrices" else None
         self.stream = stream
         c, a, n = model.components(), len(model.alphabet), len(parent)
+        ins_prob, log_cpt_weight = np.asarray(model.root, dtype=float).reshape(c, a), np.log(np.asarray(model.cpt_weight, dtype=float))
+        if self.mode == "lengths":
+            self.history = capi.History.from_lengths(parent, ins_prob, log_cpt_weight, tokens, np.asarray(model.sub_rate, dtype=float), length, stream=stream)
+            return
         branch_sub = np.zeros((c, n, a, a))
         for r in range(n - 1):
             branch_sub[:, r] = np.asarray(self.sub_prob(length[r]), dtype=float)
-        self.history = capi.History(parent, np.asarray(model.root, dtype=float).reshape(c, a), np.log(np.asarray(model.cpt_weight, dtype=float)),
-                                    tokens, branch_sub, stream=stream)
+        self.history = capi.History(parent, ins_prob, log_cpt_weight, tokens, branch_sub, stream=stream)
 
     def lp_sub(self):
         return self.history.log_like(0, want_columns=False)[0]
@@ -198,6 +209,8 @@ class DeviceEvaluator:
         return self.history.indel_counts()
 
     def propose(self, nodes, lengths):
+        if self.mode == "lengths":
+            return self.history.propose_lengths(nodes, lengths, stream=self.stream)
         return self.history.propose(nodes, np.asarray([self.sub_prob(t) for t in lengths], dtype=float), stream=self.stream)
 
     def accept(self):

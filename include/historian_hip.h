@@ -23,8 +23,8 @@
  *   - Asynchronous on the caller's stream (they return once the work is queued): hx_batch_forward, hx_batch_backward on a
  *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
  *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
- *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix, hx_distance_neg_log_like, hx_history_create and
- *     hx_history_propose run their kernels on `stream` and return when they are done.
+ *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix, hx_distance_neg_log_like, hx_history_create,
+ *     hx_history_create_from_lengths, hx_history_propose and hx_history_propose_lengths run their kernels on `stream` and return when they are done.
  *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
  *     Forward launch (an event), with no host synchronisation.
  *   - Readers (results, matrices, cells, tracebacks, walks, counts) synchronise with the batch's LAST stream only - the stream
@@ -469,6 +469,41 @@ int hx_history_log_like(hx_history* h, int32_t which, double* lp_sub, double* co
 int hx_history_indel_counts(hx_history* h, int64_t* counts);
 /* Duration of the kernels of the most recent evaluation (create or propose) of this history. */
 int hx_history_last_kernel_ms(hx_history* h, float* ms);
+
+/* Proposals as branch lengths: the history takes its rate matrices once and computes exp(R t) of the changed branches on
+ * the device (k_branch_expm, one workgroup per (node, component)), straight into the slots the proposal reads them from.
+ * The matrices are gsl_linalg_exponential_ss restated, bit for bit those of the host mirror's RateModel::getSubProbMatrix
+ * (what differs from a host run is nothing: multiplies, adds and 1. / integer in the host's order; the series' shape is
+ * taken on the host with the host's libm, see hx_expm_shape).
+ *
+ * rate [C][A][A] RateModel::subRate (copied).  HX_ERR_RANGE: an element that is NaN or infinite; HX_ERR_STATE: a proposal
+ * is pending.  The current matrices are not recomputed: rates set after creation serve the proposals that follow. */
+int hx_history_set_rates(hx_history* h, const double* rate);
+/* hx_history_propose's contract in every respect (stream, pending state, the walked set, accept and reject,
+ * hx_history_last_kernel_ms - which includes k_branch_expm -, nothing launched and nothing changed on refusal), with
+ * lengths [n_changed], the new length of each named node's branch, in place of the matrices.  Further refusals:
+ * HX_ERR_STATE when no rates are set; HX_ERR_RANGE for a length that is negative, NaN or infinite (or so large that
+ * max|R| * t overflows).  t = 0 is legal and gives the identity exactly.  hx_history_propose keeps working on the same
+ * history, before and after. */
+int hx_history_propose_lengths(hx_history* h, int32_t n_changed, const int32_t* nodes, const double* lengths,
+                               double* lp_sub, void* stream);
+/* hx_history_create with rate [C][A][A] and lengths [N] (the root's is not read) in place of branch_sub: allocate, set the
+ * rates, exp(R t) of all N - 1 branches into the current slots, the full evaluation.  The same refusals as
+ * hx_history_create, hx_history_set_rates and hx_history_propose_lengths, before anything is allocated. */
+int hx_history_create_from_lengths(const hx_history_model* model, const int8_t* tokens, int64_t n_cols, const double* rate,
+                                   const double* lengths, void* stream, hx_history** out);
+/* out [C][A][A]: the matrices of `node`'s branch.  which = 0: the current ones; which = 1: the pending proposal's if the
+ * node is among its changed nodes, else the current ones (HX_ERR_STATE without a pending proposal).  HX_ERR_RANGE: a node
+ * outside 0 .. N - 2. */
+int hx_history_branch_matrix(hx_history* h, int32_t which, int32_t node, double* out);
+/* A measurement aid (tools/history_bench.py), not needed to use the history: the duration of k_branch_expm within the most
+ * recent evaluation of this history (part of hx_history_last_kernel_ms); 0 when that evaluation brought its matrices. */
+int hx_history_last_expm_ms(hx_history* h, float* ms);
+/* Host only, no device: (terms, squarings, shrink = 1. / exp(log(2.) * squarings)) of gsl_linalg_exponential_ss for a
+ * matrix R t with max |R_ij| = max_abs_rate - the function the library itself shapes every k_branch_expm workgroup with.
+ * Rounding is monotone and t >= 0, so max_ij |fl(R_ij t)| == fl(max_abs_rate * t), the norm getSubProbMatrix looks up.
+ * HX_ERR_RANGE: an argument that is negative, NaN or infinite, or a product that overflows. */
+int hx_expm_shape(double max_abs_rate, double t, int32_t* terms, int32_t* squarings, double* shrink);
 
 /* -- tree estimation: maximum-likelihood pairwise distances (reference src/model.cpp:506-655) ------
  * RateModel::distanceMatrix for the rows of a gapped alignment: per pair of rows the counts of aligned residue
