@@ -121,7 +121,7 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_history_create", "hx_history_destroy", "hx_history_propose", "hx_history_accept", "hx_history_reject",
            "hx_history_log_like", "hx_history_indel_counts", "hx_history_last_kernel_ms", "hx_history_set_rates",
            "hx_history_propose_lengths", "hx_history_create_from_lengths", "hx_history_branch_matrix", "hx_expm_shape",
-           "hx_history_last_expm_ms"]
+           "hx_history_last_expm_ms", "hx_history_row_lengths", "hx_history_excluded_profiles"]
 
 
 class HxError(RuntimeError):
@@ -226,6 +226,8 @@ def load():
     lib.hx_history_propose_lengths.argtypes = [vp, C.c_int32, _i32p, _f64p, _f64p, vp]
     lib.hx_history_create_from_lengths.argtypes = [C.POINTER(HxHistoryModel), C.POINTER(C.c_int8), C.c_int64, _f64p, _f64p, vp, C.POINTER(vp)]
     lib.hx_history_branch_matrix.argtypes = [vp, C.c_int32, C.c_int32, _f64p]
+    lib.hx_history_row_lengths.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.hx_history_excluded_profiles.argtypes = [vp, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int32, C.POINTER(_f64p), vp]
     lib.hx_expm_shape.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p]
     lib.hx_batch_read_matrix_async.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
@@ -1003,6 +1005,31 @@ class History:
         out = np.empty((self.n, 3, 4), dtype=np.int64)
         _check(load().hx_history_indel_counts(self._h, _p(out, C.POINTER(C.c_int64))))
         return out
+
+    def row_lengths(self):
+        """[N] int64: the positions of every node (the columns in which it is not a gap)"""
+        out = np.empty(self.n, dtype=np.int64)
+        _check(load().hx_history_row_lengths(self._h, _p(out, C.POINTER(C.c_int64))))
+        return out
+
+    def excluded_profiles(self, pairs, normalize=True, which=0, stream=None):
+        """hx_history_excluded_profiles: pairs [(node, excluded neighbour)] -> a list of [len(node)][C][A] arrays, the
+        reference's logNodeExcludedPostProb of every column in which the node is not a gap (getConditionalPWMs)"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        node, exclude = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        inside = (node >= 0) & (node < self.n)
+        lens = self.row_lengths()
+        out = [np.empty((int(lens[r]) if ok else 0, self.c, self.a)) for r, ok in zip(node, inside)]
+        ptrs = (_f64p * max(len(out), 1))(*[_p(o, _f64p) if o.size else C.cast(None, _f64p) for o in out])
+        _check(load().hx_history_excluded_profiles(self._h, which, len(out), _p(node, _i32p), _p(exclude, _i32p), 1 if normalize else 0, ptrs,
+                                                   C.c_void_p(stream or 0)))
+        return out
+
+    def branch_profiles(self, node, normalize=True, which=0):
+        """(parent_pwm, node_pwm) of the branch above `node`: what BranchAlignMove and Refiner realign across it"""
+        parent = int(self._keep[0][node]) if 0 <= node < self.n else -1
+        p, n = self.excluded_profiles([(parent, node), (node, parent)], normalize=normalize, which=which)
+        return p, n
 
     def kernel_ms(self):
         ms = C.c_float()

@@ -23,7 +23,8 @@
 // CountSubstEvents bit is accepted and ignored, and SumProduct* must be NULL.
 // Sampler: BranchMatrix and the eleven-state SiblingMatrix (hx_host_sibling.cpp: fill on the device through
 // hx_sibling_batch_*, single or as fillBatch; sample / logPostProb / parentSeq over the copy read back) are mirrored here; the
-// sampler's alignment moves and prune-and-regraft (getConditionalPWMs, sampleSeq) are not built; the tree-height moves
+// sampler's alignment moves and prune-and-regraft (sampleSeq, the moves themselves) are not built - their first step,
+// TreeAlignFuncs::getConditionalPWMs, is, on the resident history (hx_history_excluded_profiles); the tree-height moves
 // (NodeHeightMove, RescaleMove), Move::accept, Sampler::sample / run and TreeAlignFuncs::logLikelihood of a whole history are
 // (hx_host_sampler.cpp): the substitution term through the device-resident history hx_history_*, the rest on the host.
 #pragma once
@@ -927,6 +928,19 @@ struct TreeAlignFuncs {
   static double rootExtProb(const RateModel& model) { return model.insExtProb; }
   // not in the reference: the history as hx_history_create takes it (tokens [columns][nodes], exp(R t) of every branch)
   static hx_history* residentHistory(const RateModel& model, const History& history);
+  // src/sampler.cpp:356-370: per node of `exclude`, logNodeExcludedPostProb of every column in which it is not a gap.  The
+  // way up is the resident history's, the way down runs along the path to each node (hx_history_excluded_profiles), so
+  // fillUpNodes and fillDownNodes - the reference's way of not filling what it will not read - are taken and not used.
+  // Serves the maps of BranchAlignMove, NodeAlignMove and Refiner: every excluded node the parent or a child of its node.
+  // PruneAndRegraftMove's map on its detached tree (a node with nothing excluded, -1) aborts: not built.
+  static map<TreeNodeIndex, PosWeightMatrix> getConditionalPWMs(const RateModel& model, const ReconTree& tree, const vguard<FastSeq>& gapped,
+                                                                const map<TreeNodeIndex, TreeNodeIndex>& exclude, const set<TreeNodeIndex>& fillUpNodes,
+                                                                const set<TreeNodeIndex>& fillDownNodes, bool normalize = true);
+  // not in the reference: the same on a history that is resident already (a Sampler's `resident`), current state.  `model`
+  // and `tree` must be the ones the history was made from: the rows are sized by the model's components and alphabet, and
+  // the history holds no copy to check them against
+  static map<TreeNodeIndex, PosWeightMatrix> getConditionalPWMs(hx_history* resident, const RateModel& model, const ReconTree& tree,
+                                                                const map<TreeNodeIndex, TreeNodeIndex>& exclude, bool normalize = true);
 
   class BranchMatrixBase {
   public:
@@ -1058,7 +1072,7 @@ struct Sampler : TreeAlignFuncs {
   // hx_sibling_batch_sample_paths / read_cells, the matrices of a fillBatch share their batch (sampleBatch walks them in one
   // launch), and the dense copy is read on the first cell() call only.  HX_HOST_WALKS=1 keeps the host walks over the copy.
   // fillBatch fills several matrices in one device batch (a move fills two, a sweep of moves many).  The sampler's
-  // alignment moves (getConditionalPWMs, sampleSeq) are not built.  Parity of this lattice is pinned by enumeration
+  // alignment moves (sampleSeq, the moves themselves) are not built.  Parity of this lattice is pinned by enumeration
   // (tests/test_oracle_sibling.py), not by a reference fixture: none holds a sibling matrix.
   class SiblingMatrix {
   public:

@@ -246,6 +246,60 @@ LogProb TreeAlignFuncs::substLogLikelihood(const RateModel& model, const History
   return lpSub;
 }
 
+// the maps getConditionalPWMs serves name a neighbour for every node; PruneAndRegraftMove's (on a detached tree: a node with
+// nothing excluded, neighbours of another tree) is not among them
+static void neighboursOnly(const ReconTree& tree, const map<TreeNodeIndex, TreeNodeIndex>& exclude) {
+  const TreeNodeIndex N = tree.nodes();
+  for (const auto& ne : exclude) {
+    const TreeNodeIndex node = ne.first, ex = ne.second;
+    const bool inside = node >= 0 && node < N && ex >= 0 && ex < N;
+    if (!inside || (tree.parent[node] != ex && tree.parent[ex] != node)) Abort("%s moves are not built", Sampler::Move::typeName(Sampler::Move::PruneAndRegraft));
+  }
+}
+
+map<TreeNodeIndex, TreeAlignFuncs::PosWeightMatrix> TreeAlignFuncs::getConditionalPWMs(hx_history* resident, const RateModel& model, const ReconTree& tree,
+                                                                                      const map<TreeNodeIndex, TreeNodeIndex>& exclude, bool normalize) {
+  const TreeNodeIndex N = tree.nodes();
+  const size_t A = model.alphabetSize(), C = (size_t)model.components();
+  neighboursOnly(tree, exclude);
+  map<TreeNodeIndex, PosWeightMatrix> pwms;
+  if (exclude.empty()) return pwms;
+  vguard<int64_t> len((size_t)N);
+  detail::check(hx_history_row_lengths(resident, len.data()), "hx_history_row_lengths");
+  vguard<int32_t> nodes, excluded;
+  vguard<vguard<double>> flat;
+  vguard<double*> out;
+  for (const auto& ne : exclude) {
+    nodes.push_back((int32_t)ne.first);
+    excluded.push_back((int32_t)ne.second);
+    flat.emplace_back((size_t)len[ne.first] * C * A);
+  }
+  for (auto& f : flat) out.push_back(f.empty() ? nullptr : f.data());
+  detail::check(hx_history_excluded_profiles(resident, 0, (int32_t)nodes.size(), nodes.data(), excluded.data(), normalize ? 1 : 0, out.data(), nullptr),
+                "hx_history_excluded_profiles");
+  for (size_t k = 0; k < nodes.size(); ++k) {
+    if (flat[k].empty()) continue;                   // (the reference's map has no entry for a node without positions)
+    PosWeightMatrix& pwm = pwms[nodes[k]];
+    pwm.assign((size_t)len[nodes[k]], vguard<vguard<LogProb>>(C, vguard<LogProb>(A)));
+    const double* v = flat[k].data();
+    for (auto& pos : pwm)
+      for (auto& cpt : pos)
+        for (auto& lp : cpt) lp = *v++;
+  }
+  return pwms;
+}
+
+map<TreeNodeIndex, TreeAlignFuncs::PosWeightMatrix> TreeAlignFuncs::getConditionalPWMs(const RateModel& model, const ReconTree& tree, const vguard<FastSeq>& gapped,
+                                                                                      const map<TreeNodeIndex, TreeNodeIndex>& exclude, const set<TreeNodeIndex>&,
+                                                                                      const set<TreeNodeIndex>&, bool normalize) {
+  neighboursOnly(tree, exclude);                     // (before a history is made for nothing)
+  History history;
+  history.gapped = gapped;
+  history.tree = tree;
+  std::shared_ptr<hx_history> h(residentHistory(model, history), hx_history_destroy);
+  return getConditionalPWMs(h.get(), model, tree, exclude, normalize);
+}
+
 LogProb TreeAlignFuncs::logLikelihood(const SimpleTreePrior& treePrior, const RateModel& model, const History& history, const char*) {
   const LogProb lpTree = treePrior.treeLogLikelihood(history.tree);
   const LogProb lpRoot = rootLogLikelihood(model, history);

@@ -23,6 +23,9 @@
 //   hxtest treemoves <rows.fa> <tree.nh> <model.json> <steps> <seed>   a tree-height chain on a fixed alignment (node-height and
 //                                                  rescale moves, hx_host_sampler.cpp): the four likelihood parts of the initial
 //                                                  history, one line per step, the final tree
+//   hxtest condpwm <rows.fa> <tree.nh> <model.json> <node> <normalize>   the two excluded-neighbour profiles of the branch above
+//                                                  <node> (TreeAlignFuncs::getConditionalPWMs), lpEnd of the unbanded
+//                                                  Sampler::BranchMatrix built from them, a seeded sample and its logPostProb
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -370,6 +373,74 @@ int treeMoves(int, char** args) {
   return 0;
 }
 
+// condpwm <rows.fa> <tree.nh> <model.json> <node> <normalize>: what BranchAlignMove does first with the branch above <node>
+// (src/sampler.cpp:582-594).  Prints "lengths <parent> <node>"; "parent <pos>" and "node <pos>" with the C x A entries of
+// every row of the two profiles (hex floats); "lpEnd" of an unbanded Sampler::BranchMatrix built from them; a seeded sample
+// as two rows of '*' and '-'; its "logPostProb".  <node> given as prune:<k> calls getConditionalPWMs with the map
+// PruneAndRegraftMove builds for node k (src/sampler.cpp:843-848): it aborts, those moves are not built.
+int conditionalProfiles(int, char** args) {
+  vguard<FastSeq> rows = readFastSeqs(args[0]);
+  std::ifstream treeFile(args[1]);
+  Require(treeFile.good(), "Couldn't open %s", args[1]);
+  std::stringstream newick;
+  newick << treeFile.rdbuf();
+  RateModel rates;
+  rates.readFile(args[2]);
+  TreeAlignFuncs::History history;
+  history.tree = ReconTree::parse(newick.str());
+  const ReconTree& tree = history.tree;
+  for (TreeNodeIndex n = 0; n < tree.nodes(); ++n) {
+    const auto row = std::find_if(rows.begin(), rows.end(), [&](const FastSeq& fs) { return fs.name == tree.nodeName[n]; });
+    Require(row != rows.end(), "No row for tree node %s", tree.nodeName[n].c_str());
+    history.gapped.push_back(*row);
+  }
+  const bool prune = strncmp(args[3], "prune:", 6) == 0;
+  const TreeNodeIndex node = (TreeNodeIndex)atoi(args[3] + (prune ? 6 : 0));
+  Require(node >= 0 && node < tree.root(), "Node %d has no branch", (int)node);
+  const TreeNodeIndex parent = tree.parent[node];
+  const bool normalize = atoi(args[4]) != 0;
+  map<TreeNodeIndex, TreeNodeIndex> exclude;
+  const set<TreeNodeIndex> unused;
+  if (prune) {
+    exclude[node] = -1;
+    for (TreeNodeIndex sib : tree.child[parent])
+      if (sib != node) exclude[sib] = parent;
+    if (tree.parent[parent] >= 0) exclude[tree.parent[parent]] = parent;
+    (void)TreeAlignFuncs::getConditionalPWMs(rates, tree, history.gapped, exclude, unused, unused, normalize);
+    return 0;
+  }
+  exclude[node] = parent;
+  exclude[parent] = node;
+  const auto pwms = TreeAlignFuncs::getConditionalPWMs(rates, tree, history.gapped, exclude, unused, unused, normalize);
+  const TreeAlignFuncs::PosWeightMatrix none;
+  const auto& pSeq = pwms.count(parent) ? pwms.at(parent) : none;
+  const auto& nSeq = pwms.count(node) ? pwms.at(node) : none;
+  printf("lengths %zu %zu\n", pSeq.size(), nSeq.size());
+  for (int which = 0; which < 2; ++which) {
+    const auto& seq = which ? nSeq : pSeq;
+    for (size_t pos = 0; pos < seq.size(); ++pos) {
+      printf("%s %zu", which ? "node" : "parent", pos);
+      for (const auto& cpt : seq[pos])
+        for (double v : cpt) printf(" %a", v);
+      printf("\n");
+    }
+  }
+  vguard<SeqIdx> xPos(pSeq.size() + 1), yPos(nSeq.size() + 1);
+  for (size_t k = 0; k < xPos.size(); ++k) xPos[k] = (SeqIdx)k;
+  for (size_t k = 0; k < yPos.size(); ++k) yPos[k] = (SeqIdx)k;
+  const GuideAlignmentEnvelope everywhere;
+  const Sampler::BranchMatrix matrix(rates, pSeq, nSeq, tree.branchLength(node), everywhere, xPos, yPos, 0, 1);
+  printf("lpEnd %a\n", matrix.lpEnd);
+  Sampler::BranchMatrix::random_engine generator(22);
+  const AlignPath path = matrix.sample(generator);
+  for (AlignRowIndex row = 0; row < 2; ++row) {
+    for (bool here : path.at(row)) putchar(here ? '*' : '-');
+    putchar('\n');
+  }
+  printf("logPostProb %a\n", matrix.logPostProb(path));
+  return 0;
+}
+
 const Command commands[] = {
     {"logsumexp", 0, 1, "[-slow|-fast]", lseGrid},
     {"seqprofile", 2, 2, "<alphabet> <sequence>", leafProfileJson},
@@ -382,6 +453,7 @@ const Command commands[] = {
     {"walktime", 5, 6, "<seqfile> <modelfile> <left time> <right time> <matrices> [band]", walkTiming},
     {"distances", 2, 4, "<alignfile> <modelfile> [max iterations [host pairs]]", distances},
     {"treemoves", 5, 5, "<rows.fa> <tree.nh> <modelfile> <steps> <seed>", treeMoves},
+    {"condpwm", 5, 5, "<rows.fa> <tree.nh> <modelfile> <node | prune:node> <normalize>", conditionalProfiles},
 };
 
 }  // namespace

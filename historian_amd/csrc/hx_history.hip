@@ -19,6 +19,10 @@
 //
 // k_history_sum adds the column likelihoods in one workgroup, a fixed order for a given number of columns, whatever the
 // grid of the column kernel and whichever columns were recomputed.  No atomics anywhere.
+//
+// k_history_excluded answers a query on the live history and writes nothing to it: the excluded-neighbour profiles that
+// TreeAlignFuncs::getConditionalPWMs collects (src/sampler.cpp:356-370, SumProduct::logNodeExcludedPostProb) from the
+// messages the history holds and a way down along the one path from each column's root to the node asked for.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -200,6 +204,154 @@ __global__ void __launch_bounds__(256) k_history_indels(const signed char* __res
   }
 }
 
+// ---- excluded-neighbour profiles: SumProduct::logNodeExcludedPostProb (src/sumprod.cpp:219-250) of every column ----
+struct HxArgs {
+  int A, C, N, n_pairs;
+  long long n_cols, ncp, n_blocks;
+  long long e_slot, lg_slot;
+  const signed char* tok;          // [N][ncp]
+  const int* root;                 // [ncp]
+  const int* child;                // [N][2]
+  const int* info;                 // [N] bit 0: the slot of the node's messages in the state asked for; bit 1: of its matrix
+  const int* pair;                 // [n_pairs][4] node, excluded neighbour, start of the path (-1: none), its length
+  const int* path;                 // the paths, each from the tree's root to the node
+  const long long* out_off;        // [n_pairs] the pair's block in `out`, in doubles
+  const long long* block_off;      // [N][n_blocks] the position of a block's first column in the node's own coordinates
+  const double* ins_prob;          // [C][A]
+  const double* log_cpt_weight;    // [C]
+  const double* mats;              // [2][C][N][A][A]
+  const double* E;
+  const double* logE;
+  double* out;                     // per pair [len(node)][C][A]
+};
+
+// y = x M with M staged in a wave's LDS: transposed where the row routine runs (sp_rows<TA>), as it is otherwise
+template <int TA>
+__device__ __forceinline__ void vec_mat(const HX_LDS double* L, const int A, const double (&x)[sp_ax<TA>], double (&y)[sp_ax<TA>]) {
+  if constexpr (sp_rows<TA>) {
+    lds_mat_vec<TA>(L, x, [&](const int q, const double ya, const double yb) { y[2 * q] = ya; y[2 * q + 1] = yb; });
+  } else {
+    for (int b = 0; b < A; ++b) {
+      double s = 0.;
+      for (int a = 0; a < A; ++a) s += x[a] * L[a * A + b];
+      y[b] = s;
+    }
+  }
+}
+
+// A lane per column, a wave per component, like k_history_columns; reads the history, writes `out` only.  Per pair the
+// way down (SumProduct::fillDown, src/sumprod.cpp:163-198) along the one path from the tree's root to the node: every
+// lane walks the same path and starts with insProb at the path node that is its column's root; the nodes between a
+// column's root and an ungapped node are ungapped (hx_history_create's contract), so a started lane multiplies at every
+// further step: G[r] = (G[parent] * E[sibling]) exp(R t)_r, logG[r] = logG[parent] + logE[sibling].  The branch matrix is
+// staged once per (pair, path node) and wave, skipped where no lane of the wave has started.  Then the profile, in the
+// reference's order of additions; row p of the pair's block is the node's p-th ungapped column.
+template <int TA>
+__global__ void __launch_bounds__(512) k_history_excluded(const HxArgs h) {
+  constexpr int AX = sp_ax<TA>;
+  const int A = TA ? TA : h.A, C = h.C, N = h.N, AA = A * A;
+  // The launch plan is hx_history_create's (sp_column_plan: the same waves, the same bytes), so the [C][64] likelihoods of
+  // k_history_columns lie in front of the matrices here too; this kernel does not touch them (512 C bytes idle: it costs
+  // occupancy at large C, where a plan of its own would fit more workgroups to a CU).
+  extern __shared__ double sh_ll[];                 // [C][64] (not used), then per wave [A * A]: exp(R t)
+  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, Wb = (int)blockDim.x >> 6;
+  HX_LDS double* Lsub = (HX_LDS double*)(sh_ll + 64 * C + AA * wave);
+  for (long long base = (long long)blockIdx.x * 64; base < h.n_cols; base += (long long)gridDim.x * 64) {
+    const bool busy = base + lane < h.n_cols;
+    const long long col = base + lane;               // (< ncp)
+    const SpBlock blk{base >> 6, C, N, (A + 1) & ~1, lane};
+    const int root = h.root[col];
+    for (int cpt = wave; cpt < C; cpt += Wb) {
+      CMat ins = cmat(h.ins_prob + cpt * A);
+      const double lcw = h.log_cpt_weight[cpt];
+      for (int k = 0; k < h.n_pairs; ++k) {
+        const int node = h.pair[4 * k], excl = h.pair[4 * k + 1], path_at = h.pair[4 * k + 2], path_len = h.pair[4 * k + 3];
+        const int tk = busy ? h.tok[node * h.ncp + col] : -2;
+        const bool live = tk != -2;
+        const unsigned long long present = __ballot(live);
+        if (!present) continue;                      // (the whole wave: the node is a gap in all 64 columns)
+        double g[AX];
+        double lg = 0.;
+        bool started = false;
+        for (int j = 0; path_at >= 0 && j < path_len; ++j) {
+          const int r = h.path[path_at + j];
+          const bool on = live && started;
+          if (live && r == root) {
+#pragma unroll
+            for (int a = 0; a < A; ++a) g[a] = ins[a];
+            started = true;
+          }
+          if (!__any(on)) continue;                  // (the whole wave; j = 0, the tree's root, always comes here)
+          const int inf = h.info[r];
+          wave_lds_sync();                           // (the reads of the previous matrix are done)
+          lds_stage<sp_rows<TA>>(Lsub, h.mats + ((((long long)(inf >> 1) & 1) * C + cpt) * N + r) * AA, A, lane);
+          wave_lds_sync();
+          if (!on) continue;
+          const int p = h.path[path_at + j - 1];
+          const int sib = h.child[2 * p] == r ? h.child[2 * p + 1] : h.child[2 * p];
+          double d[AX];
+#pragma unroll
+          for (int a = 0; a < A; ++a) d[a] = g[a];
+          if (sib >= 0 && h.tok[sib * h.ncp + col] != -2) {
+            const int ss = h.info[sib] & 1;
+            const long long ats = blk.node(cpt, sib);
+            lg += blk.lg(h.logE + ss * h.lg_slot, ats);
+            get_row<TA>(blk.row(h.E + ss * h.e_slot, ats), A, [&](const int a, const double e) { d[a] *= e; });
+          }
+          vec_mat<TA>(Lsub, A, d, g);
+        }
+        if (!live) continue;
+        const long long pos = h.block_off[node * h.n_blocks + blk.cb] + __builtin_popcountll(present & ((1ull << lane) - 1));
+        double* o = h.out + h.out_off[k] + (pos * C + cpt) * A;
+        // the children other than the excluded one that send a message (a gap's is all ones: log 1 + 0)
+        const int c0 = h.child[2 * node], c1 = h.child[2 * node + 1];
+        const bool h0 = c0 >= 0 && c0 != excl && h.tok[c0 * h.ncp + col] != -2, h1 = c1 >= 0 && c1 != excl && h.tok[c1 * h.ncp + col] != -2;
+        const int s0 = h0 ? h.info[c0] & 1 : 0, s1 = h1 ? h.info[c1] & 1 : 0;
+        const long long at0 = blk.node(cpt, c0), at1 = blk.node(cpt, c1);
+        const double* e0 = blk.row(h.E + s0 * h.e_slot, at0);
+        const double* e1 = blk.row(h.E + s1 * h.e_slot, at1);
+        const double l0 = h0 ? blk.lg(h.logE + s0 * h.lg_slot, at0) : 0., l1 = h1 ? blk.lg(h.logE + s1 * h.lg_slot, at1) : 0.;
+        const bool down = path_at >= 0;
+        if (tk >= 0) {
+          double v = 0. + lcw;
+          if (h0) v += log(sp_at(e0, tk)) + l0;
+          if (h1) v += log(sp_at(e1, tk)) + l1;
+          if (down) {
+            double gt = 0.;
+#pragma unroll
+            for (int a = 0; a < A; ++a) gt = a == tk ? g[a] : gt;
+            v += log(gt) + lg;
+          }
+          for (int a = 0; a < A; ++a) o[a] = a == tk ? v : HX_NEG_INF;
+          continue;
+        }
+        double v[AX];
+#pragma unroll
+        for (int a = 0; a < A; ++a) v[a] = 0. + lcw;
+        if (h0) get_row<TA>(e0, A, [&](const int a, const double e) { v[a] += log(e) + l0; });
+        if (h1) get_row<TA>(e1, A, [&](const int a, const double e) { v[a] += log(e) + l1; });
+#pragma unroll
+        for (int a = 0; a < A; ++a) o[a] = down ? v[a] + (log(g[a]) + lg) : v[a];
+      }
+    }
+  }
+}
+
+// The normalisation of the compacted profiles, a lane per position: norm is log_accum_exp folded over v[c][i], c major and
+// i minor, from -inf (src/sumprod.cpp:226, 242); then every entry has it subtracted.
+__global__ void __launch_bounds__(256) k_history_excluded_norm(const long long* __restrict__ out_off, const long long* __restrict__ out_len, const int n_pairs,
+                                                               const int row, double* __restrict__ out, const double* __restrict__ lse_tab) {
+  for (int k = (int)blockIdx.y; k < n_pairs; k += (int)gridDim.y) {
+    const long long len = out_len[k];
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < len; p += (long long)gridDim.x * blockDim.x) {
+      double* o = out + out_off[k] + p * row;
+      double norm = HX_NEG_INF;
+      for (int q = 0; q < row; ++q) norm = lse(norm, o[q], lse_tab);
+      for (int q = 0; q < row; ++q) o[q] -= norm;
+    }
+  }
+}
+
 }  // namespace
 
 }  // namespace hx
@@ -227,6 +379,11 @@ struct hx_history {
   size_t lds = 0;
   float ms = 0.f, expm_ms = 0.f;                      // of the last evaluation: all its kernels; k_branch_expm alone
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
+  // excluded-neighbour queries: the positions of every node (host, from the tokens at create), their block offsets on the
+  // device from the first query on, the query's plan and its output (both grow to the largest query so far)
+  std::vector<long long> row_len, block_off;
+  SpBuf d_block_off, query, xout;
+  size_t query_bytes = 0, xout_doubles = 0;
   ~hx_history() {
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);
@@ -390,6 +547,7 @@ int history_create(const char* fn, const hx_history_model* hm, const int8_t* tok
   h->A = A; h->C = C; h->N = N; h->device = device; h->n_cols = n_cols; h->ncp = ncp;
   h->parent.assign(hm->parent, hm->parent + N);
   h->child = child;
+  history_positions(tokT.data(), N, ncp, h->row_len, h->block_off);
   h->eslot.assign(N, 0);
   h->mslot.assign(N, 1);                             // (the first evaluation "changes" every branch: its matrices go to slot 0)
   h->tpb = 64 * plan.waves;
@@ -550,6 +708,113 @@ int hx_history_indel_counts(hx_history* h, int64_t* counts) {
   }
   if (hipMemcpy(counts, h->counts.p, (size_t)h->N * 12 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_history_indel_counts: copy failed");
+  return HX_OK;
+}
+
+int hx_history_row_lengths(hx_history* h, int64_t* len) {
+  if (!h || !len) return api_fail(HX_ERR_INVALID_ARG, "hx_history_row_lengths: null argument");
+  for (int r = 0; r < h->N; ++r) len[r] = h->row_len[r];
+  return HX_OK;
+}
+
+int hx_history_excluded_profiles(hx_history* h, int32_t which, int32_t n_pairs, const int32_t* node, const int32_t* exclude, int32_t normalize, double* const* out,
+                                 void* stream) {
+  const char* fn = "hx_history_excluded_profiles";
+  if (!h || !node || !exclude || !out || n_pairs <= 0 || (which != 0 && which != 1)) return sp_fail(HX_ERR_INVALID_ARG, fn, "null argument, no pairs, or `which` not 0 or 1");
+  const int N = h->N, C = h->C, A = h->A;
+  ExcludedPlan plan;
+  switch (history_excluded_plan(h->parent, h->row_len, (long long)C * A, n_pairs, node, exclude, plan)) {
+    case 1: return sp_fail(HX_ERR_RANGE, fn, "a node or neighbour outside 0 .. N - 1");
+    case 2: return sp_fail(HX_ERR_INVALID_ARG, fn, "an excluded neighbour that is neither the node's parent nor its child");
+    default: break;
+  }
+  for (int k = 0; k < n_pairs; ++k)
+    if (plan.out_len[k] > 0 && !out[k]) return sp_fail(HX_ERR_INVALID_ARG, fn, "null argument");
+  if (which == 1 && !h->pending) return sp_fail(HX_ERR_STATE, fn, "no proposal is pending");
+  const double* lse_tab = device_lse_table(h->device);
+  if (!lse_tab) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_history: hx_init has not been called for the history's device");
+  const SpPlan col_plan = sp_column_plan(A, C, 1, true);
+  if (col_plan.lds > HX_LDS_LIMIT) return sp_fail(HX_ERR_INVALID_ARG, fn, "the LDS plan exceeds the LDS of a CU");
+  if (plan.total == 0) {                             // (no node has a position: nothing to compute)
+    h->ms = h->expm_ms = 0.f;
+    return HX_OK;
+  }
+  // the slots of the state asked for: the pending proposal's messages of the walked nodes and matrices of the changed ones
+  // lie in the other slot (history_run's info words)
+  std::vector<int> info(N);
+  for (int r = 0; r < N; ++r) info[r] = h->eslot[r] | (h->mslot[r] << 1);
+  if (which == 1) {
+    for (int r : h->walked) info[r] ^= 1;
+    for (int r : h->changed) info[r] ^= 2;
+  }
+  // one block: the offsets and lengths (8-byte words first), the info words, the pairs, the paths
+  const size_t n_ll = 2 * (size_t)n_pairs, n_int = info.size() + plan.pair.size() + plan.path.size();
+  std::vector<long long> block(n_ll + (n_int + 1) / 2);
+  std::copy(plan.out_off.begin(), plan.out_off.end(), block.begin());
+  std::copy(plan.out_len.begin(), plan.out_len.end(), block.begin() + n_pairs);
+  int* words = reinterpret_cast<int*>(block.data() + n_ll);
+  std::copy(info.begin(), info.end(), words);
+  std::copy(plan.pair.begin(), plan.pair.end(), words + N);
+  std::copy(plan.path.begin(), plan.path.end(), words + N + plan.pair.size());
+  const size_t bytes = block.size() * sizeof(long long);
+  if (bytes > h->query_bytes) {
+    if (h->query.p) (void)hipFree(h->query.p);
+    h->query.p = nullptr;
+    h->query_bytes = 0;
+    if (hipMalloc(&h->query.p, bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    h->query_bytes = bytes;
+  }
+  if ((size_t)plan.total > h->xout_doubles) {
+    if (h->xout.p) (void)hipFree(h->xout.p);
+    h->xout.p = nullptr;
+    h->xout_doubles = 0;
+    if (hipMalloc(&h->xout.p, (size_t)plan.total * sizeof(double)) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    h->xout_doubles = (size_t)plan.total;
+  }
+  if (!h->d_block_off.p) {
+    const size_t off_bytes = h->block_off.size() * sizeof(long long);
+    if (hipMalloc(&h->d_block_off.p, off_bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    if (hipMemcpy(h->d_block_off.p, h->block_off.data(), off_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(h->d_block_off.p);
+      h->d_block_off.p = nullptr;
+      return sp_fail(HX_ERR_HIP, fn, "copy failed");
+    }
+  }
+  if (hipMemcpy(h->query.p, block.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  const long long* d_ll = static_cast<const long long*>(h->query.p);
+  const int* d_words = reinterpret_cast<const int*>(d_ll + n_ll);
+  HxArgs a;
+  a.A = A; a.C = C; a.N = N; a.n_pairs = n_pairs;
+  a.n_cols = h->n_cols; a.ncp = h->ncp; a.n_blocks = h->ncp / 64; a.e_slot = h->e_slot; a.lg_slot = h->lg_slot;
+  a.tok = static_cast<const signed char*>(h->tok.p);
+  a.root = h->d_root; a.child = h->d_child;
+  a.info = d_words; a.pair = d_words + N; a.path = d_words + N + plan.pair.size();
+  a.out_off = d_ll; a.block_off = static_cast<const long long*>(h->d_block_off.p);
+  a.ins_prob = h->d_ins; a.log_cpt_weight = h->d_lcw;
+  a.mats = static_cast<const double*>(h->mats.p);
+  a.E = static_cast<const double*>(h->E.p); a.logE = static_cast<const double*>(h->logE.p);
+  a.out = static_cast<double*>(h->xout.p);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long blocks64 = h->ncp / 64;
+  const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
+  const unsigned tpb = 64 * (unsigned)col_plan.waves;
+  (void)hipEventRecord(h->ev_a, st);
+  if (A == 4) hipLaunchKernelGGL(k_history_excluded<4>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
+  else if (A == 20) hipLaunchKernelGGL(k_history_excluded<20>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
+  else hipLaunchKernelGGL(k_history_excluded<0>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
+  if (normalize) {
+    const long long nb = (plan.max_len + 255) / 256;
+    hipLaunchKernelGGL(k_history_excluded_norm, dim3((unsigned)(nb > 65535 ? 65535 : nb), (unsigned)(n_pairs > 65535 ? 65535 : n_pairs)), dim3(256), 0, st, d_ll,
+                       d_ll + n_pairs, n_pairs, C * A, a.out, lse_tab);
+  }
+  (void)hipEventRecord(h->ev_b, st);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
+  (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
+  h->expm_ms = 0.f;
+  for (int k = 0; k < n_pairs; ++k)
+    if (plan.out_len[k] > 0 &&
+        hipMemcpy(out[k], a.out + plan.out_off[k], (size_t)plan.out_len[k] * C * A * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      return sp_fail(HX_ERR_HIP, fn, "copy failed");
   return HX_OK;
 }
 

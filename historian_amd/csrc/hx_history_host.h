@@ -84,4 +84,63 @@ inline int history_closure(const std::vector<int>& parent, const int n_changed, 
   return 0;
 }
 
+// ---- excluded-neighbour profiles (k_history_excluded): the host's share of a query ----
+
+// The positions of every node - the columns in which it is not a gap - and, per block of 64 columns, the position of the
+// block's first column.  tokT: [N][ncp] transposed tokens, -2 a gap (the padding past n_cols is gaps).
+// len: [N]; block_off: [N][ncp / 64].
+inline void history_positions(const signed char* tokT, const int N, const long long ncp, std::vector<long long>& len, std::vector<long long>& block_off) {
+  const long long n_blocks = ncp / 64;
+  len.assign(N, 0);
+  block_off.assign((size_t)N * n_blocks, 0);
+  for (int r = 0; r < N; ++r) {
+    long long at = 0;
+    for (long long b = 0; b < n_blocks; ++b) {
+      block_off[(size_t)r * n_blocks + b] = at;
+      const signed char* t = tokT + (size_t)r * ncp + b * 64;
+      for (int l = 0; l < 64; ++l) at += t[l] != -2;
+    }
+    len[r] = at;
+  }
+}
+
+// The plan of one query.  Per pair four words: the node, the excluded neighbour, where its path starts in `path` (-1: the
+// excluded neighbour is the parent, no way down is needed) and the path's length; the path runs from the tree's root to
+// the node, both included.  out_off / out_len: where the pair's [len][C][A] block starts in the output (in doubles) and
+// its rows.
+struct ExcludedPlan {
+  std::vector<int> pair, path;
+  std::vector<long long> out_off, out_len;
+  long long total = 0;               // doubles of output
+  long long max_len = 0;
+};
+// 0: fine; 1: a node or neighbour outside 0 .. N - 1; 2: a neighbour that is neither the node's parent nor its child.
+// parent: [N], children before parents, the root last; len: history_positions'; row: C * A.
+inline int history_excluded_plan(const std::vector<int>& parent, const std::vector<long long>& len, const long long row, const int n_pairs, const int* node,
+                                 const int* exclude, ExcludedPlan& plan) {
+  const int N = (int)parent.size();
+  plan = ExcludedPlan();
+  for (int k = 0; k < n_pairs; ++k)
+    if (node[k] < 0 || node[k] >= N || exclude[k] < 0 || exclude[k] >= N) return 1;
+  for (int k = 0; k < n_pairs; ++k)
+    if (parent[node[k]] != exclude[k] && parent[exclude[k]] != node[k]) return 2;
+  std::vector<int> up;
+  for (int k = 0; k < n_pairs; ++k) {
+    const int r = node[k];
+    const bool down = parent[r] != exclude[k];
+    plan.pair.push_back(r);
+    plan.pair.push_back(exclude[k]);
+    plan.pair.push_back(down ? (int)plan.path.size() : -1);
+    up.clear();
+    for (int p = r; down && p >= 0; p = parent[p]) up.push_back(p);
+    plan.pair.push_back((int)up.size());
+    plan.path.insert(plan.path.end(), up.rbegin(), up.rend());
+    plan.out_off.push_back(plan.total);
+    plan.out_len.push_back(len[r]);
+    plan.total += len[r] * row;
+    if (len[r] > plan.max_len) plan.max_len = len[r];
+  }
+  return 0;
+}
+
 }  // namespace hx

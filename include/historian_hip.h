@@ -24,7 +24,7 @@
  *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
  *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
  *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix, hx_distance_neg_log_like, hx_history_create,
- *     hx_history_create_from_lengths, hx_history_propose and hx_history_propose_lengths run their kernels on `stream` and return when they are done.
+ *     hx_history_create_from_lengths, hx_history_propose, hx_history_propose_lengths and hx_history_excluded_profiles run their kernels on `stream` and return when they are done.
  *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
  *     Forward launch (an event), with no host synchronisation.
  *   - Readers (results, matrices, cells, tracebacks, walks, counts) synchronise with the batch's LAST stream only - the stream
@@ -499,6 +499,25 @@ int hx_history_branch_matrix(hx_history* h, int32_t which, int32_t node, double*
 /* A measurement aid (tools/history_bench.py), not needed to use the history: the duration of k_branch_expm within the most
  * recent evaluation of this history (part of hx_history_last_kernel_ms); 0 when that evaluation brought its matrices. */
 int hx_history_last_expm_ms(hx_history* h, float* ms);
+
+/* Excluded-neighbour profiles of a live history: what TreeAlignFuncs::getConditionalPWMs (reference src/sampler.cpp:356-370)
+ * collects, SumProduct::logNodeExcludedPostProb (src/sumprod.cpp:219-250) of every column in which the node is not a gap -
+ * the profile of a node given everything on its side of a neighbour and nothing beyond it.  The way up is the history's
+ * own; the way down (fillDown, src/sumprod.cpp:163-198) runs along the one path from each column's root to the node.
+ * Nothing is written to the history; no atomics: two calls give the same bytes.
+ *
+ * len [N]: the positions of every node (the columns in which it is not a gap). */
+int hx_history_row_lengths(hx_history* h, int64_t* len);
+/* node[k], exclude[k]: exclude[k] is node[k]'s parent or one of its children.  out[k]: host memory for
+ * len[node[k]] * C * A doubles, [position][component][residue] (the layout of hx_branch_job::x_pwm); a node without positions
+ * gets nothing written and its out[k] may be NULL.  normalize != 0: every position has log_sum_exp over its C * A entries
+ * (the table of hx_init, component major) subtracted.  which: 0 the current state, 1 the pending proposal.  Runs on `stream`,
+ * returns when done; hx_history_last_kernel_ms then reports this query's kernels.  Refused before anything is launched, the
+ * stored state unchanged: HX_ERR_RANGE (a node or neighbour outside 0 .. N - 1), HX_ERR_INVALID_ARG (a null pointer,
+ * n_pairs <= 0, an exclude[k] that is neither parent nor child of node[k]), HX_ERR_STATE (which = 1 without a pending
+ * proposal). */
+int hx_history_excluded_profiles(hx_history* h, int32_t which, int32_t n_pairs, const int32_t* node,
+                                 const int32_t* exclude, int32_t normalize, double* const* out, void* stream);
 /* Host only, no device: (terms, squarings, shrink = 1. / exp(log(2.) * squarings)) of gsl_linalg_exponential_ss for a
  * matrix R t with max |R_ij| = max_abs_rate - the function the library itself shapes every k_branch_expm workgroup with.
  * Rounding is monotone and t >= 0, so max_ij |fl(R_ij t)| == fl(max_abs_rate * t), the norm getSubProbMatrix looks up.
