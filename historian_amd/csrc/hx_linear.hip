@@ -20,7 +20,8 @@
 //     since what was lost is below e^-D of what those cells hold;
 //   * lpEnd and lpStart are exact to fp64 rounding.
 // D = 1001 ln 2 - 7 ln(1 / phi) nats: 2^-1022, less the 2^20 by which a sum must exceed a term that trunc_sum dropped (its
-// low word, below 2^-1042, stays in the sum), less the factor 2 of a renormalised mantissa, less seven steps without a
+// low word, below 2^-1042, stays in the sum; under trunc_sum_masked, which the Forward fill of one workgroup per pair takes, a
+// dropped term contributes nothing and the 2^20 only makes D conservative), less the factor 2 of a renormalised mantissa, less seven steps without a
 // renormalisation (HXL_RENORM_MASK) at the model's smallest per-step factor phi = transition x emission on the best move out
 // of a cell's largest state (derivation: tests/param_edge_cases.py).  Such spreads arise where two states of a cell are the same
 // gap run taken by two routes - IDM and IMI on row 0, IMD and IIW in column 0, and their mirror images in the Backward matrix -
@@ -60,13 +61,29 @@ struct L5 { double imm, imd, idm, imi, iiw; int e; };
 #define HXL_EXP_M10 4.5399929762484854e-05      // e^-10
 __device__ __forceinline__ double trunc_sum(double a, double b) {
   const double hi = fmax_plain(a, b), lo = fmin_plain(a, b);
-  // (a dropped term keeps its low word: a number below 2^-1042, which a sum of at least 2^-1002 does not feel - states within
-  // D nats of their cell's largest, see the header - one select instead of two)
+  // (a dropped term keeps its low word: a number below 2^-1042, which a sum of at least 2^-1002 does not feel - one select
+  // instead of two.  The form of the instantiations that do not take trunc_sum_masked)
   const int keep = lo > hi * HXL_EXP_M10 ? __double2hiint(lo) : 0;
   return hi + __hiloint2double(keep, __double2loint(lo));
 }
+// The same sum without the select: the smaller term is ADDED ONLY IN THE LANES THAT KEEP IT - max, min, multiply, compare, add:
+// five vector instructions where trunc_sum takes six, and a dropped term contributes nothing at all.  The comparison, its
+// operands and their rounding are trunc_sum's, so the same terms are dropped.  The compare writes EXEC, the add runs under it,
+// and EXEC is put back from `all`: the caller's EXEC as read once per step, never a literal -1.  One asm block per sum, not
+// volatile, so the scheduler still interleaves whole blocks of independent chains.  The hazard recogniser does not look into
+// the block; what it would have covered: a VALU write of EXEC needs five wait states before a DPP instruction - `step` puts an
+// s_nop 4 in front of its DPP group; VCC, which the e32 compare writes as well, is declared clobbered.
+// vmax / vmin, not fmax_plain / fmin_plain: `a` is the previous sum's asm result, which the compiler's own maximum would first
+// canonicalise with a v_max_f64 a, a - the instruction this form is there to save (16 of them per step pair).
+__device__ __forceinline__ double trunc_sum_masked(double a, double b, const uint64_t all) {
+  double r = vmax(a, b);
+  const double lo = vmin(a, b), thr = r * HXL_EXP_M10;
+  asm("v_cmpx_gt_f64_e32 vcc, %1, %2\n\tv_add_f64 %0, %0, %1\n\ts_mov_b64 exec, %3" : "+v"(r) : "v"(lo), "v"(thr), "s"(all) : "vcc");
+  return r;
+}
 // acc (+) m * p
-template <bool TRUNC> __device__ __forceinline__ double lin_acc(double m, double p, double acc) {
+template <bool TRUNC, bool MSUM = false> __device__ __forceinline__ double lin_acc(double m, double p, double acc, const uint64_t all = 0) {
+  if (TRUNC && MSUM) return trunc_sum_masked(acc, m * p, all);
   if (TRUNC) return trunc_sum(acc, m * p);
   return __builtin_fma(m, p, acc);
 }
@@ -167,6 +184,10 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
   // the compiler's schedule: it holds all 18 transition probabilities in scalar registers to the end of the step, and the
   // uniform strip's further scalars would be spilled and reloaded inside the step loop (measured: 9.4 -> 9.7 ms on 256 pairs).
   constexpr bool RESCHED = DIR == 0;
+  // Which truncated sum: trunc_sum_masked where it measured faster - the Forward fill of one
+  // workgroup per pair.  With several workgroups per pair (two waves per SIMD) it measured 6 % SLOWER; the Backward fill
+  // and the banded instantiations keep trunc_sum as well.
+  constexpr bool MSUM = TRUNC && DIR == 0 && !BANDED && !MULTI;
   constexpr int RING_ENTRIES = BANDED ? 0 : W * HXL_RING;  // (a banded pair is one wave: every strip boundary is the wrap-around link)
   typedef double d2v __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -412,6 +433,8 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     };
     // one anti-diagonal step: the lane's new cell from left (own previous), u1 = (i-1, j), u2 = (i-1, j-1)
     auto step = [&](const int t, const L5& left, L5& out, L5& u1, L5& u2, const unsigned w) {
+      const uint64_t all = MSUM ? __builtin_amdgcn_read_exec() : 0;   // (what trunc_sum_masked puts back into EXEC)
+      const auto sum = [&](const double m, const double p, const double acc) { return lin_acc<TRUNC, MSUM>(m, p, acc, all); };
       if (!lds_words && (t & 63) == 62) refill_words(t + 2 + 128);   // (steps from t+2 on read up to index t+2+127)
       if ((t & 7) == 7 && has_above && t + 1 < Cc) {
         if (wrap_in) {
@@ -433,10 +456,10 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         // (row0-1, t+1), lane 0's upper neighbour of the next step, which the other four chains then cover.
         // Unconditional: past the last column it returns a stale entry, which only feeds cells outside the lattice.
         double s_imm = u2.imm * P[0][0];
-        s_imm = lin_acc<TRUNC>(u2.imd, P[1][0], s_imm);
-        s_imm = lin_acc<TRUNC>(u2.idm, P[2][0], s_imm);
-        s_imm = lin_acc<TRUNC>(u2.imi, P[3][0], s_imm);
-        s_imm = lin_acc<TRUNC>(u2.iiw, P[4][0], s_imm);
+        s_imm = sum(u2.imd, P[1][0], s_imm);
+        s_imm = sum(u2.idm, P[2][0], s_imm);
+        s_imm = sum(u2.imi, P[3][0], s_imm);
+        s_imm = sum(u2.iiw, P[4][0], s_imm);
         const int e_diag = u2.e;
         __builtin_amdgcn_sched_barrier(0);
         u2 = ring_entry(t + 1);
@@ -445,15 +468,15 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         double s_iiw = u1.imm * P[0][4];
         double s_idm = left.imm * P[0][2];
         double s_imi = left.imm * P[0][3];
-        s_imd = lin_acc<TRUNC>(u1.imd, P[1][1], s_imd);
-        s_iiw = lin_acc<TRUNC>(u1.imi, P[3][4], s_iiw);
-        s_idm = lin_acc<TRUNC>(left.imd, P[1][2], s_idm);
-        s_imi = lin_acc<TRUNC>(left.imi, P[3][3], s_imi);
-        s_imd = lin_acc<TRUNC>(u1.idm, P[2][1], s_imd);
-        s_iiw = lin_acc<TRUNC>(u1.iiw, P[4][4], s_iiw);
-        s_idm = lin_acc<TRUNC>(left.idm, P[2][2], s_idm);
-        s_imd = lin_acc<TRUNC>(u1.imi, P[3][1], s_imd);
-        s_idm = lin_acc<TRUNC>(left.iiw, P[4][2], s_idm);
+        s_imd = sum(u1.imd, P[1][1], s_imd);
+        s_iiw = sum(u1.imi, P[3][4], s_iiw);
+        s_idm = sum(left.imd, P[1][2], s_idm);
+        s_imi = sum(left.imi, P[3][3], s_imi);
+        s_imd = sum(u1.idm, P[2][1], s_imd);
+        s_iiw = sum(u1.iiw, P[4][4], s_iiw);
+        s_idm = sum(left.idm, P[2][2], s_idm);
+        s_imd = sum(u1.imi, P[3][1], s_imd);
+        s_idm = sum(left.iiw, P[4][2], s_idm);
         // common exponent of the new cell, and the three groups brought to it; a state that may not be entered
         // (y or x state not ready: src/forward.cpp:97,133) is shifted out of the fp64 range, i.e. to zero
         E = left.e > u1.e ? left.e : u1.e;
@@ -494,11 +517,11 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         const double d1x = __builtin_ldexp(t1x, du), d2x = __builtin_ldexp(t2x, du);
         const double d1y = __builtin_ldexp(t1y, dl), d2y = __builtin_ldexp(t2y, dl);
         // (the reference accumulates term by term, in this order: src/forward.cpp:1018-1065)
-        out.imm = lin_acc<TRUNC>(P[0][3], d2y, lin_acc<TRUNC>(P[0][2], d1y, lin_acc<TRUNC>(P[0][4], d2x, lin_acc<TRUNC>(P[0][1], d1x, P[0][0] * D))));
-        out.imd = lin_acc<TRUNC>(P[1][2], d1y, lin_acc<TRUNC>(P[1][1], d1x, P[1][0] * D));
-        out.idm = lin_acc<TRUNC>(P[2][2], d1y, lin_acc<TRUNC>(P[2][1], d1x, P[2][0] * D));
-        out.imi = lin_acc<TRUNC>(P[3][3], d2y, lin_acc<TRUNC>(P[3][4], d2x, lin_acc<TRUNC>(P[3][1], d1x, P[3][0] * D)));
-        out.iiw = lin_acc<TRUNC>(P[4][2], d1y, lin_acc<TRUNC>(P[4][4], d2x, P[4][0] * D));
+        out.imm = sum(P[0][3], d2y, sum(P[0][2], d1y, sum(P[0][4], d2x, sum(P[0][1], d1x, P[0][0] * D))));
+        out.imd = sum(P[1][2], d1y, sum(P[1][1], d1x, P[1][0] * D));
+        out.idm = sum(P[2][2], d1y, sum(P[2][1], d1x, P[2][0] * D));
+        out.imi = sum(P[3][3], d2y, sum(P[3][4], d2x, sum(P[3][1], d1x, P[3][0] * D)));
+        out.iiw = sum(P[4][2], d1y, sum(P[4][4], d2x, P[4][0] * D));
       }
       out.e = E;
       if ((t & HXL_RENORM_MASK) == 0) {            // wave-uniform
@@ -541,6 +564,12 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
           asm volatile("" ::: "memory");           // data before flag
           if (lane == 63) progp[wave] = my_base + col + 1;   // (LDS operations of a wave complete in order)
         }
+      }
+      if (MSUM) {
+        // five wait states between the last sum's write of EXEC and the DPP group (see trunc_sum_masked)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_nop 4");
+        __builtin_amdgcn_sched_barrier(0);
       }
       u2 = dpp_shr1_old(u2, out);
     };
