@@ -109,7 +109,7 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_host_free", "hx_quick_batch_create", "hx_quick_batch_destroy", "hx_quick_batch_run",
            "hx_quick_batch_results", "hx_quick_batch_layout", "hx_quick_batch_read_matrix",
            "hx_quick_batch_total_cells", "hx_quick_batch_last_kernel_ms", "hx_sumprod_columns", "hx_sumprod_last_kernel_ms", "hx_sumprod_ancestors",
-           "hx_batch_read_matrix_async", "hx_batch_wait_read", "hx_batch_indel_counts", "hx_batch_event_counts", "hx_batch_shared_wavefront_pairs", "hx_batch_relaunches",
+           "hx_batch_read_matrix_async", "hx_batch_wait_read", "hx_batch_indel_counts", "hx_batch_event_counts", "hx_batch_shared_wavefront_pairs", "hx_batch_relaunches", "hx_batch_forward_folded",
            "hx_branch_batch_create", "hx_branch_batch_destroy", "hx_branch_batch_run", "hx_branch_batch_results",
            "hx_branch_batch_read_matrix", "hx_branch_batch_total_cells", "hx_branch_batch_last_kernel_ms",
            "hx_sibling_batch_create", "hx_sibling_batch_destroy", "hx_sibling_batch_run", "hx_sibling_batch_results",
@@ -168,6 +168,8 @@ def load():
     lib.hx_batch_total_cells.argtypes = [vp]
     lib.hx_batch_shared_wavefront_pairs.argtypes = [vp]
     lib.hx_batch_relaunches.argtypes = [vp]
+    if hasattr(lib, "hx_batch_forward_folded"):      # (absent from an older library selected with HX_LIB_PATH)
+        lib.hx_batch_forward_folded.argtypes = [vp]
     lib.hx_batch_total_cells.restype = C.c_int64
     lib.hx_batch_last_kernel_ms.argtypes = [vp, C.c_int32, C.POINTER(C.c_float)]
     lib.hx_quick_batch_create.argtypes = [C.POINTER(HxQuickJob), C.c_int32, C.POINTER(vp)]
@@ -423,6 +425,13 @@ class Batch:
     def relaunches(self):
         """fills repeated with one workgroup per pair after waves of a several-workgroups launch gave up"""
         return int(load().hx_batch_relaunches(self._h))
+
+    def forward_folded(self):
+        """whether the last Forward fill of the unbanded scaled-probability leaf pairs ran hx_linear.hip's FOLD instantiation"""
+        n = load().hx_batch_forward_folded(self._h)
+        if n < 0:
+            _check(n)
+        return bool(n)
 
     def kernel_ms(self, which=0):
         ms = C.c_float()

@@ -582,6 +582,7 @@ struct hx_batch {
   int64_t total_cells = 0;
   bool forward_done = false, backward_done = false;
   bool used_multi[2] = {false, false};   // the last Forward / Backward launch dealt some pair to several workgroups
+  bool forward_folded = false;           // the last Forward launch of unbanded scaled-probability leaf pairs took hx_linear.hip's FOLD instantiation
   bool no_multi = false;                 // ... which once failed (waves gave up waiting for one another): one workgroup per pair from now on
   int relaunches = 0;                    // fills repeated for that reason
   bool sub_scattered = false;        // subx / suby of table-emission jobs exist per state (k_scatter_sub, on demand)
@@ -1308,6 +1309,34 @@ static int fill_band_sweep(hx_batch* b, const ClassRange& cr, int dir, hipStream
 // The strip pipelines of leaf and chain classes: scaled probabilities (hx_linear.hip) for leaf pairs whose y side fits LDS
 // under HX_LSE_LINEAR, else table log-sum-exps (hx_chain.hip).  A small batch of unbanded such pairs (one rank's share of a
 // strong-scaling run) is dealt to several workgroups per pair.
+// Whether the unbanded scaled-probability Forward fill may write its chains relative to their first transitions (hx_linear.hip
+// FOLD) for these jobs: r[a][d] = exp(T[a][d] - T[0][d]) takes the place of the transition probabilities and the pivot P[0][d]
+// moves into the multiplier of the chain's sum.  Admitted when, for every job, every pivot and every used ratio is within
+// HX_FOLD_MAX_NATS of 1:
+//   * the chain's terms m r[a][d] are the parent's m P[a][d] over the pivot: at least as large (pivot <= 1: nothing underflows
+//     that did not) and at most e^B times a mantissa (nothing overflows);
+//   * the multiplier is the parent's times the pivot: at most B nats smaller; the product of sum and multiplier is the parent's.
+// So at most B nats of fp64's range move from the multiplier to the chain.  The contract's D (hx_linear.hip, header comment;
+// tests/param_edge_cases.py) keeps 2^20 = 13.86 nats between a sum and a term that trunc_sum dropped; the launches that fold -
+// one workgroup per pair: trunc_sum_masked, where a dropped term contributes nothing, or no truncation at all - do not use
+// them.  B = 10 ln 2 takes half of that slack (the protein models of bench.py and the tests need 6.3 nats: the pivot of a
+// gap-opening transition).  Any other model - and every launch of several workgroups per pair - runs the unfolded code.
+#define HX_FOLD_MAX_NATS 6.931471805599453
+static bool linear_fold_admits(const hx_batch* b, const ClassRange& cr) {
+  if (const char* v = getenv("HX_LINEAR_FOLD")) if (atoi(v) == 0) return false;     // tuning / test hook
+  for (int q = 0; q < cr.n; ++q) {
+    const DevJob& J = b->jobs[b->order[cr.begin + q]];
+    for (int d = 0; d < 5; ++d) {
+      if (!(J.T[0][d] <= 0.0 && J.T[0][d] >= -HX_FOLD_MAX_NATS)) return false;        // (NaN and -inf fail as well)
+      for (int a = 1; a < 5; ++a) {
+        const bool used = d == 0 || (d == 1 && a != 4) || (d == 2 && a != 3) || (d == 3 && a == 3) || (d == 4 && (a == 3 || a == 4));
+        if (used && !(fabs(J.T[a][d] - J.T[0][d]) <= HX_FOLD_MAX_NATS)) return false;
+      }
+    }
+  }
+  return true;
+}
+
 static int fill_strips(hx_batch* b, int c, int dir, hipStream_t st) {
   const DeviceTables& D = g_dev[b->device];
   const ClassRange& cr = b->cls[c];
@@ -1321,9 +1350,14 @@ static int fill_strips(hx_batch* b, int c, int dir, hipStream_t st) {
     int rc;
     if ((rc = zeroed_counters(b, dir, (size_t)cr.n * 256, st, &counters)) != HX_OK) return rc;
   }
-  if (b->pol.linear && leaf == 2)
-    LAUNCH_TRY((dir ? launch_backward_leaf_linear : launch_forward_leaf_linear)(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab},
-                                                                                cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi, counters, b->pol.trunc, st));
+  if (b->pol.linear && leaf == 2 && dir == 0) {
+    const bool fold = !banded && multi <= 1 && linear_fold_admits(b, cr);
+    if (!banded) b->forward_folded = fold;
+    LAUNCH_TRY(launch_forward_leaf_linear(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab}, cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi,
+                                          counters, b->pol.trunc, fold, st));
+  } else if (b->pol.linear && leaf == 2)
+    LAUNCH_TRY(launch_backward_leaf_linear(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab}, cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi,
+                                           counters, b->pol.trunc, st));
   else
     LAUNCH_TRY((dir ? launch_backward_chain : launch_forward_chain)(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, leaf, banded,
                                                                     cr.yl_cols, cr.yl_emis, multi, counters, st));
@@ -1377,6 +1411,10 @@ int hx_batch_forward(hx_batch* b, void* stream) {
   LAUNCH_TRY(launch_prep(b->d_jobs, b->n_jobs, b->max_states, b->max_cls, b->max_ca, b->max_cls_pairs, Tab8{D.tab}, records_now, st));
   b->records_valid = records_now;
   b->used_multi[0] = false;
+  // test hook: every byte of the Forward matrices is 0xFF (a NaN) in front of the fills, so that a slot a fill does not write
+  // can be told from one it does (tests/test_gpu_linear_padding.py)
+  if (const char* v = getenv("HX_POISON_MATRIX"))
+    if (atoi(v) != 0) HIP_TRY(hipMemsetAsync(b->d_fwd, 0xFF, sizeof(double) * (size_t)b->fwd_total, st));
   HIP_TRY(hipEventRecord(b->ev[0][0], st));
   // per-cell emission terms of the jobs without a class-pair table (general profiles).  Part of the fill:
   // the reference evaluates them inside its fill loop, so the launch is inside the timed region.
@@ -1535,6 +1573,11 @@ static int read_lp(hx_batch* b, double* out, int which) {
 }
 int hx_batch_lp_end(hx_batch* b, double* out) { return read_lp(b, out, 0); }
 int hx_batch_lp_start(hx_batch* b, double* out) { return read_lp(b, out, 1); }
+
+int hx_batch_forward_folded(const hx_batch* b) {
+  if (const int rc = check_reader(b, true, nullptr)) return rc;
+  return b->forward_done && b->forward_folded ? 1 : 0;
+}
 
 int hx_batch_relaunches(const hx_batch* b) {
   if (const int rc = check_reader(b, true, nullptr)) return rc;

@@ -65,7 +65,7 @@ void launch_gather_cells(const DevJob* d_jobs, int job, const double* M, int mir
 int log_table_doubles();
 void build_log_table(double* out /* [log_table_doubles()] */);
 int launch_forward_leaf_linear(const DevJob* d_jobs, int n_jobs, int max_rows, bool banded, Tab8 tab, Tab16 log_tab,
-                                int yl_cols, int yl_emis, int yl_cls, int multi, int* counters, bool trunc, hipStream_t st);
+                                int yl_cols, int yl_emis, int yl_cls, int multi, int* counters, bool trunc, bool fold, hipStream_t st);
 
 int launch_backward_leaf_linear(const DevJob* d_jobs, int n_jobs, int max_rows, bool banded, Tab8 tab, Tab16 log_tab,
                                  int yl_cols, int yl_emis, int yl_cls, int multi, int* counters, bool trunc, hipStream_t st);

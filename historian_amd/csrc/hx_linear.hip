@@ -21,7 +21,7 @@
 //   * lpEnd and lpStart are exact to fp64 rounding.
 // D = 1001 ln 2 - 7 ln(1 / phi) nats: 2^-1022, less the 2^20 by which a sum must exceed a term that trunc_sum dropped (its
 // low word, below 2^-1042, stays in the sum; under trunc_sum_masked, which the Forward fill of one workgroup per pair takes, a
-// dropped term contributes nothing and the 2^20 only makes D conservative), less the factor 2 of a renormalised mantissa, less seven steps without a
+// dropped term contributes nothing and the 2^20 only makes D conservative; FOLD spends 2^10 of it), less the factor 2 of a renormalised mantissa, less seven steps without a
 // renormalisation (HXL_RENORM_MASK) at the model's smallest per-step factor phi = transition x emission on the best move out
 // of a cell's largest state (derivation: tests/param_edge_cases.py).  Such spreads arise where two states of a cell are the same
 // gap run taken by two routes - IDM and IMI on row 0, IMD and IIW in column 0, and their mirror images in the Backward matrix -
@@ -33,7 +33,12 @@
 // waves round-robin, lane <-> row, step <-> anti-diagonal, up/diag neighbours by DPP wave_shr:1, the whole y side in LDS,
 // two steps per iteration so that a lane stores 16 contiguous bytes per state plane.  Unlike there, the strip above's
 // last row travels between waves through LDS rings (mantissas + exponent); only the link from the last wave to the first
-// wave's next strip goes through the matrix.  Variants: banded batches (one wavefront per pair over the strips' step
+// wave's next strip goes through the matrix.  The unbanded Forward fill stores only the 128-byte lines of a step pair that hold
+// a lattice cell (MASKED: the strips' skew triangles and the dead rows of a matrix's last strip are never written, and no reader
+// addresses them), ends a matrix's last strip with its last live row, and - for models whose transitions lie within e^+-6.93 of
+// one another, one workgroup per pair - writes each of the five chains of a cell relative to its first transition (FOLD: the
+// chain's first product moves into a multiplier that the sum meets anyway; hx_api.hip linear_fold_admits).
+// Variants: banded batches (one wavefront per pair over the strips' step
 // windows, band-compressed planes, several pairs per workgroup) and the Backward fill (mirrored sweep).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -172,13 +177,14 @@ struct LdsPlan { int elds, ycol, yclass, flags, zero;   // inside block A
 // counter in memory (`counters`: 256 zeroed ints per pair, one per workgroup, [255] = a poll gave up), `sc1` polls that give
 // up after HXL_PATIENCE rounds (the pair's lpEnd / lpStart becomes NaN).  As k_fill_chain's MULTI (hx_chain.hip).
 #define HXL_PATIENCE (1 << 22)
-template <int W, bool BANDED, int PPW, int DIR, bool MULTI = false, bool TRUNC = false>
+template <int W, bool BANDED, int PPW, int DIR, bool MULTI = false, bool TRUNC = false, bool FOLD = false>
 __global__ void __launch_bounds__(W * PPW * 64, 4)   // four waves per SIMD: 128 vector registers
 k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ exact_tab, const double* __restrict__ log_tab,
                       const LdsPlan plan, const int n_jobs, const int groups = 1, int* const counters = nullptr) {
   static_assert(!MULTI || (!BANDED && PPW == 1 && W > 1), "several workgroups per pair: unbanded pairs, one pair per workgroup");
   static_assert(!BANDED || W == 1, "banded batches run one wavefront per pair");
   static_assert(PPW == 1 || BANDED, "several pairs per workgroup: banded batches only");
+  static_assert(!FOLD || (DIR == 0 && !BANDED && !MULTI), "chains relative to their first transition: the unbanded Forward fill of one workgroup per pair");
   constexpr int THREADS = W * PPW * 64, PT = W * 64;       // threads of the workgroup / of a pair
   // The Forward fill's step pair is hand-scheduled (step_pair below) on a wave-uniform strip number.  The Backward fill keeps
   // the compiler's schedule: it holds all 18 transition probabilities in scalar registers to the end of the step, and the
@@ -188,6 +194,9 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
   // workgroup per pair.  With several workgroups per pair (two waves per SIMD) it measured 6 % SLOWER; the Backward fill
   // and the banded instantiations keep trunc_sum as well.
   constexpr bool MSUM = TRUNC && DIR == 0 && !BANDED && !MULTI;
+  // The unbanded Forward fill stores only the lanes of a step pair that hold a lattice cell (see `put`), and ends a matrix's
+  // last strip with its last live row.  The Backward fill and the banded instantiations write their strips' padding as before.
+  constexpr bool MASKED = DIR == 0 && !BANDED;
   constexpr int RING_ENTRIES = BANDED ? 0 : W * HXL_RING;  // (a banded pair is one wave: every strip boundary is the wrap-around link)
   typedef double d2v __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -238,8 +247,9 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     for (int c = tid; c < Ky1; c += PT) {
       const bool real = c < J.y.n_cls;
       const int rep = real ? J.y.cls_rep[c] : 0;
-      yclass[2 * c] = real ? exp(J.y.pack[4 * (size_t)rep + 1]) : 0.;
-      yclass[2 * c + 1] = real ? exp(J.y.pack[4 * (size_t)rep + 2]) : 0.;
+      // (FOLD: the pivots of the IDM and IMI chains, P[0][2] and P[0][3], go into the multipliers of their sums)
+      yclass[2 * c] = real ? (FOLD ? exp(J.y.pack[4 * (size_t)rep + 1] + J.T[0][2]) : exp(J.y.pack[4 * (size_t)rep + 1])) : 0.;
+      yclass[2 * c + 1] = real ? (FOLD ? exp(J.y.pack[4 * (size_t)rep + 2] + J.T[0][3]) : exp(J.y.pack[4 * (size_t)rep + 2])) : 0.;
     }
     for (int e = tid; e < Kx1 * Ky1; e += PT) elds[e] = exp(J.emis_pad[e]);
   }
@@ -259,8 +269,8 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     for (int d = 0; d < 5; ++d) {
       const bool used = d == 0 || (d == 1 && a != 4) || (d == 2 && a != 3) || (d == 3 && (a == 0 || a == 3)) ||
                         (d == 4 && (a == 0 || a == 3 || a == 4));
-      if (!used) { P[a][d] = 0.; continue; }
-      const double pv = exp(J.T[a][d]);            // (wave-uniform, but computed by the vector unit)
+      if (!used || (FOLD && a == 0)) { P[a][d] = 0.; continue; }     // (FOLD: the pivots are never read)
+      const double pv = FOLD ? exp(J.T[a][d] - J.T[0][d]) : exp(J.T[a][d]);            // (wave-uniform, but computed by the vector unit)
       double v = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(pv)), __builtin_amdgcn_readfirstlane(__double2loint(pv)));
       asm volatile("" : "+s"(v));
       P[a][d] = v;
@@ -322,9 +332,10 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
       // Forward: the state's own in-transition, rootsubx, insx.  Backward: those of state ic+1, which an absorbing
       // move leads to; the readiness test is the row's own state's in both directions.
       const d4v q = DIR ? xpack[ic + 1] : p;
-      fx = row_valid ? exp(q.x) : 0.;
-      f_imd = row_valid ? exp(q.x + q.y) : 0.;
-      f_iiw = row_valid ? exp(q.x + q.z) : 0.;
+      // (FOLD: the pivots of the IMM, IMD and IIW chains, P[0][0], P[0][1] and P[0][4], go into the multipliers of their sums)
+      fx = row_valid ? (FOLD ? exp(q.x + J.T[0][0]) : exp(q.x)) : 0.;
+      f_imd = row_valid ? (FOLD ? exp(q.x + q.y + J.T[0][1]) : exp(q.x + q.y)) : 0.;
+      f_iiw = row_valid ? (FOLD ? exp(q.x + q.z + J.T[0][4]) : exp(q.x + q.z)) : 0.;
       x_wait = (row_valid && !(p.w < 0.0)) ? 0 : (1 << 29);
       eoff = (unsigned)J.x.ecls[DIR ? ic + 1 : ic] * (unsigned)(J.y.n_cls + 1);
       if (BANDED) {
@@ -342,7 +353,13 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     const int my_base = (s / WT) * Cc;
     int64_t store_base = (int64_t)s * ss;          // (wave-uniform; the lane adds its 16 bytes)
     int store_t0 = 0;                              // (band-compressed storage: a window's cells are stored from its own offset)
-    const int nsteps = (Cc + 64) & ~1;             // Cc + 63 anti-diagonals, rounded up to whole step pairs
+    // Cc + 63 anti-diagonals, rounded up to whole step pairs.  The unbanded Forward fill ends the sweep of a matrix's last strip
+    // where its last live row does (row R - 1 finishes column Cc - 1 at step Cc + (R - row0) - 2): the steps after it compute
+    // dead rows only, and the last strip of the pair's last wave is the tail of the kernel.  A last strip hands nothing on
+    // (no ring_out, no wrap_out: `fin` and publish_drained below are not reached), so nothing else counts on those steps.
+    // MASKED keeps the count unrounded - the step loop advances by two either way - because the strip's last live lane is
+    // then nsteps - Cc, and the store mask needs no scalar register of its own for it.
+    const int nsteps = MASKED ? Cc + (R - row0 > 64 ? 63 : R - row0 - 1) : (Cc + 64) & ~1;
 
     // The strip above's last row arrives through that wave's LDS ring, one cell {5 mantissas, exponent} per
     // column: the producer's lane 63 writes it the moment it is computed, lane 0 of this wave needs it 64 + a few
@@ -452,10 +469,15 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
       int E;
       if (DIR == 0) {
       // the five sums of src/forward.cpp:103-115,139-150,171-180 on probabilities
+        // FOLD: each chain relative to its first transition.  With r[a][d] = exp(T[a][d] - T[0][d]) (held in P's registers),
+        //   m0 P[0][d] (+) m1 P[1][d] (+) ...  =  P[0][d] (m0 (+) m1 r[1][d] (+) ...):
+        // trunc_sum's test lo > hi e^-10 does not change when both operands are scaled by one positive factor, so the same
+        // terms are dropped, in the same left-nested order.  The pivot P[0][d] sits in the multiplier that the sum meets anyway
+        // (fx, f_imd, f_iiw per strip, the two yclass entries), and the chain's first product - five v_mul_f64 per cell - is gone.
         // the diagonal cell's chain first: its registers are free after five products and take the ring entry
         // (row0-1, t+1), lane 0's upper neighbour of the next step, which the other four chains then cover.
         // Unconditional: past the last column it returns a stale entry, which only feeds cells outside the lattice.
-        double s_imm = u2.imm * P[0][0];
+        double s_imm = FOLD ? u2.imm : u2.imm * P[0][0];
         s_imm = sum(u2.imd, P[1][0], s_imm);
         s_imm = sum(u2.idm, P[2][0], s_imm);
         s_imm = sum(u2.imi, P[3][0], s_imm);
@@ -464,10 +486,10 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         __builtin_amdgcn_sched_barrier(0);
         u2 = ring_entry(t + 1);
         __builtin_amdgcn_sched_barrier(0);
-        double s_imd = u1.imm * P[0][1];
-        double s_iiw = u1.imm * P[0][4];
-        double s_idm = left.imm * P[0][2];
-        double s_imi = left.imm * P[0][3];
+        double s_imd = FOLD ? u1.imm : u1.imm * P[0][1];
+        double s_iiw = FOLD ? u1.imm : u1.imm * P[0][4];
+        double s_idm = FOLD ? left.imm : left.imm * P[0][2];
+        double s_imi = FOLD ? left.imm : left.imm * P[0][3];
         s_imd = sum(u1.imd, P[1][1], s_imd);
         s_iiw = sum(u1.imi, P[3][4], s_iiw);
         s_idm = sum(left.imd, P[1][2], s_idm);
@@ -599,6 +621,7 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     // a pair of steps: in the strip-skewed layout its two cells per row are adjacent, 16 bytes per lane and state plane
     auto step_pair = [&](const int t) {
       if (RESCHED) {
+        const uint64_t all_lanes = MASKED ? __builtin_amdgcn_read_exec() : 0;   // (what the masked stores put back into EXEC)
         // The first cell's table reads are covered by step(t + 1); the second cell's go out two at a time under the arithmetic
         // of the first cell's logarithms (the barriers keep the compiler from gathering them behind it).
         step(t, cb, ca, ua, ub, next_word(t));
@@ -625,9 +648,36 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
           // memory): non-temporal stores - 17.4 -> 15.8 ms on the headline workload with separate state planes; with the
           // interleaved layout (5 KiB contiguous per iteration) they measure the same as plain stores.
           // MULTI: the strip below may run on another XCD: write-through stores (never `nt`, which stays in this XCD's L2)
+          // MASKED: only the lanes that hold a lattice cell store.  Lane l's two cells of this step pair are columns t - l and
+          // t + 1 - l of row row0 + l, so it has something to store iff l <= t + 1, l >= t - Cc + 1 and l <= last_lane: one
+          // contiguous range of lanes, wave-uniform, built by the scalar unit (two shifts and an and; no vector instruction),
+          // and widened to whole 128-byte lines (eight lanes of a state plane; matrices are 1 KiB-aligned), so that no line
+          // is written in part: the lane-exact range measured 1.6 % slower under the untruncated policy (DESIGN.md section 7,
+          // round 14).  The lines of the skew triangles at either end of a strip and of the dead rows of a matrix's last
+          // strip - about 5 % of the headline's bytes - are never written; no reader addresses them (every reader goes from a
+          // lattice cell through cell_slot_blk).  Each store is one asm
+          // block that narrows EXEC, stores and puts EXEC back from the value read at the top of the step pair (never a
+          // literal, as trunc_sum_masked): no instruction of the compiler's runs under the narrowed mask.  The wrap-around
+          // link's count below ("five stores per iteration") counts store INSTRUCTIONS, which stay five; and a strip that
+          // publishes is never a last strip, so with t <= Cc + 62 none of its step pairs has an empty range.
+          uint64_t keep = 0;
+          if (MASKED) {
+            int n = wend;                       // (opaque: nsteps - Cc is taken here, not kept in a register of its own)
+            asm volatile("" : "+s"(n));
+            const int last_lane = n - Cc;
+            int hi = t + 1 < last_lane ? t + 1 : last_lane, lo = t + 1 - Cc > 0 ? t + 1 - Cc : 0;
+            hi |= 7; lo &= ~7;                  // whole 128-byte lines: groups of eight lanes
+            keep = ((~0ull >> (63 - hi)) & (~0ull << (lo & 63))) & all_lanes;
+          }
           const auto put = [&](const int k, const double l, const double h) {
             const d2v v{l, h};
-            if (MULTI) asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(Mu + k * pb) : "memory");
+            if (MASKED && MULTI)
+              asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_mov_b64 exec, %4"
+                           ::"v"(voff), "v"(v), "s"(Mu + k * pb), "s"(keep), "s"(all_lanes) : "memory");
+            else if (MASKED)
+              asm volatile("s_mov_b64 exec, %3\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_mov_b64 exec, %4"
+                           ::"v"(voff), "v"(v), "s"(Mu + k * pb), "s"(keep), "s"(all_lanes) : "memory");
+            else if (MULTI) asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(Mu + k * pb) : "memory");
             else __builtin_nontemporal_store(v, (HX_GLOBAL d2v*)(Mu + k * pb + voff));
           };
           const double h0 = log_finish(cb.imm, cb.e, eb0);
@@ -671,7 +721,8 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         // wrap-around link: a column counts once its stores have left the wave.  Vector-memory operations retire in
         // issue order and every iteration issues five stores (and nothing else), so everything stored
         // HXL_PUBLISH_LAG steps = 8 iterations ago is older than the wave's 40 youngest operations.
-        const int fin = (t + 2 < nsteps ? t + 2 : nsteps) - 63;
+        const int nsteps2 = MASKED ? (nsteps + 1) & ~1 : nsteps;   // (whole step pairs)
+        const int fin = (t + 2 < nsteps2 ? t + 2 : nsteps2) - 63;
         if (fin >= Cc) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           publish_drained(my_base + Cc);
@@ -753,8 +804,10 @@ static LdsPlan plan_lds(int W, int PPW, bool banded, int yl_cols, int yl_emis, i
   return p;
 }
 
+// fold: the chains relative to their first transitions (FOLD; admitted by linear_fold_admits for every job of the launch).
+// Only the unbanded launches of one workgroup per pair have the instantiation; the others ignore the flag.
 int launch_forward_leaf_linear(const DevJob* d_jobs, int n_jobs, int max_rows, bool banded, Tab8 tab8, Tab16 tab16,
-                               int yl_cols, int yl_emis, int yl_cls, int multi, int* counters, bool trunc, hipStream_t st) {
+                               int yl_cols, int yl_emis, int yl_cls, int multi, int* counters, bool trunc, bool fold, hipStream_t st) {
   const double* tab = tab8.p;
   const double* log_tab = tab16.p;
   if (yl_cls > HX_YL_MAX_CLS_LINEAR + 1) return launch_fail("%d emission classes exceed the scaled-probability kernel's column words", yl_cls);
@@ -769,12 +822,14 @@ int launch_forward_leaf_linear(const DevJob* d_jobs, int n_jobs, int max_rows, b
                          multi, counters);
     return 0;
   }
-#define HXL_LAUNCH(W_, B_, PPW_) do { const LdsPlan p = plan_lds(W_, PPW_, B_, yl_cols, yl_emis, yl_cls); \
+#define HXL_LAUNCH4(W_, B_, PPW_, F_) do { const LdsPlan p = plan_lds(W_, PPW_, B_, yl_cols, yl_emis, yl_cls); \
     if (p.total > HX_LDS_LIMIT) return launch_fail("k_fill_leaf_linear<%d> needs %d bytes of LDS (limit %d)", W_, p.total, HX_LDS_LIMIT); \
-    if (trunc) hipLaunchKernelGGL((k_fill_leaf_linear<W_, B_, PPW_, 0, false, true>), dim3((n_jobs + PPW_ - 1) / PPW_), dim3(W_ * PPW_ * 64), p.total, st, \
+    if (trunc) hipLaunchKernelGGL((k_fill_leaf_linear<W_, B_, PPW_, 0, false, true, F_>), dim3((n_jobs + PPW_ - 1) / PPW_), dim3(W_ * PPW_ * 64), p.total, st, \
                        d_jobs, tab, log_tab, p, n_jobs); \
-    else hipLaunchKernelGGL((k_fill_leaf_linear<W_, B_, PPW_, 0>), dim3((n_jobs + PPW_ - 1) / PPW_), dim3(W_ * PPW_ * 64), p.total, st, \
+    else hipLaunchKernelGGL((k_fill_leaf_linear<W_, B_, PPW_, 0, false, false, F_>), dim3((n_jobs + PPW_ - 1) / PPW_), dim3(W_ * PPW_ * 64), p.total, st, \
                        d_jobs, tab, log_tab, p, n_jobs); } while (0)
+#define HXL_LAUNCH(W_, B_, PPW_) HXL_LAUNCH4(W_, B_, PPW_, false)
+#define HXL_LAUNCH_U(W_) do { if (fold) HXL_LAUNCH4(W_, false, 1, true); else HXL_LAUNCH4(W_, false, 1, false); } while (0)
   if (banded) {
     // one wavefront per pair; with more pairs than fit the CUs one by one (LDS: four workgroups of one pair), six pairs
     // per workgroup share the logarithm table: twelve waves per CU
@@ -790,18 +845,20 @@ int launch_forward_leaf_linear(const DevJob* d_jobs, int n_jobs, int max_rows, b
   }
   const char* v = getenv("HX_LINEAR_WAVES");     // tuning / test hook: waves per pair (any count works for any size)
   const int forced = v ? atoi(v) : 0;
-  if (forced == 1) HXL_LAUNCH(1, false, 1);
-  else if (forced == 2) HXL_LAUNCH(2, false, 1);
-  else if (forced == 4) HXL_LAUNCH(4, false, 1);
-  else if (forced == 8) HXL_LAUNCH(8, false, 1);
-  else if (forced == 16) HXL_LAUNCH(16, false, 1);
-  else if (max_rows <= 64) HXL_LAUNCH(1, false, 1);
-  else if (max_rows <= 128) HXL_LAUNCH(2, false, 1);
-  else if (max_rows <= 256) HXL_LAUNCH(4, false, 1);
+  if (forced == 1) HXL_LAUNCH_U(1);
+  else if (forced == 2) HXL_LAUNCH_U(2);
+  else if (forced == 4) HXL_LAUNCH_U(4);
+  else if (forced == 8) HXL_LAUNCH_U(8);
+  else if (forced == 16) HXL_LAUNCH_U(16);
+  else if (max_rows <= 64) HXL_LAUNCH_U(1);
+  else if (max_rows <= 128) HXL_LAUNCH_U(2);
+  else if (max_rows <= 256) HXL_LAUNCH_U(4);
   // more pairs than compute units: eight waves per pair, two pairs per CU (less pipeline fill per pair)
-  else if (max_rows <= 512 || n_jobs > 256) HXL_LAUNCH(8, false, 1);
-  else HXL_LAUNCH(16, false, 1);
+  else if (max_rows <= 512 || n_jobs > 256) HXL_LAUNCH_U(8);
+  else HXL_LAUNCH_U(16);
+#undef HXL_LAUNCH_U
 #undef HXL_LAUNCH
+#undef HXL_LAUNCH4
   return 0;
 }
 

@@ -320,6 +320,12 @@ int hx_batch_shared_wavefront_pairs(const hx_batch* b);
  * HX_ERR_HIP is returned only if the repeated fill fails too.  Negative: an error. */
 int hx_batch_relaunches(const hx_batch* b);
 
+/* Diagnostics (test hook): 1 when the most recent hx_batch_forward ran its unbanded scaled-probability leaf pairs with the
+ * chains of the recursion written relative to their first transitions (hx_linear.hip, FOLD: every transition of every such
+ * pair within e^+-6.93 of its chain's first, one workgroup per pair; HX_LINEAR_FOLD=0 turns it off), 0 when it ran the
+ * unfolded code or the batch has no such pairs; negative: an error. */
+int hx_batch_forward_folded(const hx_batch* b);
+
 /* Duration in milliseconds of the most recent hx_batch_forward / hx_batch_backward
  * fill kernel (HIP events recorded around that kernel on its stream). */
 int hx_batch_last_kernel_ms(hx_batch* b, int32_t which, float* ms);
