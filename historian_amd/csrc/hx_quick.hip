@@ -48,7 +48,9 @@ __device__ __forceinline__ double lane_value(double v, int l) {
 // operands except max(-0.0, +0.0) (sign of zero); the scores are sums of logarithms and never -0.0.
 __device__ __forceinline__ double dmax(double a, double b) { return vmax(a, b); }
 
-#define HX_QA_LAG 16
+#ifndef HX_QA_LAG
+#define HX_QA_LAG 16   // steps a column's stores are given before it is published (measured against 26: DESIGN section 9)
+#endif
 #define HX_QA_MAX_ALPH 31
 
 // COLG: the per-column constants do not fit LDS (y longer than HX_QA_LDS_COLS): they live in a per-pair
@@ -183,8 +185,14 @@ __global__ void __launch_bounds__(W * 64) k_quickalign(const DevQuick* __restric
       M2[plane2] = d2v{ca.ins, cb.ins};
       M2[2 * plane2] = d2v{ca.del, cb.del};
       // publish progress: the strip's last row has finished column (t + 1) - 63; a column counts once its
-      // stores have left the wave (every iteration issues 5 vector-memory operations: everything stored
-      // HX_QA_LAG steps ago is older than the wave's 40 youngest, see hx_chain.hip)
+      // stores have left the wave.  Vector-memory operations retire in issue order and every iteration
+      // (two steps) issues at least its 3 stores (with the full envelope and the column tables in LDS it
+      // issues nothing else), so everything stored HX_QA_LAG steps = HX_QA_LAG / 2 iterations ago is older
+      // than the wave's PUBLISH_WAIT youngest operations (the same guard as in hx_chain.hip)
+      constexpr int STORES_PER_ITER = 3;
+      constexpr int PUBLISH_WAIT = STORES_PER_ITER * (HX_QA_LAG / 2) < 63 ? STORES_PER_ITER * (HX_QA_LAG / 2) : 63;
+      static_assert(PUBLISH_WAIT <= STORES_PER_ITER * (HX_QA_LAG / 2) && PUBLISH_WAIT <= 63 && HX_QA_LAG % 2 == 0,
+                    "the wait count must not exceed the operations issued since the published column's stores");
       const int fin = (t + 2 < nsteps ? t + 2 : nsteps) - 63;
       if (fin >= Cc) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -192,7 +200,7 @@ __global__ void __launch_bounds__(W * 64) k_quickalign(const DevQuick* __restric
       } else {
         const int done = fin - HX_QA_LAG;
         if (done > 0 && ((done >> 6) != ((done - 2) >> 6))) {
-          asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PUBLISH_WAIT) : "memory");
           if (lane == 0) progp[wave] = my_base + done;
         }
       }

@@ -10,7 +10,7 @@ from historian_amd import capi
 from oracle import c_oracle
 from oracle import historian_oracle as ho
 from oracle import quickalign_oracle as q
-from tests import helpers as H
+from tests.quickalign_helpers import run_and_check, score_vector
 
 pytestmark = pytest.mark.gpu
 G = "tests/golden/reference_data/"
@@ -30,29 +30,11 @@ def amino():
     return model, q.QuickAlignScores(model, 1.0)
 
 
-def score_vector(sc):
-    return [getattr(sc, n) for n in capi.QuickBatch.SCORE_NAMES]
-
-
 def make_pair(rng, A, lx, ly, sub=.15):
     x = "".join(rng.choice(A) for _ in range(lx))
     y = "".join((c if rng.random() > sub else rng.choice(A)) for c in x[:ly])
     y += "".join(rng.choice(A) for _ in range(max(0, ly - len(y))))
     return x, y
-
-
-def run_and_check(pairs, A, sc):
-    """pairs: list of (x, y, diagonals or None)"""
-    jobs = [(q.tokens(x, A), q.tokens(y, A), len(A), sc.submat, score_vector(sc), d) for x, y, d in pairs]
-    b = capi.QuickBatch(jobs)
-    b.run()
-    score, xe, ye = b.results()
-    for k, (xt, yt, a, sm, sv, d) in enumerate(jobs):
-        want = c_oracle.quickalign(xt, yt, a, sm, sc, d)
-        H.assert_same_bits(b.read_matrix(k), want["cells"], "pair %d cells" % k)
-        H.assert_same_bits([score[k]], [want["score"]], "pair %d score" % k)
-        assert (int(xe[k]), int(ye[k])) == (want["x_end"], want["y_end"])
-    b.close()
 
 
 def test_reference_fixture_pair_and_its_traceback(amino):

@@ -6,7 +6,7 @@ import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-from historian_amd import capi, hostmodel
+from historian_amd import capi, workload
 from oracle import c_oracle, historian_oracle as ho, quickalign_oracle as q
 
 pairs = int(sys.argv[1]) if len(sys.argv) > 1 else 512
@@ -18,12 +18,10 @@ sc = q.QuickAlignScores(model, 0.5)
 scores = [getattr(sc, n) for n in capi.QuickBatch.SCORE_NAMES]
 a = len(model.alphabet)
 pi = np.asarray(model.ins_prob[0], dtype=float); pi /= pi.sum()
-sys.path.insert(0, ROOT)
-import bench
 jobs = []
 for k in range(pairs):
     rng = np.random.default_rng(5000 + k)
-    x, y = bench.synth_pair(rng, pi, length)
+    x, y = workload.synth_pair(rng, pi, length)
     jobs.append((x.astype(np.int32), y.astype(np.int32), a, sc.submat, scores, None))
 capi.init(0, c_oracle.table())
 b = capi.QuickBatch(jobs)
