@@ -209,7 +209,7 @@ k_fill_band(const DevJob* __restrict__ jobs, const double* __restrict__ exact_ta
     if (OFFLOAD) {
       int seen = 0;
       for (int k = 0; k < n_steps; k += 2) {
-        while (seen < k + 2) {
+        while (seen < k + 2) {                         // (hx_handoff.h lds_wait, written out: the call reorders the prologue)
           seen = __builtin_amdgcn_readfirstlane(progL[0]);
           if (seen < k + 2) __builtin_amdgcn_s_sleep(1);
         }
@@ -583,7 +583,7 @@ k_fill_band(const DevJob* __restrict__ jobs, const double* __restrict__ exact_ta
     const int sl = store + (k >> 1) * blk;
     if (OFFLOAD) {
       // the ring slots of steps k, k + 1 were last used by steps k - 8, k - 7: the converting wave must be past them
-      while (cons_seen < k + 2 - RING) {
+      while (cons_seen < k + 2 - RING) {             // (as lds_wait of hx_handoff.h, without its closing barrier)
         cons_seen = __builtin_amdgcn_readfirstlane(consL[0]);
         if (cons_seen < k + 2 - RING) __builtin_amdgcn_s_sleep(1);
       }

@@ -30,6 +30,7 @@
 #include "hx_policy.h"
 #include "hx_leafcell.h"
 #include "hx_kernels.h"
+#include "hx_handoff.h"
 
 namespace hx {
 
@@ -153,10 +154,8 @@ __device__ __forceinline__ C5 chain_cell(const DevJob& J, const LSE& L, const XR
 // MULTI: few pairs of many strips (one rank's share of a strong-scaling run): a pair's strips are dealt to `groups`
 // workgroups of W waves, so that its waves spread over several CUs instead of sharing one CU's four SIMDs.  What a strip
 // takes from the strip above already travels through the matrix; across workgroups (and XCDs) the stores are write-through
-// (`sc1`), the progress counters sit in memory (`counters`, 256 zeroed ints per pair: one per wave, [255] = a poll gave up)
-// and are written / polled with `sc1` accesses behind the storing wave's own s_waitcnt - the hand-off of hx_dag.hip's
-// lone-pair launches.  A poll gives up after HX_CHAIN_PATIENCE rounds and the pair's lpEnd / lpStart becomes NaN.
-#define HX_CHAIN_PATIENCE (1 << 22)
+// and the progress counters sit in memory (`counters`, 256 zeroed ints per pair: one per wave, [255] = a poll gave up, and
+// the pair's lpEnd / lpStart becomes NaN): hx_handoff.h.
 template <int DIR, int W, class LSE, bool FAST, bool LEAF, bool YL, bool BANDED, int MINW = 1, int PPW = 1, bool MULTI = false>
 __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob* __restrict__ jobs,
                                                                       const double* __restrict__ exact_tab,
@@ -243,25 +242,20 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
   bool dead = false;                                // MULTI: a poll ran out of patience
   const auto wait_above = [&](const int need) {
     if (!MULTI) {
+      // (hx_handoff.h lds_wait without its closing barrier, which reorders three Backward instantiations: what follows the
+      // wait here are agent-scope loads, which the compiler keeps behind a volatile read)
       while (progp[prev_wave] < need) __builtin_amdgcn_s_sleep(1);
       return;
     }
-    if (dead) return;
-    int polls = 0;
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(gprog + prev_wave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < need) {
-      if (++polls > HX_CHAIN_PATIENCE) {
-        dead = true;
-        if (lane == 0) __hip_atomic_store(gprog + 255, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
+    int seen = 0;
+    if (!dead && agent_wait<1>(gprog, prev_wave, seen, need, HX_MULTI_PATIENCE_DEFAULT)) {
+      dead = true;
+      raise_gave_up(gprog, lane);
     }
-    asm volatile("" ::: "memory");
   };
-  const auto publish = [&](const int value) {      // (behind the caller's s_waitcnt: the columns up to `value` are out)
-    if (lane != 0) return;
-    if (MULTI) __hip_atomic_store(gprog + gw, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else progp[wave] = value;
+  const auto publish = [&](const int value) {      // (behind the caller's drain: the columns up to `value` are out)
+    if (MULTI) agent_publish(gprog + gw, lane, value);
+    else if (lane == 0) progp[wave] = value;
   };
 
   for (int s = gw; s < n_strips; s += WT) {
@@ -353,12 +347,8 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
           bnd = c5_neg_inf();
           const int64_t sl = jj < Cc ? (sbase ? stored_slot(J, row0 - 1, jj) : cell_slot(ss, row0 - 1, jj)) : -1;
           if (sl >= 0) {                           // (not stored: outside the envelope, -inf)
-            // agent-scope relaxed loads (global_load ... sc1): served by L2, never by a stale L1 line
-            bnd.imm = __hip_atomic_load(M + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bnd.imd = __hip_atomic_load(M + plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bnd.idm = __hip_atomic_load(M + 2 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bnd.imi = __hip_atomic_load(M + 3 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bnd.iiw = __hip_atomic_load(M + 4 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const Planes<5> c = load_cell_agent<5>(M, plane, sl);
+            bnd = C5{c.v[0], c.v[1], c.v[2], c.v[3], c.v[4]};
           }
           // consume the loads here, so that the wait for them sits in this once-per-64-steps
           // block and not at the merge point every step passes
@@ -468,11 +458,8 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
       wait_above(need);
       const int64_t sl = sbase ? stored_slot(J, row0 - 1, wstart - 1) : cell_slot(ss, row0 - 1, wstart - 1);
       if (lane == 0 && sl >= 0) {
-        ub.imm = __hip_atomic_load(M + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ub.imd = __hip_atomic_load(M + plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ub.idm = __hip_atomic_load(M + 2 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ub.imi = __hip_atomic_load(M + 3 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ub.iiw = __hip_atomic_load(M + 4 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const Planes<5> c = load_cell_agent<5>(M, plane, sl);
+        ub = C5{c.v[0], c.v[1], c.v[2], c.v[3], c.v[4]};
         if (!above_in_envelope(wstart - 1)) ub = c5_neg_inf();
       }
     }
@@ -505,13 +492,9 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
         HX_GLOBAL d2v* M2 = (HX_GLOBAL d2v*)(M + sl);
         const int64_t plane2 = plane >> 1;
         if (MULTI) {
-          // the strip below may run on another XCD: write-through stores (never `nt`, which stays in this XCD's L2)
-          const d2v v0{ca.imm, cb.imm}, v1{ca.imd, cb.imd}, v2{ca.idm, cb.idm}, v3{ca.imi, cb.imi}, v4{ca.iiw, cb.iiw};
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[0]), "v"(v0) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[plane2]), "v"(v1) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[2 * plane2]), "v"(v2) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[3 * plane2]), "v"(v3) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[4 * plane2]), "v"(v4) : "memory");
+          // the strip below may run on another XCD
+          const d2v v[5] = {{ca.imm, cb.imm}, {ca.imd, cb.imd}, {ca.idm, cb.idm}, {ca.imi, cb.imi}, {ca.iiw, cb.iiw}};
+          store_pair_through<5>(M2, plane2, v);
         } else {
           // write-once data: non-temporal stores (the 1/64 of it that the strip below reads back comes from L2 or memory)
           __builtin_nontemporal_store(d2v{ca.imm, cb.imm}, &M2[0]);
@@ -521,25 +504,16 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
           __builtin_nontemporal_store(d2v{ca.iiw, cb.iiw}, &M2[4 * plane2]);
         }
       }
-      // publish progress.  The strip's last row has finished column (t + 1) - (SR - 1); a
-      // column counts as published once its stores have left the wave.  Vector-memory
-      // operations retire in issue order and every iteration (two steps) issues at least its
-      // 5 stores (the LDS-resident-y path issues nothing else), so everything stored
-      // HX_PUBLISH_LAG steps = HX_PUBLISH_LAG / 2 iterations ago is older than the wave's
-      // PUBLISH_WAIT youngest operations.
-      constexpr int STORES_PER_ITER = 5;
-      constexpr int PUBLISH_WAIT = STORES_PER_ITER * (HX_PUBLISH_LAG / 2) < 63 ? STORES_PER_ITER * (HX_PUBLISH_LAG / 2) : 63;
-      static_assert(PUBLISH_WAIT <= STORES_PER_ITER * (HX_PUBLISH_LAG / 2) && PUBLISH_WAIT <= 63 && HX_PUBLISH_LAG % 2 == 0,
-                    "the wait count must not exceed the operations issued since the published column's stores");
+      // publish progress, lagged: every iteration issues at least its 5 stores (the LDS-resident-y path issues nothing else)
       const int fin = (t + 2 < nsteps ? t + 2 : nsteps) - (SR - 1);
       if (fin >= Cc) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        drain_stores();
         if (WIN) published = Cc;
         publish(my_base + Cc);
       } else {
         const int done = fin - HX_PUBLISH_LAG;
         if (done > (WIN ? published : 0) && ((done >> 6) != ((done - 2) >> 6))) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PUBLISH_WAIT) : "memory");
+          drain_lagged<5, HX_PUBLISH_LAG>();
           if (WIN) published = done;
           publish(my_base + done);
         }
@@ -551,7 +525,7 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
       const int upto = (w == 0 && whi[1] > wlo[1]) ? wlo[1] - (SR - 1) : Cc;
       const int done = upto > Cc ? Cc : upto;
       if (done > published) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        drain_stores();
         published = done;
         publish(my_base + done);
       }
@@ -562,11 +536,8 @@ __global__ void __launch_bounds__(W * PPW * 64, MINW) k_fill_chain(const DevJob*
       publish(my_base + Cc);
     }
     if (MULTI && s == n_strips - 1) {
-      // the last strip finishes last (every strip follows the one above) and its own stores are out (vmcnt(0) in front of
-      // its last publish); what END reads may lie in other workgroups' strips: drop this CU's L1 first
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const bool gave_up = __hip_atomic_load(gprog + 255, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+      // the last strip finishes last (every strip follows the one above); what END reads may lie in other workgroups' strips
+      const bool gave_up = acquire_gave_up(gprog);
       if (lane == 0) {
         if (DIR == 0) *J.lp_end = gave_up ? __builtin_nan("") : forward_lp_end(J, LX);
         else *J.lp_start = gave_up ? __builtin_nan("") : J.bwd[cell_slot(ss, R - 1, Cc - 1)];

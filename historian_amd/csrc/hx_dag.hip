@@ -11,14 +11,11 @@
 // recent stores), ordered by
 //   * own strip:    vector-memory operations of a wave retire in issue order, so a load sees every
 //                   store the wave issued before it;
-//   * strips above: a wave publishes (monotonic LDS counter), after draining its stores, how many
-//                   columns of its strip are complete; the wave below does not enter step t before
+//   * strips above: the strip hand-off (hx_handoff.h): the wave below does not enter step t before
 //                   columns 0..t of the strip above are published.  Strips further up completed
 //                   those columns earlier still.
-// All waves of a workgroup share one CU and one L1, so draining + the LDS counter is a
-// workgroup-scope release/acquire; no cache maintenance is needed.
 //
-// k_fill_dag<1>        Backward: the recursion as the reference writes it, per-step drain.
+// k_backward_dag_strips  Backward: the recursion as the reference writes it, per-step drain.
 // k_forward_dag_pipe   Forward, restructured for latency (see the comment above it): outgoing sums
 //                      stored per cell, inline transition records, register forwarding of the
 //                      previous step, stores issued behind the next step's loads.
@@ -40,6 +37,7 @@
 #include "hx_common.h"
 #include "hx_policy.h"
 #include "hx_kernels.h"
+#include "hx_handoff.h"
 
 namespace hx {
 
@@ -103,91 +101,6 @@ __device__ __forceinline__ bool in_env(const Mat& m, uint8_t xf, uint8_t yf, int
   int d = xe - ye;
   d = d < 0 ? -d : d;
   return d <= m.max_dist;
-}
-
-// one Forward cell (reference src/forward.cpp:78-203); the caller has checked the envelope
-template <class LSE>
-__device__ __forceinline__ C5 forward_cell_dag(const Mat& m, const Side& x, const Side& y, const double (*T)[6],
-                                               const LSE& L, int i, int j, uint8_t xf, uint8_t yf) {
-  const HX_GLOBAL double* M = m.M;
-  const int64_t plane = m.plane, ss = m.ss;
-  C5 r = c5_neg_inf();
-  if (i == 0 && j == 0) r.imm = 0.0;
-  const bool xnull = xf & F_NULL, ynull = yf & F_NULL;
-  const bool yok = (yf & F_READY) || y.empty;   // yState.isReady() || yEmpty
-  const bool xok = (xf & F_READY) || x.empty;
-  const int xb = x.in_off[i], xe = x.in_off[i + 1];
-  const int yb = y.in_off[j], ye = y.in_off[j + 1];
-
-  if (!xnull) {
-    if (yok) {
-      for (int t = xb; t < xe; ++t) {
-        const C5 s = ld5(M, plane, cell_slot(ss, x.in_src[t], j));
-        const double lp = x.in_lp[t];
-        double a = L(s.imm + T[0][1], s.imd + T[1][1]);
-        double b = L(s.imm + T[0][4], s.imi + T[3][4]);
-        a = L(a, s.idm + T[2][1]);
-        b = L(b, s.iiw + T[4][4]);
-        a = L(a, s.imi + T[3][1]);
-        r.imd = L(r.imd, a + lp);
-        r.iiw = L(r.iiw, b + lp);
-      }
-      r.imd += x.rootsub[i];
-      r.iiw += x.ins[i];
-    }
-  } else if (yok) {
-    for (int t = xb; t < xe; ++t) {
-      const int64_t sl = cell_slot(ss, x.in_src[t], j);
-      const double lp = x.in_lp[t];
-      r.imd = L(r.imd, M[plane + sl] + lp);
-      r.iiw = L(r.iiw, M[4 * plane + sl] + lp);
-    }
-  }
-
-  if (!ynull) {
-    if (xok) {
-      for (int t = yb; t < ye; ++t) {
-        const C5 s = ld5(M, plane, cell_slot(ss, i, y.in_src[t]));
-        const double lp = y.in_lp[t];
-        double a = L(s.imm + T[0][2], s.imd + T[1][2]);
-        const double b = L(s.imm + T[0][3], s.imi + T[3][3]);
-        a = L(a, s.idm + T[2][2]);
-        a = L(a, s.iiw + T[4][2]);
-        r.idm = L(r.idm, a + lp);
-        r.imi = L(r.imi, b + lp);
-      }
-      r.idm += y.rootsub[j];
-      r.imi += y.ins[j];
-    }
-  } else {
-    for (int t = yb; t < ye; ++t) {
-      const int64_t sl = cell_slot(ss, i, y.in_src[t]);
-      const double lp = y.in_lp[t];
-      r.idm = L(r.idm, M[2 * plane + sl] + lp);
-      r.imi = L(r.imi, M[3 * plane + sl] + lp);
-    }
-  }
-
-  if (!xnull && !ynull) {
-    for (int tx = xb; tx < xe; ++tx) {
-      const int sx = x.in_src[tx];
-      const double lpx = x.in_lp[tx];
-      for (int ty = yb; ty < ye; ++ty) {
-        const C5 s = ld5(M, plane, cell_slot(ss, sx, y.in_src[ty]));
-        double a = L(s.imm + T[0][0], s.imd + T[1][0]);
-        a = L(a, s.idm + T[2][0]);
-        a = L(a, s.imi + T[3][0]);
-        a = L(a, s.iiw + T[4][0]);
-        r.imm = L(r.imm, a + lpx + y.in_lp[ty]);
-      }
-    }
-    r.imm += emis_at(m, x, y, i, j);
-  } else if (ynull && (xf & F_EMIT_OR_START)) {
-    for (int t = yb; t < ye; ++t) r.imm = L(r.imm, M[cell_slot(ss, i, y.in_src[t])] + y.in_lp[t]);
-  } else if (yok) {
-    for (int t = xb; t < xe; ++t) r.imm = L(r.imm, M[cell_slot(ss, x.in_src[t], j)] + x.in_lp[t]);
-  }
-  return r;
 }
 
 // one Backward cell (reference src/forward.cpp:996-1086); B is stored mirrored (hx_device.h)
@@ -359,7 +272,7 @@ __device__ __forceinline__ BwdRec load_bwd_rec(const HX_GLOBAL char* base, int i
   return r;
 }
 
-// COH: the matrix is being written by other workgroups too (k_backward_dag_multi): every load of a cell bypasses the L1
+// COH: the matrix is being written by other workgroups too (k_backward_dag_strips<.., MULTI>): every load of a cell bypasses the L1
 // (`sc1`, a relaxed agent-scope load) - the producing wave stored it `sc1` and published its progress behind its own
 // s_waitcnt vmcnt(0), the form MI355X_MICROARCH.md lists as valid without an L2 write-back.
 template <bool COH>
@@ -550,149 +463,33 @@ __device__ __forceinline__ C5 backward_cell_rec(const Mat& m, const Side& x, con
 #define HX_DAG_MAX_WAVES 16
 #define HX_DAG_REC_WAVES 8      // the state-record Backward kernels: 8 waves, so that a wave may use 256 registers (the batch of first-transition loads)
 
-// DIR 0: Forward, DIR 1: Backward (swept in mirrored coordinates)
-template <int DIR, class LSE, bool FAST, bool REC = false>
-__global__ void __launch_bounds__((REC ? HX_DAG_REC_WAVES : HX_DAG_MAX_WAVES) * 64) k_fill_dag(const DevJob* __restrict__ jobs,
+// Backward, swept in mirrored coordinates: the recursion as the reference writes it, every cell's destinations read back from
+// the matrix.  REC: the state records of both profiles, built here into the pair's scratch planes (the caller launches these
+// instantiations only for pairs that have them, and only after the Forward fill is done with them).
+// MULTI: ONE pair (or two) on several CUs: the pair's strips are dealt to the waves of G workgroups instead of the waves of
+// one, so that a pair of thirty strips needs one pass instead of two and its waves share SIMDs less.  What the strips hand
+// each other - the matrix itself - travels write-through (every cell stored and loaded at agent scope: CellLoads), and the
+// progress counters live in memory (the last 256 ints of the pair's scratch planes, zeroed by the host): hx_handoff.h.  A
+// wave that gives up publishes poison; the pair's lpStart then reads NaN and the host reports an error.  All workgroups of
+// the launch must be resident at once (the caller launches at most sixteen).
+template <class LSE, bool FAST, bool REC = false, bool MULTI = false>
+__global__ void __launch_bounds__((REC ? HX_DAG_REC_WAVES : HX_DAG_MAX_WAVES) * 64) k_backward_dag_strips(const DevJob* __restrict__ jobs,
                                                                       const double* __restrict__ exact_tab,
-                                                                      const double* __restrict__ fast_tab) {
-  __shared__ volatile int prog[HX_DAG_MAX_WAVES];
+                                                                      const double* __restrict__ fast_tab, const int groups = 1,
+                                                                      const int patience = 0) {
+  static_assert(!MULTI || REC, "several workgroups per pair: the state-record formulation only");
+  __shared__ volatile int prog[MULTI ? 1 : HX_DAG_MAX_WAVES];
   __shared__ __attribute__((aligned(16))) double ftab[FAST ? (HX_FAST_INTERVALS + 1) * 2 : 2];
   const int threads = blockDim.x, W = threads >> 6;
   if (FAST)
     for (int k = threadIdx.x; k < (HX_FAST_INTERVALS + 1) * 2; k += threads) ftab[k] = fast_tab[k];
-  if (threadIdx.x < HX_DAG_MAX_WAVES) prog[threadIdx.x] = 0;
+  if (!MULTI && threadIdx.x < HX_DAG_MAX_WAVES) prog[threadIdx.x] = 0;
   __syncthreads();
   const LSE L = LSE::make(FAST ? (const double*)ftab : fast_tab)   /* exact mode: fast_tab is the pair table */;
   volatile HX_LDS int* progp = (volatile HX_LDS int*)prog;
 
-  const DevJob& J = jobs[blockIdx.x];
-  const Side x = make_side(J.x), y = make_side(J.y);
-  Mat m;
-  m.M = as_global(DIR ? J.bwd : J.fwd);
-  m.etab = as_global((const double*)J.emis);
-  m.eplane = as_global((const double*)J.emis_plane);
-  m.plane = J.plane; m.ss = J.strip_stride;
-  m.R = J.n_rows; m.Cc = J.n_cols; m.max_dist = J.max_dist;
-  const int R = m.R, Cc = m.Cc;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n_strips = (R + 63) >> 6;
-  const int prev_wave = (wave + W - 1) % W;
-  const bool banded = J.max_dist >= 0;
-  const HX_GLOBAL int32_t* win = as_global(DIR ? J.bwd_windows : J.fwd_windows);
-  // REC: the state records of both profiles, built here into the pair's scratch planes (the caller launches this
-  // instantiation only for pairs that have them, and only after the Forward fill is done with them)
-  HX_GLOBAL char* xrec = nullptr;
-  HX_GLOBAL char* yrec = nullptr;
-  if (REC) {
-    xrec = (HX_GLOBAL char*)as_global(J.agg);
-    yrec = xrec + (size_t)x.n * HX_BWD_REC_BYTES;
-    build_bwd_recs(x, xrec, banded, (int)threadIdx.x, threads);
-    build_bwd_recs(y, yrec, banded, (int)threadIdx.x, threads);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  for (int s = wave; s < n_strips; s += W) {
-    const int im = (s << 6) + lane;              // row in sweep coordinates
-    const bool rvalid = im < R;
-    const int i = rvalid ? (DIR ? R - 1 - im : im) : 0;
-    const uint8_t xf = x.flags[i];
-    const int xenv = banded ? x.env[i] : 0;
-    BwdRec rx;
-    if (REC) rx = load_bwd_rec(xrec, i);
-    const int above_base = ((s - 1) / W) * Cc;   // columns the wave above published in its earlier strips
-    const int my_base = (s / W) * Cc;
-    const int64_t store_base = (int64_t)s * m.ss + (lane << 1);
-    int seen = 0;
-    // step windows [w0,w1) and [w2,w3) that hold this strip's in-envelope cells (whole sweep when unbanded)
-    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};
-    if (banded) {
-      wlo[0] = win[4 * s]; whi[0] = win[4 * s + 1];
-      wlo[1] = win[4 * s + 2]; whi[1] = win[4 * s + 3];
-    }
-    int published = 0;
-    for (int w = 0; w < 2; ++w) {
-      for (int t = wlo[w]; t < whi[w]; ++t) {
-        if (s > 0) {
-          const int need = above_base + (t + 1 < Cc ? t + 1 : Cc);
-          if (seen < need) {
-            do {
-              seen = __builtin_amdgcn_readfirstlane(progp[prev_wave]);
-              if (seen < need) __builtin_amdgcn_s_sleep(1);
-            } while (seen < need);
-            asm volatile("" ::: "memory");
-          }
-        }
-        const int jm = t - lane;
-        if (rvalid && jm >= 0 && jm < Cc) {
-          const int j = DIR ? Cc - 1 - jm : jm;
-          BwdRec ry;
-          if (REC) ry = load_bwd_rec(yrec, j);
-          const uint8_t yf = REC ? (uint8_t)ry.flags : y.flags[j];
-          if (in_env(m, xf, yf, xenv, banded ? (REC ? ry.env : y.env[j]) : 0)) {
-            const C5 c = REC ? backward_cell_rec<LSE, false, 3>(m, x, y, J.T, L, i, j, rx, ry)
-                       : DIR ? backward_cell_dag(m, x, y, J.T, L, i, j, xf, yf)
-                             : forward_cell_dag(m, x, y, J.T, L, i, j, xf, yf);
-            const int64_t sl = store_base + ((int64_t)(t >> 1) << 7) + (t & 1);
-            m.M[sl] = c.imm;
-            m.M[m.plane + sl] = c.imd;
-            m.M[2 * m.plane + sl] = c.idm;
-            m.M[3 * m.plane + sl] = c.imi;
-            m.M[4 * m.plane + sl] = c.iiw;
-          }
-        }
-        // The next step of this wave reads this step's cells back through memory: vector-memory operations of a wave
-        // take effect in issue order, so no wait is needed for that.  The strip below learns of them through the counter:
-        // every eighth step the wave drains its stores and publishes how many columns all of its rows have completed.
-        if ((t & 7) == 7) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          int done = t - 62;
-          done = done > Cc ? Cc : done;
-          if (done > published) {
-            published = done;
-            if (lane == 0) progp[wave] = my_base + done;
-          }
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      // columns between / after the windows hold no in-envelope cell of this strip: they count as complete
-      // once everything before them is
-      const int upto = (w == 0 && whi[1] > wlo[1]) ? wlo[1] - 63 : Cc;
-      int done = upto > Cc ? Cc : upto;
-      if (done > published) {
-        published = done;
-        if (lane == 0) progp[wave] = my_base + done;
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (DIR == 0) *J.lp_end = forward_lp_end(J, ExactLse{exact_tab});
-    else *J.lp_start = J.bwd[cell_slot(m.ss, R - 1, Cc - 1)];   // B(0,0).IMM in mirrored coordinates
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Backward for ONE pair (or two) on several CUs: the pair's strips are dealt to the 16 G waves of G workgroups instead of the
-// 16 waves of one, so that a pair of thirty strips needs one pass instead of two and its waves share SIMDs less.  What the
-// strips hand each other - the matrix itself - travels write-through: every cell is stored `sc1`, every cell is loaded `sc1`
-// (CellLoads), a wave's progress counter lives in global memory (zeroed by the host before the launch), is stored `sc1`
-// behind the wave's own s_waitcnt vmcnt(0) and polled with `sc1` loads.  A poll gives up after HX_MULTI_PATIENCE rounds: the
-// pair's lpStart then reads NaN and the host reports an error - never a hang.  All workgroups of the launch must be resident
-// at once (the caller launches at most sixteen).  State records as in k_fill_dag<.., REC>.
-// ---------------------------------------------------------------------------------------------------------------------
-template <class LSE, bool FAST>
-__global__ void __launch_bounds__(HX_DAG_REC_WAVES * 64) k_backward_dag_multi(const DevJob* __restrict__ jobs,
-                                                                                const double* __restrict__ exact_tab,
-                                                                                const double* __restrict__ fast_tab, const int G, const int patience) {
-  __shared__ __attribute__((aligned(16))) double ftab[FAST ? (HX_FAST_INTERVALS + 1) * 2 : 2];
-  const int threads = blockDim.x, W = threads >> 6, WT = W * G;
-  if (FAST)
-    for (int k = threadIdx.x; k < (HX_FAST_INTERVALS + 1) * 2; k += threads) ftab[k] = fast_tab[k];
-  __syncthreads();
-  const LSE L = LSE::make(FAST ? (const double*)ftab : fast_tab);
-  const int job = (int)blockIdx.x / G, grp = (int)blockIdx.x % G;
-  const DevJob& J = jobs[job];
+  const int G = MULTI ? groups : 1;
+  const DevJob& J = MULTI ? jobs[(int)blockIdx.x / G] : jobs[blockIdx.x];
   const Side x = make_side(J.x), y = make_side(J.y);
   Mat m;
   m.M = as_global(J.bwd);
@@ -702,101 +499,103 @@ __global__ void __launch_bounds__(HX_DAG_REC_WAVES * 64) k_backward_dag_multi(co
   m.R = J.n_rows; m.Cc = J.n_cols; m.max_dist = J.max_dist;
   const int R = m.R, Cc = m.Cc;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int gw = grp * W + wave;                   // this wave among the pair's WT waves
   const int n_strips = (R + 63) >> 6;
-  const int prev_gw = (gw + WT - 1) % WT;
+  const int WT = W * G, gw = MULTI ? ((int)blockIdx.x % G) * W + wave : wave;   // the pair's waves, and this one among them
+  const int prev_wave = (gw + WT - 1) % WT;
   const bool banded = J.max_dist >= 0;
   const HX_GLOBAL int32_t* win = as_global(J.bwd_windows);
-  // records: every workgroup builds them (the same bytes at the same addresses), its own waves read them after its barrier
-  HX_GLOBAL char* xrec = (HX_GLOBAL char*)as_global(J.agg);
-  HX_GLOBAL char* yrec = xrec + (size_t)x.n * HX_BWD_REC_BYTES;
-  build_bwd_recs(x, xrec, banded, (int)threadIdx.x, threads);
-  build_bwd_recs(y, yrec, banded, (int)threadIdx.x, threads);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  // progress counters of the pair's waves: the last 256 ints of its scratch planes
-  HX_GLOBAL int* gprog = (HX_GLOBAL int*)as_global(reinterpret_cast<int*>(J.agg + 5 * J.plane) - 256);
-  bool dead = false;
-  HX_GLOBAL double* Mw = as_global(J.bwd);       // (global, not flat, instructions: the hand-off is only measured valid for those)
-  const auto put = [&](int64_t k, double v) { __hip_atomic_store(Mw + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-  const auto publish = [&](int value) {
-    if (lane == 0) __hip_atomic_store(gprog + gw, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // (MULTI: every workgroup builds the records - the same bytes at the same addresses; its own waves read them after its barrier)
+  HX_GLOBAL char* xrec = nullptr;
+  HX_GLOBAL char* yrec = nullptr;
+  if (REC) {
+    xrec = (HX_GLOBAL char*)as_global(J.agg);
+    yrec = xrec + (size_t)x.n * HX_BWD_REC_BYTES;
+    build_bwd_recs(x, xrec, banded, (int)threadIdx.x, threads);
+    build_bwd_recs(y, yrec, banded, (int)threadIdx.x, threads);
+    drain_stores();
+    __syncthreads();
+  }
+  HX_GLOBAL int* gprog = MULTI ? (HX_GLOBAL int*)as_global(reinterpret_cast<int*>(J.agg + 5 * J.plane) - 256) : nullptr;
+  bool dead = false;                               // MULTI: this wave gave up - run out without computing
+  // (MULTI: global, not flat, instructions - the hand-off is only measured valid for those)
+  const auto put = [&](const int64_t k, const double v) {
+    if (MULTI) __hip_atomic_store(m.M + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else m.M[k] = v;
   };
 
   for (int s = gw; s < n_strips; s += WT) {
-    const int im = (s << 6) + lane;
+    const int im = (s << 6) + lane;              // row in sweep coordinates
     const bool rvalid = im < R;
     const int i = rvalid ? R - 1 - im : 0;
     const uint8_t xf = x.flags[i];
     const int xenv = banded ? x.env[i] : 0;
-    const BwdRec rx = load_bwd_rec(xrec, i);
-    const int above_base = ((s - 1) / WT) * Cc;
+    BwdRec rx;
+    if (REC) rx = load_bwd_rec(xrec, i);
+    const int above_base = ((s - 1) / WT) * Cc;  // columns the wave above published in its earlier strips
     const int my_base = (s / WT) * Cc;
     const int64_t store_base = (int64_t)s * m.ss + (lane << 1);
     int seen = 0;
-    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};
+    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};   // the strip's step windows (hx_handoff.h), the whole sweep when unbanded
     if (banded) {
       wlo[0] = win[4 * s]; whi[0] = win[4 * s + 1];
       wlo[1] = win[4 * s + 2]; whi[1] = win[4 * s + 3];
     }
     int published = 0;
+    // behind a drain: the columns all rows of the strip have completed (a wave that gave up releases them all, as poison)
+    const auto publish_upto = [&](int done) {
+      if (MULTI && dead) done = Cc;
+      if (done > published) {
+        published = done;
+        if (MULTI) agent_publish(gprog + gw, lane, my_base + done, dead);
+        else if (lane == 0) progp[wave] = my_base + done;
+      }
+    };
     for (int w = 0; w < 2; ++w) {
       for (int t = wlo[w]; t < whi[w]; ++t) {
-        if (s > 0 && !dead) {
+        if (s > 0) {
           const int need = above_base + (t + 1 < Cc ? t + 1 : Cc);
-          int polls = 0;
-          while (seen < need) {
-            seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(gprog + prev_gw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (seen < need) {
-              if (++polls > patience) { dead = true; break; }
-              __builtin_amdgcn_s_sleep(2);
-            }
+          if (MULTI) {
+            if (!dead) dead = agent_wait<2>(gprog, prev_wave, seen, need, patience);
+          } else if (seen < need) {
+            lds_wait<1>(progp, prev_wave, seen, need);
           }
-          if (seen == HX_MULTI_POISON) dead = true;      // the wave above (or one above it) gave up
         }
         const int jm = t - lane;
-        if (!dead && rvalid && jm >= 0 && jm < Cc) {
+        if (!(MULTI && dead) && rvalid && jm >= 0 && jm < Cc) {
           const int j = Cc - 1 - jm;
-          const BwdRec ry = load_bwd_rec(yrec, j);
-          const uint8_t yf = (uint8_t)ry.flags;
-          if (in_env(m, xf, yf, xenv, banded ? ry.env : 0)) {
-            const C5 c = backward_cell_rec<LSE, true, 3>(m, x, y, J.T, L, i, j, rx, ry);
+          BwdRec ry;
+          if (REC) ry = load_bwd_rec(yrec, j);
+          const uint8_t yf = REC ? (uint8_t)ry.flags : y.flags[j];
+          if (in_env(m, xf, yf, xenv, banded ? (REC ? ry.env : y.env[j]) : 0)) {
+            const C5 c = REC ? backward_cell_rec<LSE, MULTI, 3>(m, x, y, J.T, L, i, j, rx, ry)
+                             : backward_cell_dag(m, x, y, J.T, L, i, j, xf, yf);
             const int64_t sl = store_base + ((int64_t)(t >> 1) << 7) + (t & 1);
-            put(sl, c.imm); put(m.plane + sl, c.imd); put(2 * m.plane + sl, c.idm); put(3 * m.plane + sl, c.imi); put(4 * m.plane + sl, c.iiw);
+            put(sl, c.imm);
+            put(m.plane + sl, c.imd);
+            put(2 * m.plane + sl, c.idm);
+            put(3 * m.plane + sl, c.imi);
+            put(4 * m.plane + sl, c.iiw);
           }
         }
+        // The next step of this wave reads this step's cells back through memory: vector-memory operations of a wave
+        // take effect in issue order, so no wait is needed for that.  The strip below learns of them through the counter:
+        // every eighth step the wave drains its stores and publishes how many columns all of its rows have completed.
         if ((t & 7) == 7) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          int done = t - 62;
-          done = done > Cc ? Cc : done;
-          if (dead && published != HX_MULTI_POISON) {   // (everyone below runs out as well, and knows why)
-            published = HX_MULTI_POISON;
-            publish(HX_MULTI_POISON);
-          }
-          if (!dead && done > published) {
-            published = done;
-            publish(my_base + done);
-          }
+          drain_stores();
+          const int done = t - 62;
+          publish_upto(done > Cc ? Cc : done);
         }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int upto = (w == 0 && whi[1] > wlo[1]) ? wlo[1] - 63 : Cc;
-      const int done = upto > Cc ? Cc : upto;
-      if (dead && published != HX_MULTI_POISON) {
-        published = HX_MULTI_POISON;
-        publish(HX_MULTI_POISON);
-      }
-      if (!dead && done > published) {
-        published = done;
-        publish(my_base + done);
-      }
+      drain_stores();
+      publish_upto(final_after_window(wlo, whi, w, Cc));
     }
-    // the wave of the last strip reports B(START, START).IMM (its own store, read back past the L1)
-    if (s == n_strips - 1 && lane == 0) {
-      const double v = __hip_atomic_load(Mw + cell_slot(m.ss, R - 1, Cc - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *J.lp_start = dead ? __builtin_nan("") : v;
-    }
+    // MULTI: the wave of the last strip reports B(START, START).IMM (its own store, read back past the L1)
+    if (MULTI && s == n_strips - 1 && lane == 0)
+      *J.lp_start = dead ? __builtin_nan("") : __hip_atomic_load(m.M + cell_slot(m.ss, R - 1, Cc - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+  if (MULTI) return;
+  __syncthreads();
+  if (threadIdx.x == 0) *J.lp_start = J.bwd[cell_slot(m.ss, R - 1, Cc - 1)];   // B(0,0).IMM in mirrored coordinates
 }
 
 // ---------------------------------------------------------------------------
@@ -868,7 +667,7 @@ __device__ __forceinline__ unsigned slot_at(const RowRef& r, int c) {
 // what the next step may need from the cell a lane has just computed
 // The matrix (and the scratch planes addressed relative to it) as the Forward pipeline reads and writes it.  COH: other
 // workgroups fill other strips of the same pair (the MULTI launch of k_forward_dag_pipe): every access is `sc1` - stores
-// write through, loads bypass the L1 - the hand-off of k_backward_dag_multi.
+// write through, loads bypass the L1 (hx_handoff.h).
 template <bool COH>
 struct PairPlanes {
   HX_GLOBAL double* p;
@@ -890,7 +689,7 @@ struct PairPlanes {
 
 struct Fwd10 { double imm, imd, idm, imi, iiw, g0, g1, g2, g3, g4; };
 
-// MULTI: one pair's strips dealt to `groups` workgroups (one or two pairs of many strips: see k_backward_dag_multi for the
+// MULTI: one pair's strips dealt to `groups` workgroups (one or two pairs of many strips: see hx_handoff.h for the
 // hand-off; the progress counters - 256 ints per pair - are a region the host passes in, zeroed before the launch).
 template <class LSE, bool FAST, bool MULTI = false>
 __global__ void __launch_bounds__(MULTI ? HX_DAGF_MULTI_WAVES * 64 : HX_DAGF_MAX_WAVES * 64) k_forward_dag_pipe(const DevJob* __restrict__ jobs,
@@ -939,6 +738,8 @@ __global__ void __launch_bounds__(MULTI ? HX_DAGF_MULTI_WAVES * 64 : HX_DAGF_MAX
   const int WT = W * G, gw = grp * W + wave;      // the pair's waves, and this one among them
   const int prev_wave = (gw + WT - 1) % WT;
   bool dead = false;                              // MULTI: a poll ran out of patience - run out without computing
+  // (the wait and the publish of hx_handoff.h, written out: through the calls the several-workgroups launch measured 0.5 %
+  // slower in the posterior-profile reconstruction, profiles/r16/ab_recon_posterior.txt)
   const auto read_progress = [&](const int of) -> int {
     if (MULTI) return __hip_atomic_load(gprog + of, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return progp[of];
@@ -1009,7 +810,7 @@ __global__ void __launch_bounds__(MULTI ? HX_DAGF_MULTI_WAVES * 64 : HX_DAGF_MAX
     long long tr_last = (long long)__builtin_readcyclecounter();
     int tr_steps = 0;
 #endif
-    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};
+    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};   // the strip's step windows (hx_handoff.h), the whole sweep when unbanded
     if (banded) {
       wlo[0] = win[4 * s]; whi[0] = win[4 * s + 1];
       wlo[1] = win[4 * s + 2]; whi[1] = win[4 * s + 3];
@@ -1368,7 +1169,7 @@ __global__ void __launch_bounds__(MULTI ? HX_DAGF_MULTI_WAVES * 64 : HX_DAGF_MAX
         // ---- publish, every 8th step: drain, then all stores issued so far (the cells of steps <= t-1)
         // are in memory, i.e. all 64 rows have completed the columns up to t - 1 - 63
         if ((t & 7) == 7) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          drain_stores();
           int done = t - 63;
           done = done > Cc ? Cc : done;
           if (dead) done = Cc;
@@ -1395,7 +1196,7 @@ __global__ void __launch_bounds__(MULTI ? HX_DAGF_MULTI_WAVES * 64 : HX_DAGF_MAX
         M[aggoff + 3 * plane + pend_slot] = own10.g3;
         M[aggoff + 4 * plane + pend_slot] = own10.g4;
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      drain_stores();
       // columns between / after the windows hold no in-envelope cell of this strip
       const int upto = (w == 0 && whi[1] > wlo[1]) ? wlo[1] - 63 : Cc;
       const int done = (dead || upto > Cc) ? Cc : upto;
@@ -1418,7 +1219,7 @@ __global__ void __launch_bounds__(MULTI ? HX_DAGF_MULTI_WAVES * 64 : HX_DAGF_MAX
       // the last strip finishes last (every strip follows the one above): all of the pair's cells are in memory.  What END
       // reads may lie in other workgroups' strips: drop this CU's L1 first (agent-scope acquire = buffer_inv sc1).
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      drain_stores();
       if (lane == 0) *J.lp_end = dead ? __builtin_nan("") : forward_lp_end(J, ExactLse{exact_tab});
     }
   }
@@ -1527,22 +1328,22 @@ int launch_backward_dag_pipe(const DevJob* d_jobs, int n_jobs, int max_rows, Tab
   const double* tab = tab8.p;
   const double* fast_tab = tab16.p;
   const dim3 g(n_jobs), b(dag_waves(max_rows, HX_DAG_MAX_WAVES) * 64);
-  // one or two pairs of more than sixteen strips: several workgroups per pair (k_backward_dag_multi); the caller has zeroed
-  // the progress counters
+  // one or two pairs of more than sixteen strips: several workgroups per pair (MULTI); the caller has zeroed the progress
+  // counters
   if (records && multi > 1) {
     const dim3 gm(n_jobs * multi), bm((multi_waves > 0 && multi_waves <= HX_DAG_REC_WAVES ? multi_waves : HX_DAG_REC_WAVES) * 64);
-    if (fast) hipLaunchKernelGGL((k_backward_dag_multi<FastLse, true>), gm, bm, 0, st, d_jobs, tab, fast_tab, multi, multi_patience());
-    else hipLaunchKernelGGL((k_backward_dag_multi<ExactLse3, false>), gm, bm, 0, st, d_jobs, tab, fast_tab, multi, multi_patience());
+    if (fast) hipLaunchKernelGGL((k_backward_dag_strips<FastLse, true, true, true>), gm, bm, 0, st, d_jobs, tab, fast_tab, multi, multi_patience());
+    else hipLaunchKernelGGL((k_backward_dag_strips<ExactLse3, false, true, true>), gm, bm, 0, st, d_jobs, tab, fast_tab, multi, multi_patience());
     return 0;
   }
   if (records) {
     const dim3 br(dag_waves(max_rows, HX_DAG_REC_WAVES) * 64);
-    if (fast) hipLaunchKernelGGL((k_fill_dag<1, FastLse, true, true>), g, br, 0, st, d_jobs, tab, fast_tab);
-    else hipLaunchKernelGGL((k_fill_dag<1, ExactLse3, false, true>), g, br, 0, st, d_jobs, tab, fast_tab);
+    if (fast) hipLaunchKernelGGL((k_backward_dag_strips<FastLse, true, true>), g, br, 0, st, d_jobs, tab, fast_tab);
+    else hipLaunchKernelGGL((k_backward_dag_strips<ExactLse3, false, true>), g, br, 0, st, d_jobs, tab, fast_tab);
     return 0;
   }
-  if (fast) hipLaunchKernelGGL((k_fill_dag<1, FastLse, true>), g, b, 0, st, d_jobs, tab, fast_tab);
-  else hipLaunchKernelGGL((k_fill_dag<1, ExactLse3, false>), g, b, 0, st, d_jobs, tab, fast_tab);
+  if (fast) hipLaunchKernelGGL((k_backward_dag_strips<FastLse, true>), g, b, 0, st, d_jobs, tab, fast_tab);
+  else hipLaunchKernelGGL((k_backward_dag_strips<ExactLse3, false>), g, b, 0, st, d_jobs, tab, fast_tab);
   return 0;
 }
 

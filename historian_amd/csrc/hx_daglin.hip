@@ -25,6 +25,7 @@
 #include "hx_common.h"
 #include "hx_policy.h"
 #include "hx_kernels.h"
+#include "hx_handoff.h"
 
 namespace hx {
 
@@ -106,7 +107,7 @@ __device__ __forceinline__ void add2(Acc2& A, const double ma, const double mb, 
   A.E = En;
 }
 
-// COH: the pair's strips are dealt to several workgroups (the MULTI launch, see hx_dag.hip k_backward_dag_multi): every
+// COH: the pair's strips are dealt to several workgroups (the MULTI launch, see hx_handoff.h): every
 // scratch access is `sc1` - stores write through, loads bypass the L1
 template <bool COH = false>
 __device__ __forceinline__ double ldg(const HX_GLOBAL double* base, const unsigned byte_off) {
@@ -258,6 +259,8 @@ __global__ void __launch_bounds__(HXD_MAX_WAVES * 64) k_forward_dag_linear(const
   const int WT = W * G, gw = grp * W + wave;      // the pair's waves, and this one among them
   const int prev_wave = (gw + WT - 1) % WT;
   bool dead = false;                              // MULTI: a poll ran out of patience - run out without computing
+  // (the wait and the publish of hx_handoff.h, written out: through the calls the several-workgroups launch measured 0.5 %
+  // slower in the posterior-profile reconstruction, profiles/r16/ab_recon_posterior.txt)
   const auto read_progress = [&](const int of) -> int {
     if (MULTI) return __hip_atomic_load(gprog + of, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return progp[of];
@@ -353,7 +356,7 @@ __global__ void __launch_bounds__(HXD_MAX_WAVES * 64) k_forward_dag_linear(const
     long long tr_last = (long long)__builtin_readcyclecounter();
     int tr_steps = 0;
 #endif
-    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};
+    int wlo[2] = {0, 0}, whi[2] = {Cc + 63, 0};   // the strip's step windows (hx_handoff.h), the whole sweep when unbanded
     if (banded) {
       wlo[0] = win[4 * s]; whi[0] = win[4 * s + 1];
       wlo[1] = win[4 * s + 2]; whi[1] = win[4 * s + 3];
@@ -705,7 +708,7 @@ __global__ void __launch_bounds__(HXD_MAX_WAVES * 64) k_forward_dag_linear(const
         // ---- publish, every 8th step: drain, then all stores issued so far (the cells of steps <= t - 1) are in memory,
         // i.e. all 64 rows have completed the columns up to t - 1 - 63
         if ((t & 7) == 7) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          drain_stores();
           int done = t - 63;
           done = (dead || done > Cc) ? Cc : done;
           if (done > published) {
@@ -722,7 +725,7 @@ __global__ void __launch_bounds__(HXD_MAX_WAVES * 64) k_forward_dag_linear(const
 #pragma unroll
       for (int v = 0; v < V_PLANES; ++v) stg<MULTI>(LIN, v * planeB + pv.slot, pv.v[v]);
       stgi<MULTI>(EX, pv.slot >> 1, pv.E);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      drain_stores();
       // columns between / after the windows hold no in-envelope cell of this strip
       const int upto = (w == 0 && whi[1] > wlo[1]) ? wlo[1] - 63 : Cc;
       const int done = (dead || upto > Cc) ? Cc : upto;
@@ -746,7 +749,7 @@ __global__ void __launch_bounds__(HXD_MAX_WAVES * 64) k_forward_dag_linear(const
       // the last strip finishes last (every strip follows the one above): all of the pair's cells are in memory.  What END
       // reads may lie in other workgroups' strips: drop this CU's L1 first (agent-scope acquire), as k_forward_dag_pipe does
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      drain_stores();
       if (lane == 0) *J.lp_end = dead ? __builtin_nan("") : forward_lp_end(J, ExactLse{exact_tab});
     }
   }

@@ -88,14 +88,16 @@ void launch_band2_result(const DevJob* d_jobs, int n_jobs, int dir, Tab8 tab, hi
 int launch_backward_band2(const DevJob* d_jobs, int n_jobs, bool trunc, int max_rows, int max_cols, int max_cls, Tab8 tab, Tab16 log_tab,
                           bool write_edges, hipStream_t st, hipStream_t edge_st);
 
-// Several-workgroups-per-pair launches of the general-profile fills (hx_dag.hip, hx_daglin.hip): polls of another workgroup's
-// progress before a wave gives up (HX_MULTI_PATIENCE overrides; 0 makes every unsatisfied wait give up - the tests' way of
-// forcing the error path), and the progress value a wave that gave up publishes: every wave that waits on it - directly or
-// through the waves in between - gives up as well, down to the wave of the last strip, which reports NaN.
+// Several-workgroups-per-pair launches (hx_handoff.h): polls of another workgroup's progress before a wave gives up.  The
+// chain and leaf-linear fills compile the default in; the general-profile fills (hx_dag.hip, hx_daglin.hip) take it as a
+// kernel argument (HX_MULTI_PATIENCE overrides; 0 makes every unsatisfied wait give up - the tests' way of forcing the
+// error path).  HX_MULTI_POISON: the progress value a wave of theirs that gave up publishes - every wave that waits on it,
+// directly or through the waves in between, gives up as well, down to the wave of the last strip, which reports NaN.
+#define HX_MULTI_PATIENCE_DEFAULT (1 << 22)
 #define HX_MULTI_POISON 0x7FFFFFFF
 inline int multi_patience() {
   const char* e = getenv("HX_MULTI_PATIENCE");
-  return e ? atoi(e) : (1 << 22);
+  return e ? atoi(e) : HX_MULTI_PATIENCE_DEFAULT;
 }
 
 void launch_indel_counts(const DevJob* d_jobs, int job, const double* d_tm, double* d_out, int64_t cells, Tab8 tab, bool plane_valid,

@@ -47,6 +47,7 @@
 #include "hx_common.h"
 #include "hx_policy.h"
 #include "hx_kernels.h"
+#include "hx_handoff.h"
 
 namespace hx {
 
@@ -173,10 +174,8 @@ struct LdsPlan { int elds, ycol, yclass, flags, zero;   // inside block A
 // recursion: B(i,j,s) = sum over the destination cells (i+1,j+1), (i+1,j), (i,j+1) of P[s][dest state] x emission x B(dest).
 // MULTI: few pairs of many strips (one rank's share of a strong-scaling run): a pair's passes of W strips are dealt to
 // `groups` workgroups, so that its waves spread over several CUs.  Inside a workgroup nothing changes (LDS rings); the
-// wrap-around link - already a trip through the matrix - now crosses workgroups: write-through stores (`sc1`), its progress
-// counter in memory (`counters`: 256 zeroed ints per pair, one per workgroup, [255] = a poll gave up), `sc1` polls that give
-// up after HXL_PATIENCE rounds (the pair's lpEnd / lpStart becomes NaN).  As k_fill_chain's MULTI (hx_chain.hip).
-#define HXL_PATIENCE (1 << 22)
+// wrap-around link - already a trip through the matrix - now crosses workgroups (hx_handoff.h): its progress counter in memory
+// (`counters`: 256 zeroed ints per pair, one per workgroup, [255] = a poll gave up: the pair's lpEnd / lpStart becomes NaN).
 template <int W, bool BANDED, int PPW, int DIR, bool MULTI = false, bool TRUNC = false, bool FOLD = false>
 __global__ void __launch_bounds__(W * PPW * 64, 4)   // four waves per SIMD: 128 vector registers
 k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ exact_tab, const double* __restrict__ log_tab,
@@ -287,27 +286,16 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
   const int prev_grp = (grp + G - 1) % G;
   bool dead = false;                                // MULTI: a poll ran out of patience
   const auto wait_drained = [&](const int need) {   // the wrap-around link: columns of the strip above that are in memory
-    if (!MULTI) {
-      while (drainp[0] < need) __builtin_amdgcn_s_sleep(1);
-      asm volatile("" ::: "memory");
-      return;
+    if (!MULTI) return lds_wait<1>(drainp, 0, need);
+    int seen = 0;
+    if (!dead && agent_wait<1>(gdrain, prev_grp, seen, need, HX_MULTI_PATIENCE_DEFAULT)) {
+      dead = true;
+      raise_gave_up(gdrain, lane);
     }
-    if (dead) return;
-    int polls = 0;
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(gdrain + prev_grp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < need) {
-      if (++polls > HXL_PATIENCE) {
-        dead = true;
-        if (lane == 0) __hip_atomic_store(gdrain + 255, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    asm volatile("" ::: "memory");
   };
-  const auto publish_drained = [&](const int value) {   // (behind the caller's s_waitcnt)
-    if (lane != 0) return;
-    if (MULTI) __hip_atomic_store(gdrain + grp, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else drainp[0] = value;
+  const auto publish_drained = [&](const int value) {   // (behind the caller's drain)
+    if (MULTI) agent_publish(gdrain + grp, lane, value);
+    else if (lane == 0) drainp[0] = value;
   };
   // Strips are dealt round-robin, so with more strips than waves the last wave feeds the first one's NEXT strip, which
   // starts a whole sweep later: that link cannot be a bounded ring (the waves would wait for each other in a circle).
@@ -367,6 +355,7 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     // untouched - with the ring entry as its `old` operand, lane 0 receives the boundary cell in the same instruction.
     auto wait_for = [&](const int cols) {          // columns of the strip above that must have been written
       const int need = above_base + (cols < Cc ? cols : Cc);
+      // (hx_handoff.h lds_wait, written out: through the call the headline instantiations spill two more vector registers)
       while (progp[prev_wave] < need) __builtin_amdgcn_s_sleep(1);
       asm volatile("" ::: "memory");               // the ring reads below stay below
     };
@@ -391,13 +380,8 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         q[0] = d2v{0., 0.}; q[1] = d2v{0., 0.}; q[2] = d2v{0., __hiloint2double(0, HXL_EMIN)};
       }
       if (sl >= 0) {
-        // agent-scope relaxed loads: served by L2, never by a stale L1 line
-        const double a = __hip_atomic_load(M + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double b = __hip_atomic_load(M + plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double c = __hip_atomic_load(M + 2 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double d = __hip_atomic_load(M + 3 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double g = __hip_atomic_load(M + 4 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        L5 v = from_logs(a, b, c, d, g);
+        const Planes<5> c = load_cell_agent<5>(M, plane, sl);
+        L5 v = from_logs(c.v[0], c.v[1], c.v[2], c.v[3], c.v[4]);
         if (BANDED && max_dist >= 0) {
           // the strip above only wrote its in-envelope cells (HX_SPARSE_ENVELOPE: anything else is undefined)
           const int ia = DIR ? R - row0 : row0 - 1, ja = DIR ? Cc - 1 - jj : jj;   // the cell's x and y states
@@ -573,7 +557,7 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         if ((col & 7) == 0) {
           // flow control: the slots of the next eight columns must have been consumed
           const int need = my_base + col + 8 - HXL_RING;
-          while (consp[next_wave] < need) __builtin_amdgcn_s_sleep(1);
+          while (consp[next_wave] < need) __builtin_amdgcn_s_sleep(1);   // (lds_wait written out, as wait_for above)
           asm volatile("" ::: "memory");
         }
         if (lane == 63) {
@@ -703,12 +687,8 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         HX_GLOBAL d2v* M2 = (HX_GLOBAL d2v*)(M + (store_base + (lane << 1) + (int64_t)((t - store_t0) >> 1) * blk));
         const int64_t plane2 = plane >> 1;
         if (MULTI) {
-          const d2v v0{l0, h0}, v1{l1, h1}, v2{l2, h2}, v3{l3, h3}, v4{l4, h4};
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[0]), "v"(v0) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[plane2]), "v"(v1) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[2 * plane2]), "v"(v2) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[3 * plane2]), "v"(v3) : "memory");
-          asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(&M2[4 * plane2]), "v"(v4) : "memory");
+          const d2v v[5] = {{l0, h0}, {l1, h1}, {l2, h2}, {l3, h3}, {l4, h4}};
+          store_pair_through<5>(M2, plane2, v);
         } else {
           __builtin_nontemporal_store(d2v{l0, h0}, &M2[0]);
           __builtin_nontemporal_store(d2v{l1, h1}, &M2[plane2]);
@@ -718,21 +698,16 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
         }
       }
       if (wrap_out && !BANDED) {
-        // wrap-around link: a column counts once its stores have left the wave.  Vector-memory operations retire in
-        // issue order and every iteration issues five stores (and nothing else), so everything stored
-        // HXL_PUBLISH_LAG steps = 8 iterations ago is older than the wave's 40 youngest operations.
+        // wrap-around link, published lagged: every iteration issues five stores (and nothing else)
         const int nsteps2 = MASKED ? (nsteps + 1) & ~1 : nsteps;   // (whole step pairs)
         const int fin = (t + 2 < nsteps2 ? t + 2 : nsteps2) - 63;
         if (fin >= Cc) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          drain_stores();
           publish_drained(my_base + Cc);
         } else {
           const int done = fin - HXL_PUBLISH_LAG;
           if (done > 0 && ((done >> 6) != ((done - 2) >> 6))) {
-            // (five stores per iteration and nothing else: the HXL_PUBLISH_LAG / 2 iterations since hold exactly this many)
-            constexpr int PUBLISH_WAIT = 5 * (HXL_PUBLISH_LAG / 2);
-            static_assert(PUBLISH_WAIT <= 63 && HXL_PUBLISH_LAG % 2 == 0, "s_waitcnt vmcnt holds 6 bits");
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PUBLISH_WAIT) : "memory");
+            drain_lagged<5, HXL_PUBLISH_LAG>();
             publish_drained(my_base + done);
           }
         }
@@ -742,16 +717,13 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     }
     if (BANDED && wrap_out) {
       // (the windows need not reach the strip's last step: everything this strip will ever write is out)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      drain_stores();
       publish_drained(my_base + Cc);
     }
     if (has_above && !wrap_in && lane == 0) consp[wave] = above_base + Cc;
     if (MULTI && s == n_strips - 1) {
       // the last strip finishes last; what lpEnd / lpStart read lies in this strip - its stores are write-through
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const bool gave_up = __hip_atomic_load(gdrain + 255, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+      const bool gave_up = acquire_gave_up(gdrain);
       if (lane == 0) {
         if (DIR == 0) *J.lp_end = gave_up ? __builtin_nan("") : forward_lp_end(J, ExactLse{exact_tab});
         else *J.lp_start = gave_up ? __builtin_nan("") : J.bwd[cell_slot_blk(ss, blk, R - 1, Cc - 1)];
@@ -759,7 +731,7 @@ k_fill_leaf_linear(const DevJob* __restrict__ jobs, const double* __restrict__ e
     }
   }
   if (MULTI) return;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  drain_stores();
   __syncthreads();
   if (live && wave == 0 && lane == 0) {
     if (DIR == 0) *J.lp_end = forward_lp_end(J, ExactLse{exact_tab});

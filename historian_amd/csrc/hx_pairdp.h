@@ -23,6 +23,7 @@
 #include "hx_device.h"
 #include "hx_lse.h"
 #include "hx_policy.h"
+#include "hx_handoff.h"
 #include "../../include/historian_hip.h"
 
 namespace hx {
@@ -78,17 +79,6 @@ __global__ void k_pair_clear(const Job* __restrict__ jobs) {
 // value of lane `src` (wave-uniform)
 __device__ __forceinline__ double read_lane64(const double v, const int src) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
-
-// The strip hand-off: a strip publishes how many columns of its last row are stored (a monotonic count in LDS, written
-// behind a drain of the wavefront's stores); the strip below waits until the count covers the columns it is about to load
-// with agent-scope loads.  Strip s waits for strip s - 1 only, so waits cannot form a cycle.
-__device__ __forceinline__ void strip_wait(volatile int* prog, const int above, int& seen, const int need) {
-  while (seen < need) {
-    seen = __builtin_amdgcn_readfirstlane(prog[above]);
-    if (seen < need) __builtin_amdgcn_s_sleep(2);
-  }
-  asm volatile("" ::: "memory");
 }
 
 typedef double d2v __attribute__((ext_vector_type(2)));
@@ -174,7 +164,7 @@ __global__ void __launch_bounds__(64 * HXBR_MAX_WAVES) k_pair_fill(const typenam
     if (s > 0 && t0 >= 1 && t0 - 1 < Y) {
       // ... except lane 0's diagonal source of the window's first step: cell (row above, column t0 - 1) belongs to the strip
       // above, whose band may well hold it
-      strip_wait(prog, s - 1, seen, t0);
+      lds_wait<2>(prog, s - 1, seen, t0);
       if (lane == 0) {
         const int64_t sl = cell_slot(ss, (s << 6) - 1, t0 - 1);
 #pragma unroll
@@ -189,7 +179,7 @@ __global__ void __launch_bounds__(64 * HXBR_MAX_WAVES) k_pair_fill(const typenam
         // the strip above's last row, HXBR_BLK columns at a time
         const int c0 = t & ~(HXBR_BLK - 1);
         const int need = c0 + HXBR_BLK < Y ? c0 + HXBR_BLK : Y;
-        strip_wait(prog, s - 1, seen, need);
+        lds_wait<2>(prog, s - 1, seen, need);
         const int c = c0 + lane;
         const bool take = lane < HXBR_BLK && c < Y;
         const int64_t sl = cell_slot(ss, (s << 6) - 1, take ? c : 0);
@@ -252,7 +242,7 @@ __global__ void __launch_bounds__(64 * HXBR_MAX_WAVES) k_pair_fill(const typenam
       if (feeds && (t & 1)) {                       // (behind the store of a step pair)
         const int done = t - 63 + 1;                // columns of lane 63's row computed and stored so far (odd)
         if (done > 0 && ((done & (HXBR_BLK - 1)) == 1 || done >= Y)) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          drain_stores();
           if (lane == 0) prog[s] = done < Y ? done : Y;
         }
       }
@@ -260,13 +250,13 @@ __global__ void __launch_bounds__(64 * HXBR_MAX_WAVES) k_pair_fill(const typenam
     // behind a window: the last row is final up to where the next window takes it up
     {
       const int nt0 = (wn && wi + 1 < 3 && wn[2 * wi + 3] > wn[2 * wi + 2]) ? wn[2 * wi + 2] : Y + 63;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      drain_stores();
       int fin = nt0 - 63;
       fin = fin < 0 ? 0 : (fin > Y ? Y : fin);
       if (feeds && lane == 0 && fin > 0) prog[s] = fin;
     }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    drain_stores();
     if (feeds && lane == 0) prog[s] = Y;
     if (s == n_strips - 1 && lane == 0) {
       const int64_t sl = cell_slot(ss, X - 1, Y - 1);

@@ -23,6 +23,7 @@
 #include "hx_lse.h"
 #include "hx_policy.h"
 #include "hx_kernels.h"
+#include "hx_handoff.h"
 
 namespace hx {
 
@@ -124,14 +125,13 @@ __global__ void __launch_bounds__(W * 64) k_quickalign(const DevQuick* __restric
         if ((t & 63) == 0 && t < Cc) {
           const int hi = (t + 64 < Cc) ? t + 64 : Cc;
           const int need = above_base + hi;
-          while (progp[prev_wave] < need) __builtin_amdgcn_s_sleep(1);
+          lds_wait<1>(progp, prev_wave, need);
           const int cc = t + lane;
           bnd = q3_neg_inf();
           if (cc < Cc) {
             const int64_t sl = cell_slot_blk(ss, blk, row0 - 1, cc);
-            bnd.mat = __hip_atomic_load(M + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bnd.ins = __hip_atomic_load(M + plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bnd.del = __hip_atomic_load(M + 2 * plane + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const Planes<3> q = load_cell_agent<3>(M, plane, sl);
+            bnd = Q3{q.v[0], q.v[1], q.v[2]};
           }
           asm volatile("" : "+v"(bnd.mat), "+v"(bnd.ins), "+v"(bnd.del));
         }
@@ -184,23 +184,16 @@ __global__ void __launch_bounds__(W * 64) k_quickalign(const DevQuick* __restric
       M2[0] = d2v{ca.mat, cb.mat};
       M2[plane2] = d2v{ca.ins, cb.ins};
       M2[2 * plane2] = d2v{ca.del, cb.del};
-      // publish progress: the strip's last row has finished column (t + 1) - 63; a column counts once its
-      // stores have left the wave.  Vector-memory operations retire in issue order and every iteration
-      // (two steps) issues at least its 3 stores (with the full envelope and the column tables in LDS it
-      // issues nothing else), so everything stored HX_QA_LAG steps = HX_QA_LAG / 2 iterations ago is older
-      // than the wave's PUBLISH_WAIT youngest operations (the same guard as in hx_chain.hip)
-      constexpr int STORES_PER_ITER = 3;
-      constexpr int PUBLISH_WAIT = STORES_PER_ITER * (HX_QA_LAG / 2) < 63 ? STORES_PER_ITER * (HX_QA_LAG / 2) : 63;
-      static_assert(PUBLISH_WAIT <= STORES_PER_ITER * (HX_QA_LAG / 2) && PUBLISH_WAIT <= 63 && HX_QA_LAG % 2 == 0,
-                    "the wait count must not exceed the operations issued since the published column's stores");
+      // publish progress, lagged: every iteration issues at least its 3 stores (with the full envelope and the column
+      // tables in LDS it issues nothing else)
       const int fin = (t + 2 < nsteps ? t + 2 : nsteps) - 63;
       if (fin >= Cc) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        drain_stores();
         if (lane == 0) progp[wave] = my_base + Cc;
       } else {
         const int done = fin - HX_QA_LAG;
         if (done > 0 && ((done >> 6) != ((done - 2) >> 6))) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PUBLISH_WAIT) : "memory");
+          drain_lagged<3, HX_QA_LAG>();
           if (lane == 0) progp[wave] = my_base + done;
         }
       }

@@ -8,7 +8,7 @@ One level of that workload, both kinds of pair DP a tree level holds:
   * an internal-node pair built the way Reconstructor::reconstruct builds them (best trace + 10 sampled traces of two
     leaf-level DPs, reference src/recon.cpp:1010), from 2000-column C = 4 leaves: general profiles with thousands of
     states, all emission columns distinct, so the per-cell emission plane (k_emission_plane) and the general pipeline
-    (k_forward_dag_pipe, k_fill_dag<1>) run with C = 4 at size.  Forward and Backward cells bit for bit against the
+    (k_forward_dag_pipe, k_backward_dag_strips) run with C = 4 at size.  Forward and Backward cells bit for bit against the
     oracle, lpEnd / lpStart, Forward == Backward.
 The sampled profiles are made with the oracle's traceback / makeProfile code over matrices the GPU filled (the pure-Python
 fill would take hours at this size); the oracle stays the checker, the HIP path is what is checked."""
@@ -107,7 +107,7 @@ def test_internal_node_pair_of_sampled_four_component_profiles():
             assert abs(lp_end - wf["lp_end"]) <= 1e-5 * abs(wf["lp_end"])
         assert abs(lp_start - lp_end) <= 1e-6 * abs(lp_end)              # Forward == Backward
         # a lone pair of more than sixteen strips: both fills dealt its strips to several workgroups (the MULTI launch of
-        # k_forward_dag_pipe / k_forward_dag_linear, k_backward_dag_multi: write-through hand-off between CUs).  One workgroup gives the same bits.
+        # k_forward_dag_pipe / k_forward_dag_linear, k_backward_dag_strips: write-through hand-off between CUs).  One workgroup gives the same bits.
         several = b.read_matrix(0, 1)
         several_fwd = b.read_matrix(0, 0)
         b.close()

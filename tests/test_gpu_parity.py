@@ -680,7 +680,7 @@ def test_a_pair_too_small_for_the_backward_sweep_stays_out_of_its_class():
 
 def test_a_small_batch_of_general_pairs_dealt_to_several_workgroups(monkeypatch):
     # Up to eight pairs of many strips get several workgroups each (the MULTI launches of k_forward_dag_pipe,
-    # k_forward_dag_linear and k_backward_dag_multi; strips handed on through memory).  HX_DAG_MULTI_MIN_STRIPS lowers the
+    # k_forward_dag_linear and k_backward_dag_strips; strips handed on through memory).  HX_DAG_MULTI_MIN_STRIPS lowers the
     # threshold so that pairs of two to eight strips take that launch: five pairs of different sizes, one banded, one of a
     # single strip (its other waves idle).  Same bits as one workgroup per pair, in every policy, both fills.
     cases = [H.dag_case(86, n=400, samples=3), H.dag_case(87, n=300, samples=3), H.dag_case(88, n=200, samples=4, band=6),
