@@ -68,6 +68,12 @@ class HxBranchJob(C.Structure):
                 ("max_distance", C.c_int32)]
 
 
+class HxHistoryBranch(C.Structure):
+    _fields_ = [("node", C.c_int32), ("log_sub", C.POINTER(C.c_double)), ("log_ins", C.POINTER(C.c_double)),
+                ("trans", (C.c_double * 4) * 3), ("x_env", C.POINTER(C.c_int32)), ("y_env", C.POINTER(C.c_int32)),
+                ("max_distance", C.c_int32)]
+
+
 class HxSiblingJob(C.Structure):
     _fields_ = [("l_len", C.c_int32), ("r_len", C.c_int32), ("components", C.c_int32), ("alphabet", C.c_int32),
                 ("l_sub", C.POINTER(C.c_double)), ("r_sub", C.POINTER(C.c_double)), ("log_root", C.POINTER(C.c_double)),
@@ -121,7 +127,8 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_history_create", "hx_history_destroy", "hx_history_propose", "hx_history_accept", "hx_history_reject",
            "hx_history_log_like", "hx_history_indel_counts", "hx_history_last_kernel_ms", "hx_history_set_rates",
            "hx_history_propose_lengths", "hx_history_create_from_lengths", "hx_history_branch_matrix", "hx_expm_shape",
-           "hx_history_last_expm_ms", "hx_history_row_lengths", "hx_history_excluded_profiles"]
+           "hx_history_last_expm_ms", "hx_history_row_lengths", "hx_history_excluded_profiles",
+           "hx_history_branch_batch_create", "hx_history_last_handoff_ms", "hx_branch_batch_read_inputs"]
 
 
 class HxError(RuntimeError):
@@ -230,6 +237,9 @@ def load():
     lib.hx_history_branch_matrix.argtypes = [vp, C.c_int32, C.c_int32, _f64p]
     lib.hx_history_row_lengths.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.hx_history_excluded_profiles.argtypes = [vp, C.c_int32, C.c_int32, _i32p, _i32p, C.c_int32, C.POINTER(_f64p), vp]
+    lib.hx_history_branch_batch_create.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(HxHistoryBranch), C.c_int32, vp, C.POINTER(vp)]
+    lib.hx_history_last_handoff_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.hx_branch_batch_read_inputs.argtypes = [vp, C.c_int32, _f64p, _f64p, _f64p]
     lib.hx_expm_shape.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p]
     lib.hx_batch_read_matrix_async.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
@@ -688,8 +698,28 @@ class BranchBatch(_PairWalks):
             j.max_distance = md
         self._jobs = arr
         self.shapes = [(j.x_len + 1, j.y_len + 1) for j in arr]
+        self.dims = [(j.components, j.alphabet) for j in arr]
         self._h = C.c_void_p()
         _check(load().hx_branch_batch_create(arr, self.n, C.byref(self._h)))
+
+    @classmethod
+    def wrap(cls, handle, shapes, dims):
+        """a batch around a handle the library made elsewhere (History.branch_batch); it owns the handle from here on.
+        shapes: (x_len + 1, y_len + 1) per job; dims: (C, A) per job"""
+        self = cls.__new__(cls)
+        self.n, self._keep, self._jobs = len(shapes), [], None
+        self.shapes, self.dims = [tuple(s) for s in shapes], [tuple(d) for d in dims]
+        self._h = handle
+        return self
+
+    def read_inputs(self, job):
+        """hx_branch_batch_read_inputs: (x_pwm [x_len][C][A], y_sub [y_len][C][A], y_emit [y_len]) as the fill reads them"""
+        if not 0 <= job < self.n:
+            _check(load().hx_branch_batch_read_inputs(self._h, job, None, None, None))      # raises HX_ERR_RANGE
+        (xs, ys), (c, a) = self.shapes[job], self.dims[job]
+        xp, yp, ye = np.empty((xs - 1, c, a)), np.empty((ys - 1, c, a)), np.empty(ys - 1)
+        _check(load().hx_branch_batch_read_inputs(self._h, job, _p(xp, _f64p), _p(yp, _f64p), _p(ye, _f64p)))
+        return xp, yp, ye
 
     def run(self, viterbi=True, stream=None):
         _check(load().hx_branch_batch_run(self._h, 1 if viterbi else 0, C.c_void_p(stream or 0)))
@@ -1040,16 +1070,66 @@ class History:
         p, n = self.excluded_profiles([(parent, node), (node, parent)], normalize=normalize, which=which)
         return p, n
 
+    def branch_batch(self, branches, normalize=True, which=0, stream=None):
+        """hx_history_branch_batch_create: branches [(node, log_sub [C][A][A], log_ins [C][A], trans [3][4], x_env or None,
+        y_env or None, max_distance)] -> a BranchBatch whose job k aligns parent(node) with node across their branch, its
+        profiles, preMultiply and calcInsProbs computed on the device and left there"""
+        n = len(branches)
+        arr = (HxHistoryBranch * max(n, 1))()
+        keep, shapes = [], []
+        lens = self.row_lengths()
+        parent = self._keep[0]
+        for k, (node, log_sub, log_ins, trans, xenv, yenv, md) in enumerate(branches):
+            ls = np.ascontiguousarray(log_sub, dtype=np.float64)
+            li = np.ascontiguousarray(log_ins, dtype=np.float64)
+            if ls.shape != (self.c, self.a, self.a) or li.shape != (self.c, self.a):
+                raise ValueError("log_sub must be [C][A][A] and log_ins [C][A]")
+            xe = None if xenv is None else np.ascontiguousarray(xenv, dtype=np.int32)
+            yv = None if yenv is None else np.ascontiguousarray(yenv, dtype=np.int32)
+            keep.append((ls, li, xe, yv))
+            j = arr[k]
+            j.node, j.log_sub, j.log_ins = node, _p(ls, _f64p), _p(li, _f64p)
+            for s in range(3):
+                for d in range(4):
+                    j.trans[s][d] = trans[s][d]
+            j.x_env = C.cast(None, _i32p) if xe is None else xe.ctypes.data_as(_i32p)
+            j.y_env = C.cast(None, _i32p) if yv is None else yv.ctypes.data_as(_i32p)
+            j.max_distance = md
+            if 0 <= node < self.n - 1:
+                shapes.append((int(lens[parent[node]]) + 1, int(lens[node]) + 1))
+        h = C.c_void_p()
+        _check(load().hx_history_branch_batch_create(self._h, which, 1 if normalize else 0, arr, n, C.c_void_p(stream or 0), C.byref(h)))
+        return BranchBatch.wrap(h, shapes, [(self.c, self.a)] * n)
+
     def kernel_ms(self):
         ms = C.c_float()
         _check(load().hx_history_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def handoff_ms(self):
+        """(profile kernels, insertion scores, preMultiply) of the last branch_batch; their sum is kernel_ms()"""
+        ms = (C.c_float * 3)()
+        _check(load().hx_history_last_handoff_ms(self._h, ms))
+        return tuple(ms)
 
     def expm_ms(self):
         """k_branch_expm's share of kernel_ms() (0 when the last evaluation brought its matrices)"""
         ms = C.c_float()
         _check(load().hx_history_last_expm_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+def branch_guide_envelope(tokens, parent_row, node_row):
+    """The envelope coordinates Refiner::refine gives a branch's DP (host only): GuideAlignmentEnvelope(pairPath(parent,
+    node), parent, node, d) with guideSeqPos(path, row) = 0 .. len (reference src/alignpath.cpp:282-310,
+    src/sampler.cpp:118-134).  tokens [n_cols][N], -2 a gap.  -> (x_env [len(parent) + 1], y_env [len(node) + 1]) int32:
+    x_env[i] = the columns in which both rows are ungapped up to and including that of the parent's i-th position,
+    x_env[0] = 0; y_env likewise along the node's positions."""
+    tok = np.asarray(tokens)
+    x, y = tok[:, parent_row] != -2, tok[:, node_row] != -2
+    matches = np.cumsum(x & y)
+    zero = np.zeros(1, dtype=np.int64)
+    return (np.concatenate([zero, matches[x]]).astype(np.int32), np.concatenate([zero, matches[y]]).astype(np.int32))
 
 
 def expm_shape(max_abs_rate, t):

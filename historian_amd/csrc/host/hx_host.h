@@ -950,6 +950,11 @@ struct TreeAlignFuncs {
     const LogProbModel logProbModel;
     LogProb mm, mi, md, me, im, ii, id, ie, dm, dd, de;
     AlignRowIndex xRow, yRow;
+  protected:
+    std::shared_ptr<hx_branch_batch> batch;     // the device-resident matrix (job 0 of its own batch); made before what the
+                                                // resident constructor reads back from it
+    const PosWeightMatrix xRead;                // the resident constructor's copy of the parent's profile (HX_HOST_WALKS=1 only)
+  public:
     const PosWeightMatrix& xSeq;
     const PosWeightMatrix ySub;
     const vguard<LogProb> yEmit;
@@ -959,6 +964,13 @@ struct TreeAlignFuncs {
     BranchMatrixBase(const RateModel& rates, const PosWeightMatrix& parent, const PosWeightMatrix& child, double branchLength,
                      const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos,
                      AlignRowIndex parentRow, AlignRowIndex childRow, bool viterbi);
+    // not in the reference: the matrix of the branch above `node` of a resident history (the one made from `rates` and
+    // `tree`), its profiles, preMultiply and calcInsProbs computed on the device and left there
+    // (hx_history_branch_batch_create, on normalised profiles unless `normalize` is false); rows parent(node) and node.  yEmit is read back once (logPathProb adds it on the
+    // host), xSeq and ySub only for the host walks of HX_HOST_WALKS=1 - they are empty otherwise.
+    BranchMatrixBase(hx_history* resident, const RateModel& rates, const ReconTree& tree, TreeNodeIndex node, double branchLength,
+                     const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos, bool viterbi,
+                     bool normalize = true);
     LogProb cell(SeqIdx xpos, SeqIdx ypos, unsigned int state) const;   // -inf outside the envelope; state End: lpEnd at the last cell
     LogProb cell(const CellCoords& at) const { return cell(at.xpos, at.ypos, at.state); }
     bool inEnvelope(SeqIdx xpos, SeqIdx ypos) const;
@@ -971,8 +983,8 @@ struct TreeAlignFuncs {
   protected:
     // the alignment a device walk's recorded states spell (End side first), as the reference's loops build it
     AlignPath pathOfStates(const unsigned char* states, int nSteps) const;
-    std::shared_ptr<hx_branch_batch> batch;     // the device-resident matrix (job 0 of its own batch)
   private:
+    void setTransitions();
     const GuideAlignmentEnvelope& env;
     const vguard<SeqIdx>& xEnvPos;
     const vguard<SeqIdx>& yEnvPos;
@@ -987,6 +999,9 @@ struct Refiner : TreeAlignFuncs {
                  const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos,
                  AlignRowIndex parentRow, AlignRowIndex childRow)
         : BranchMatrixBase(rates, parent, child, branchLength, envelope, xEnvelopePos, yEnvelopePos, parentRow, childRow, true) {}
+    BranchMatrix(hx_history* resident, const RateModel& rates, const ReconTree& tree, TreeNodeIndex node, double branchLength,
+                 const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos, bool normalize = true)
+        : BranchMatrixBase(resident, rates, tree, node, branchLength, envelope, xEnvelopePos, yEnvelopePos, true, normalize) {}
     AlignPath best() const;
   };
 };
@@ -1063,6 +1078,9 @@ struct Sampler : TreeAlignFuncs {
                  const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos,
                  AlignRowIndex parentRow, AlignRowIndex childRow)
         : BranchMatrixBase(rates, parent, child, branchLength, envelope, xEnvelopePos, yEnvelopePos, parentRow, childRow, false) {}
+    BranchMatrix(hx_history* resident, const RateModel& rates, const ReconTree& tree, TreeNodeIndex node, double branchLength,
+                 const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos, const vguard<SeqIdx>& yEnvelopePos, bool normalize = true)
+        : BranchMatrixBase(resident, rates, tree, node, branchLength, envelope, xEnvelopePos, yEnvelopePos, false, normalize) {}
   };
 
   // src/sampler.h:226-325, src/sampler.cpp:1185-1608: the parent-proposal DP of a sibling pair - left child profile against

@@ -89,9 +89,7 @@ TreeAlignFuncs::BranchMatrixBase::BranchMatrixBase(const RateModel& rates, const
       xSize((SeqIdx)xEnvelopePos.size()), ySize((SeqIdx)yEnvelopePos.size()), lpEnd(kNegInf), env(envelope), xEnvPos(xEnvelopePos),
       yEnvPos(yEnvelopePos) {
   Assert(xSize == parent.size() + 1 && ySize == child.size() + 1, "Envelope positions do not match the profiles");
-  mm = lpTrans(Match, Match); mi = lpTrans(Match, Insert); md = lpTrans(Match, Delete); me = lpTrans(Match, End);
-  im = lpTrans(Insert, Match); ii = lpTrans(Insert, Insert); id = lpTrans(Insert, Delete); ie = lpTrans(Insert, End);
-  dm = lpTrans(Delete, Match); dd = lpTrans(Delete, Delete); de = lpTrans(Delete, End);
+  setTransitions();
 
   // flatten for the C ABI
   const int C = probModel.components(), A = (int)rates.alphabetSize();
@@ -119,6 +117,82 @@ TreeAlignFuncs::BranchMatrixBase::BranchMatrixBase(const RateModel& rates, const
   detail::check(hx_branch_batch_run(b, viterbi ? 1 : 0, nullptr), "hx_branch_batch_run");
   batch.reset(b, [](hx_branch_batch* p) { hx_branch_batch_destroy(p); });
   detail::check(hx_branch_batch_results(b, &lpEnd), "hx_branch_batch_results");
+}
+
+void TreeAlignFuncs::BranchMatrixBase::setTransitions() {
+  mm = lpTrans(Match, Match); mi = lpTrans(Match, Insert); md = lpTrans(Match, Delete); me = lpTrans(Match, End);
+  im = lpTrans(Insert, Match); ii = lpTrans(Insert, Insert); id = lpTrans(Insert, Delete); ie = lpTrans(Insert, End);
+  dm = lpTrans(Delete, Match); dd = lpTrans(Delete, Delete); de = lpTrans(Delete, End);
+}
+
+// ---- the matrix of a branch of a resident history: nothing per position is computed or held on the host ----
+
+// the batch of the one branch above `node`: the logs of the branch's model (the host's libm), the transition scores and the
+// envelope's coordinates go in, the profiles stay on the device
+static std::shared_ptr<hx_branch_batch> residentBranchBatch(hx_history* resident, const ProbModel& probModel, const LogProbModel& logProbModel,
+                                                            TreeNodeIndex node, const GuideAlignmentEnvelope& env, const vguard<SeqIdx>& xEnvPos,
+                                                            const vguard<SeqIdx>& yEnvPos, bool normalize) {
+  vguard<double> logSub, logIns;
+  for (const Mat& m : logOf(probModel.subMat))
+    for (const Vec& row : m) logSub.insert(logSub.end(), row.begin(), row.end());
+  for (const auto& cpt : logProbModel.logInsProb) logIns.insert(logIns.end(), cpt.begin(), cpt.end());
+  vguard<int32_t> xe(xEnvPos.size(), 0), ye(yEnvPos.size(), 0);
+  if (env.initialized()) {
+    for (size_t i = 0; i < xe.size(); ++i) xe[i] = env.cumulativeMatches[env.row1PosToCol[xEnvPos[i]]];
+    for (size_t j = 0; j < ye.size(); ++j) ye[j] = env.cumulativeMatches[env.row2PosToCol[yEnvPos[j]]];
+  }
+  hx_history_branch br = {};
+  br.node = (int32_t)node;
+  br.log_sub = logSub.data();
+  br.log_ins = logIns.data();
+  const TreeAlignFuncs::State states[4] = {TreeAlignFuncs::Match, TreeAlignFuncs::Insert, TreeAlignFuncs::Delete, TreeAlignFuncs::End};
+  for (int s = 0; s < 3; ++s)
+    for (int d = 0; d < 4; ++d) br.trans[s][d] = log(TreeAlignFuncs::transProb(probModel, states[s], states[d]));
+  br.x_env = env.initialized() ? xe.data() : nullptr;
+  br.y_env = env.initialized() ? ye.data() : nullptr;
+  br.max_distance = env.maxDistance;
+  detail::ensureDevice();
+  hx_branch_batch* b = nullptr;
+  detail::check(hx_history_branch_batch_create(resident, 0, normalize ? 1 : 0, &br, 1, nullptr, &b), "hx_history_branch_batch_create");
+  return std::shared_ptr<hx_branch_batch>(b, [](hx_branch_batch* p) { hx_branch_batch_destroy(p); });
+}
+
+// [len][C][A] of job 0's x_pwm or y_sub, read back for the host walks; empty otherwise
+static TreeAlignFuncs::PosWeightMatrix residentProfile(hx_branch_batch* b, bool ofParent, size_t len, size_t C, size_t A) {
+  TreeAlignFuncs::PosWeightMatrix pwm;
+  if (!detail::hostWalks()) return pwm;
+  vguard<double> flat(len * C * A);
+  detail::check(hx_branch_batch_read_inputs(b, 0, ofParent ? flat.data() : nullptr, ofParent ? nullptr : flat.data(), nullptr), "hx_branch_batch_read_inputs");
+  pwm.assign(len, vguard<vguard<LogProb>>(C, vguard<LogProb>(A)));
+  const double* v = flat.data();
+  for (auto& pos : pwm)
+    for (auto& cpt : pos)
+      for (auto& lp : cpt) lp = *v++;
+  return pwm;
+}
+
+static vguard<LogProb> residentInsertions(hx_branch_batch* b, size_t len) {
+  vguard<LogProb> yEmit(len);
+  detail::check(hx_branch_batch_read_inputs(b, 0, nullptr, nullptr, yEmit.data()), "hx_branch_batch_read_inputs");
+  return yEmit;
+}
+
+TreeAlignFuncs::BranchMatrixBase::BranchMatrixBase(hx_history* resident, const RateModel& rates, const ReconTree& tree, TreeNodeIndex node,
+                                                   double branchLength, const GuideAlignmentEnvelope& envelope, const vguard<SeqIdx>& xEnvelopePos,
+                                                   const vguard<SeqIdx>& yEnvelopePos, bool viterbi, bool normalize)
+    : model(rates), probModel(rates, std::max(1e-9 /* Tree::minBranchLength, src/tree.h:24 */, branchLength)), logProbModel(probModel),
+      xRow((AlignRowIndex)tree.parent[node]), yRow((AlignRowIndex)node),
+      batch(residentBranchBatch(resident, probModel, logProbModel, node, envelope, xEnvelopePos, yEnvelopePos, normalize)),
+      xRead(residentProfile(batch.get(), true, xEnvelopePos.size() - 1, (size_t)probModel.components(), rates.alphabetSize())), xSeq(xRead),
+      ySub(residentProfile(batch.get(), false, yEnvelopePos.size() - 1, (size_t)probModel.components(), rates.alphabetSize())),
+      yEmit(residentInsertions(batch.get(), yEnvelopePos.size() - 1)), xSize((SeqIdx)xEnvelopePos.size()), ySize((SeqIdx)yEnvelopePos.size()),
+      lpEnd(kNegInf), env(envelope), xEnvPos(xEnvelopePos), yEnvPos(yEnvelopePos) {
+  vguard<int64_t> len((size_t)tree.nodes());
+  detail::check(hx_history_row_lengths(resident, len.data()), "hx_history_row_lengths");
+  Assert((int64_t)xSize == len[tree.parent[node]] + 1 && (int64_t)ySize == len[node] + 1, "Envelope positions do not match the rows of the history");
+  setTransitions();
+  detail::check(hx_branch_batch_run(batch.get(), viterbi ? 1 : 0, nullptr), "hx_branch_batch_run");
+  detail::check(hx_branch_batch_results(batch.get(), &lpEnd), "hx_branch_batch_results");
 }
 
 LogProb TreeAlignFuncs::BranchMatrixBase::cell(SeqIdx xpos, SeqIdx ypos, unsigned int state) const {

@@ -23,7 +23,7 @@
 //   hxtest treemoves <rows.fa> <tree.nh> <model.json> <steps> <seed>   a tree-height chain on a fixed alignment (node-height and
 //                                                  rescale moves, hx_host_sampler.cpp): the four likelihood parts of the initial
 //                                                  history, one line per step, the final tree
-//   hxtest condpwm <rows.fa> <tree.nh> <model.json> <node> <normalize>   the two excluded-neighbour profiles of the branch above
+//   hxtest condpwm <rows.fa> <tree.nh> <model.json> <node> <normalize> [device]   the two excluded-neighbour profiles of the branch above
 //                                                  <node> (TreeAlignFuncs::getConditionalPWMs), lpEnd of the unbanded
 //                                                  Sampler::BranchMatrix built from them, a seeded sample and its logPostProb
 #include <algorithm>
@@ -35,6 +35,7 @@
 #include <iostream>
 #include <sstream>
 #include "../hx_host.h"
+#include "../../../../include/historian_hip.h"
 using namespace historian;
 
 namespace {
@@ -377,8 +378,10 @@ int treeMoves(int, char** args) {
 // (src/sampler.cpp:582-594).  Prints "lengths <parent> <node>"; "parent <pos>" and "node <pos>" with the C x A entries of
 // every row of the two profiles (hex floats); "lpEnd" of an unbanded Sampler::BranchMatrix built from them; a seeded sample
 // as two rows of '*' and '-'; its "logPostProb".  <node> given as prune:<k> calls getConditionalPWMs with the map
-// PruneAndRegraftMove builds for node k (src/sampler.cpp:843-848): it aborts, those moves are not built.
-int conditionalProfiles(int, char** args) {
+// PruneAndRegraftMove builds for node k (src/sampler.cpp:843-848): it aborts, those moves are not built.  With a sixth
+// argument `device` the matrix is built from one resident history without the profiles passing through the host
+// (hx_history_branch_batch_create); the lines printed are the same.
+int conditionalProfiles(int nArgs, char** args) {
   vguard<FastSeq> rows = readFastSeqs(args[0]);
   std::ifstream treeFile(args[1]);
   Require(treeFile.good(), "Couldn't open %s", args[1]);
@@ -395,6 +398,7 @@ int conditionalProfiles(int, char** args) {
     history.gapped.push_back(*row);
   }
   const bool prune = strncmp(args[3], "prune:", 6) == 0;
+  Require(nArgs <= 5 || (strcmp(args[5], "device") == 0 && !prune), "The sixth argument is `device`, and not with prune:");
   const TreeNodeIndex node = (TreeNodeIndex)atoi(args[3] + (prune ? 6 : 0));
   Require(node >= 0 && node < tree.root(), "Node %d has no branch", (int)node);
   const TreeNodeIndex parent = tree.parent[node];
@@ -409,9 +413,13 @@ int conditionalProfiles(int, char** args) {
     (void)TreeAlignFuncs::getConditionalPWMs(rates, tree, history.gapped, exclude, unused, unused, normalize);
     return 0;
   }
+  const bool device = nArgs > 5;
   exclude[node] = parent;
   exclude[parent] = node;
-  const auto pwms = TreeAlignFuncs::getConditionalPWMs(rates, tree, history.gapped, exclude, unused, unused, normalize);
+  std::shared_ptr<hx_history> resident;
+  if (device) resident.reset(TreeAlignFuncs::residentHistory(rates, history), hx_history_destroy);
+  const auto pwms = device ? TreeAlignFuncs::getConditionalPWMs(resident.get(), rates, tree, exclude, normalize)
+                           : TreeAlignFuncs::getConditionalPWMs(rates, tree, history.gapped, exclude, unused, unused, normalize);
   const TreeAlignFuncs::PosWeightMatrix none;
   const auto& pSeq = pwms.count(parent) ? pwms.at(parent) : none;
   const auto& nSeq = pwms.count(node) ? pwms.at(node) : none;
@@ -429,11 +437,12 @@ int conditionalProfiles(int, char** args) {
   for (size_t k = 0; k < xPos.size(); ++k) xPos[k] = (SeqIdx)k;
   for (size_t k = 0; k < yPos.size(); ++k) yPos[k] = (SeqIdx)k;
   const GuideAlignmentEnvelope everywhere;
-  const Sampler::BranchMatrix matrix(rates, pSeq, nSeq, tree.branchLength(node), everywhere, xPos, yPos, 0, 1);
+  const Sampler::BranchMatrix matrix = device ? Sampler::BranchMatrix(resident.get(), rates, tree, node, tree.branchLength(node), everywhere, xPos, yPos, normalize)
+                                              : Sampler::BranchMatrix(rates, pSeq, nSeq, tree.branchLength(node), everywhere, xPos, yPos, 0, 1);
   printf("lpEnd %a\n", matrix.lpEnd);
   Sampler::BranchMatrix::random_engine generator(22);
   const AlignPath path = matrix.sample(generator);
-  for (AlignRowIndex row = 0; row < 2; ++row) {
+  for (AlignRowIndex row : {matrix.xRow, matrix.yRow}) {
     for (bool here : path.at(row)) putchar(here ? '*' : '-');
     putchar('\n');
   }
@@ -453,7 +462,7 @@ const Command commands[] = {
     {"walktime", 5, 6, "<seqfile> <modelfile> <left time> <right time> <matrices> [band]", walkTiming},
     {"distances", 2, 4, "<alignfile> <modelfile> [max iterations [host pairs]]", distances},
     {"treemoves", 5, 5, "<rows.fa> <tree.nh> <modelfile> <steps> <seed>", treeMoves},
-    {"condpwm", 5, 5, "<rows.fa> <tree.nh> <modelfile> <node | prune:node> <normalize>", conditionalProfiles},
+    {"condpwm", 5, 6, "<rows.fa> <tree.nh> <modelfile> <node | prune:node> <normalize> [device]", conditionalProfiles},
 };
 
 }  // namespace

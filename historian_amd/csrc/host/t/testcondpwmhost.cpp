@@ -80,9 +80,57 @@ static void planCases() {
   printf("plan: %d failures so far\n", failures);
 }
 
+// hx_history_branch_batch_create's share: the branches checked, the query's pairs and the jobs of the batch
+static void branchCases() {
+  const II parent = {4, 4, 5, 5, 6, 6, -1};
+  const LL len = {10, 0, 7, 7, 12, 9, 0};
+  const double sub[2 * 4 * 4] = {0}, ins[2 * 4] = {0};
+  const int32_t xe[13] = {0}, ye[11] = {0};
+  auto branch = [&](int node, int md) {
+    hx_history_branch b = {};
+    b.node = node; b.log_sub = sub; b.log_ins = ins; b.max_distance = md;
+    for (int s = 0; s < 3; ++s)
+      for (int d = 0; d < 4; ++d) b.trans[s][d] = -(double)(4 * s + d);
+    b.x_env = md >= 0 ? xe : nullptr;
+    b.y_env = md >= 0 ? ye : nullptr;
+    return b;
+  };
+  hx::BranchHandoffPlan p;
+  // a leaf branch with a band, a node without positions, a branch under a parent (the root) without positions
+  const hx_history_branch three[] = {branch(0, 2), branch(1, -1), branch(5, -1)};
+  EXPECT(hx::history_branch_plan(parent, len, 4, 2, three, 3, 65536, p) == 0);
+  EXPECT(p.node == II({4, 0, 4, 1, 6, 5}) && p.exclude == II({0, 4, 1, 4, 5, 6}) && p.jobs.size() == 3);
+  EXPECT(p.jobs[0].x_len == 12 && p.jobs[0].y_len == 10 && p.jobs[0].components == 2 && p.jobs[0].alphabet == 4);
+  EXPECT(p.jobs[0].max_distance == 2 && p.jobs[0].x_env == xe && p.jobs[0].y_env == ye && p.jobs[0].trans[2][3] == -11. && !p.jobs[0].x_pwm && !p.jobs[0].y_sub);
+  EXPECT(p.jobs[1].x_len == 12 && p.jobs[1].y_len == 0 && p.jobs[1].max_distance == -1 && !p.jobs[1].x_env);
+  EXPECT(p.jobs[2].x_len == 0 && p.jobs[2].y_len == 9);
+  // the pairs make a plan of the query
+  hx::ExcludedPlan q;
+  EXPECT(hx::history_excluded_plan(parent, len, 8, 6, p.node.data(), p.exclude.data(), q) == 0 && q.out_len == LL({12, 10, 12, 0, 0, 9}));
+  // refusals: the root and what lies outside; a range error wins over a null pointer
+  for (int node : {-1, 6, 7}) {
+    const hx_history_branch bad[] = {branch(0, -1), branch(node, -1)};
+    EXPECT(hx::history_branch_plan(parent, len, 4, 2, bad, 2, 65536, p) == 1 && p.jobs.empty());
+  }
+  hx_history_branch null_sub = branch(0, -1), null_ins = branch(0, -1), half = branch(0, 0), none = branch(0, 3), outside = branch(9, -1);
+  null_sub.log_sub = nullptr; null_ins.log_ins = nullptr; half.y_env = nullptr; none.x_env = none.y_env = nullptr; outside.log_sub = nullptr;
+  EXPECT(hx::history_branch_plan(parent, len, 4, 2, &null_sub, 1, 65536, p) == 2 && hx::history_branch_plan(parent, len, 4, 2, &null_ins, 1, 65536, p) == 2);
+  EXPECT(hx::history_branch_plan(parent, len, 4, 2, &half, 1, 65536, p) == 2 && hx::history_branch_plan(parent, len, 4, 2, &none, 1, 65536, p) == 2);
+  EXPECT(hx::history_branch_plan(parent, len, 4, 2, &outside, 1, 65536, p) == 1);
+  // a parent row at the limit: 12 positions are too many when fewer than 12 are allowed, fine when fewer than 13 are
+  const hx_history_branch leaf = branch(0, -1);
+  EXPECT(hx::history_branch_plan(parent, len, 4, 2, &leaf, 1, 12, p) == 3 && hx::history_branch_plan(parent, len, 4, 2, &leaf, 1, 13, p) == 0);
+  LL huge = len;
+  huge[0] = 0x7fffffffLL;
+  EXPECT(hx::history_branch_plan(parent, huge, 4, 2, &leaf, 1, 65536, p) == 3);
+  EXPECT(hx::history_branch_plan(parent, len, 4, 2, &leaf, 0, 65536, p) == 0 && p.jobs.empty());
+  printf("branches: %d failures so far\n", failures);
+}
+
 int main() {
   positionCases();
   planCases();
+  branchCases();
   printf(failures ? "testcondpwmhost: %d FAILED\n" : "testcondpwmhost: ok\n", failures);
   return failures;
 }

@@ -15,6 +15,7 @@
 // envelope; hx_branch_batch_read_matrix returns the dense [x_len + 1][y_len + 1][3] array.
 #include <hip/hip_runtime.h>
 #include "hx_pairbatch.h"
+#include "hx_branch_inputs.h"
 
 namespace hx {
 namespace {
@@ -87,12 +88,13 @@ struct BranchCell {
   static __device__ __forceinline__ bool self_loop(const int) { return false; }
 };
 
-// one job of the ABI -> its device job and its arrays in the arena
-int fill_job(DevBranch& J, const hx_branch_job& j, PairArena& a) {
+// one job of the ABI -> its device job and its arrays in the arena; `reserved`: the per-position inputs have no host copy,
+// the device fills their space
+int fill_job(DevBranch& J, const hx_branch_job& j, PairArena& a, const bool reserved) {
   if (j.x_len >= 64 * HXBR_MAX_STRIPS)
     return api_fail(HX_ERR_RANGE, "hx_branch_batch_create: a parent profile of more than 65535 positions");
   if (j.x_len < 0 || j.y_len < 0 || j.components < 1 || j.alphabet < 1 ||
-      (j.x_len && !j.x_pwm) || (j.y_len && (!j.y_sub || !j.y_emit)) || (j.max_distance >= 0 && (!j.x_env || !j.y_env)))
+      (!reserved && ((j.x_len && !j.x_pwm) || (j.y_len && (!j.y_sub || !j.y_emit)))) || (j.max_distance >= 0 && (!j.x_env || !j.y_env)))
     return api_fail(HX_ERR_INVALID_ARG, "hx_branch_batch_create: inconsistent job (lengths, components, missing arrays)");
   J.X = j.x_len + 1; J.Y = j.y_len + 1;
   J.CA = j.components * j.alphabet;
@@ -100,9 +102,15 @@ int fill_job(DevBranch& J, const hx_branch_job& j, PairArena& a) {
   J.max_dist = j.max_distance;
   for (int s = 0; s < 3; ++s)
     for (int d = 0; d < 4; ++d) J.T[s][d] = j.trans[s][d];
-  a.put(J.x_pwm, j.x_pwm, (size_t)j.x_len * J.CA);
-  a.put(J.y_sub, j.y_sub, (size_t)j.y_len * J.CA);
-  a.put(J.y_emit, j.y_emit, (size_t)j.y_len);
+  if (reserved) {
+    a.reserve(J.x_pwm, (size_t)j.x_len * J.CA);
+    a.reserve(J.y_sub, (size_t)j.y_len * J.CA);
+    a.reserve(J.y_emit, (size_t)j.y_len);
+  } else {
+    a.put(J.x_pwm, j.x_pwm, (size_t)j.x_len * J.CA);
+    a.put(J.y_sub, j.y_sub, (size_t)j.y_len * J.CA);
+    a.put(J.y_emit, j.y_emit, (size_t)j.y_len);
+  }
   a.put_env(J, j.x_env, j.y_env, !getenv("HX_BRANCH_NO_WINDOWS"));
   return HX_OK;
 }
@@ -116,12 +124,45 @@ struct hx_branch_batch : PairBatch<DevBranch, 3> {
   bool viterbi = false;             // the form of the last run
 };
 
+long long hx::branch_max_x_len() { return 64LL * HXBR_MAX_STRIPS; }
+
+int hx::branch_batch_reserve(const hx_branch_job* jobs, const double* const* log_sub, const double* const* log_ins, const int32_t n_jobs,
+                             hx_branch_batch** out, BranchInputs* where) {
+  const int rc = hx_branch_batch::create(jobs, n_jobs, out, [&](DevBranch& J, const hx_branch_job& j, PairArena& a) {
+    if (const int bad = fill_job(J, j, a, true)) return bad;
+    BranchInputs& w = where[&j - jobs];
+    a.put(w.log_sub, log_sub[&j - jobs], (size_t)j.components * j.alphabet * j.alphabet);
+    a.put(w.log_ins, log_ins[&j - jobs], (size_t)j.components * j.alphabet);
+    return (int)HX_OK;
+  });
+  if (rc != HX_OK) return rc;
+  for (int k = 0; k < n_jobs; ++k) {
+    const DevBranch& J = (*out)->jobs[k];
+    where[k].x_pwm = const_cast<double*>(J.x_pwm);
+    where[k].y_sub = const_cast<double*>(J.y_sub);
+    where[k].y_emit = const_cast<double*>(J.y_emit);
+  }
+  return HX_OK;
+}
+
 extern "C" {
 
 int hx_branch_batch_destroy(hx_branch_batch* b) { delete b; return HX_OK; }
 
 int hx_branch_batch_create(const hx_branch_job* jobs, int32_t n_jobs, hx_branch_batch** out) {
-  return hx_branch_batch::create(jobs, n_jobs, out, fill_job);
+  return hx_branch_batch::create(jobs, n_jobs, out, [](DevBranch& J, const hx_branch_job& j, PairArena& a) { return fill_job(J, j, a, false); });
+}
+
+int hx_branch_batch_read_inputs(hx_branch_batch* b, int32_t job, double* x_pwm, double* y_sub, double* y_emit) {
+  if (!b) return api_fail(HX_ERR_INVALID_ARG, "batch is null");
+  if (job < 0 || job >= b->n_jobs) return api_fail(HX_ERR_RANGE, "job out of range");
+  const DevBranch& J = b->jobs[job];
+  const size_t nx = sizeof(double) * (size_t)(J.X - 1) * J.CA, ny = sizeof(double) * (size_t)(J.Y - 1) * J.CA, ne = sizeof(double) * (size_t)(J.Y - 1);
+  if (hipSetDevice(b->device) != hipSuccess || (x_pwm && nx && hipMemcpy(x_pwm, J.x_pwm, nx, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (y_sub && ny && hipMemcpy(y_sub, J.y_sub, ny, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (y_emit && ne && hipMemcpy(y_emit, J.y_emit, ne, hipMemcpyDeviceToHost) != hipSuccess))
+    return api_fail(HX_ERR_HIP, "hx_branch_batch_read_inputs: HIP call failed");
+  return HX_OK;
 }
 
 int hx_branch_batch_run(hx_branch_batch* b, int32_t viterbi, void* stream) {

@@ -34,6 +34,8 @@
 #include "hx_kernels.h"
 #include "hx_sumprod.h"
 #include "hx_expm.h"
+#include "hx_history_host.h"
+#include "hx_branch_inputs.h"
 
 namespace hx {
 
@@ -352,6 +354,70 @@ __global__ void __launch_bounds__(256) k_history_excluded_norm(const long long* 
   }
 }
 
+// ---- the hand-off to the branch DP (hx_history_branch_batch_create): TreeAlignFuncs::calcInsProbs and preMultiply
+// (src/sampler.cpp:452-476) of a child's excluded-parent profile, which k_history_excluded wrote to the batch's y_sub ----
+struct HbJob {
+  const double* log_sub;           // [C][A][A] log exp(R t) of the branch, row = parent residue
+  const double* log_ins;           // [C][A]
+  double* y_sub;                   // [y_len][C][A]: the child's profile, then (in place) preMultiply of it
+  double* y_emit;                  // [y_len]
+  long long y_len;
+};
+
+// calcInsProbs, a lane per position: the table log_sum_exp folded over (lcw[c] + log_ins[c][a]) + child[c][a], c major
+// and a minor, from -inf.  Runs before k_history_pre_multiply overwrites the profile.
+__global__ void __launch_bounds__(256) k_history_ins_probs(const HbJob* __restrict__ jobs, const int n_jobs, const int C, const int A,
+                                                           const double* __restrict__ log_cpt_weight, const double* __restrict__ lse_tab) {
+  for (int k = (int)blockIdx.y; k < n_jobs; k += (int)gridDim.y) {
+    const HbJob J = jobs[k];
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < J.y_len; p += (long long)gridDim.x * blockDim.x) {
+      const double* v = J.y_sub + p * C * A;
+      double s = HX_NEG_INF;
+      for (int c = 0; c < C; ++c) {
+        const double lcw = log_cpt_weight[c];
+        for (int a = 0; a < A; ++a) s = lse(s, (lcw + J.log_ins[c * A + a]) + v[c * A + a], lse_tab);
+      }
+      J.y_emit[p] = s;
+    }
+  }
+}
+
+// preMultiply in place: out[pos][c][a] = the table log_sum_exp folded over log_sub[c][a][b] + child[pos][c][b], b ascending,
+// from -inf.  A workgroup takes (job, component, tile of P positions): log_sub[c] lies in LDS as [b][a], so the lanes of a
+// wave - neighbouring a of one position - read neighbouring words while child[pos][c][b] is one word for all of them; the
+// tile's rows are staged before any of them is overwritten, and no other workgroup touches them.  One component's matrix
+// at a time: C does not enter the LDS plan (8 A (A + P) bytes).  Every output is one thread's serial chain of A sums.
+__global__ void __launch_bounds__(256) k_history_pre_multiply(const HbJob* __restrict__ jobs, const int n_jobs, const int C, const int A, const int P,
+                                                              const double* __restrict__ lse_tab) {
+  extern __shared__ double sh_pm[];                  // [A][A] log_sub[c] transposed, then [P][A] the child rows of the tile
+  double* Ls = sh_pm;
+  double* Lc = sh_pm + A * A;
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  // (every trip count below is uniform over the workgroup: the barriers are reached by all of it)
+  for (int k = (int)blockIdx.z; k < n_jobs; k += (int)gridDim.z) {
+    const HbJob J = jobs[k];
+    const long long tiles = (J.y_len + P - 1) / P;
+    if ((long long)blockIdx.x >= tiles) continue;
+    for (int c = (int)blockIdx.y; c < C; c += (int)gridDim.y) {
+      __syncthreads();                               // (the reads of the previous matrix are done)
+      for (int e = tid; e < A * A; e += nt) Ls[(e % A) * A + e / A] = J.log_sub[(long long)c * A * A + e];
+      for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long p0 = tile * P;
+        const int n = (int)(J.y_len - p0 < P ? J.y_len - p0 : P) * A;
+        __syncthreads();                             // (the matrix is staged; the reads of the previous tile are done)
+        for (int e = tid; e < n; e += nt) Lc[e] = J.y_sub[((p0 + e / A) * C + c) * A + e % A];
+        __syncthreads();
+        for (int e = tid; e < n; e += nt) {
+          const int pl = e / A, a = e % A;
+          double acc = HX_NEG_INF;
+          for (int b = 0; b < A; ++b) acc = lse(acc, Ls[b * A + a] + Lc[pl * A + b], lse_tab);
+          J.y_sub[((p0 + pl) * C + c) * A + a] = acc;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 }  // namespace hx
@@ -378,7 +444,8 @@ struct hx_history {
   int tpb = 64;
   size_t lds = 0;
   float ms = 0.f, expm_ms = 0.f;                      // of the last evaluation: all its kernels; k_branch_expm alone
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
+  float handoff_ms[3] = {0.f, 0.f, 0.f};             // of the last hx_history_branch_batch_create: profiles, insertion scores, preMultiply
+  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr;
   // excluded-neighbour queries: the positions of every node (host, from the tokens at create), their block offsets on the
   // device from the first query on, the query's plan and its output (both grow to the largest query so far)
   std::vector<long long> row_len, block_off;
@@ -388,6 +455,7 @@ struct hx_history {
     if (ev_a) (void)hipEventDestroy(ev_a);
     if (ev_b) (void)hipEventDestroy(ev_b);
     if (ev_c) (void)hipEventDestroy(ev_c);
+    if (ev_d) (void)hipEventDestroy(ev_d);
   }
 };
 
@@ -578,7 +646,8 @@ int history_create(const char* fn, const hx_history_model* hm, const int8_t* tok
     return sp_fail(HX_ERR_HIP, fn, "copy failed");
   if (rate)
     if (int rc = history_put_rates(h, fn, rate, max_abs, expm)) return rc;
-  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess || hipEventCreate(&h->ev_c) != hipSuccess)
+  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess || hipEventCreate(&h->ev_c) != hipSuccess ||
+      hipEventCreate(&h->ev_d) != hipSuccess)
     return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
   // the full evaluation: the proposal that changes and walks every node, accepted
   std::vector<int> all(N);
@@ -611,6 +680,87 @@ int history_propose(const char* fn, hx_history* h, const int n_changed, const in
   h->changed.swap(changed);
   h->walked.swap(walked);
   h->pending = true;
+  return HX_OK;
+}
+
+// The kernels of an excluded-neighbour query on `st`, not waited for: the plan to the device (with `extra`, which the
+// caller's further kernels read at *d_extra), k_history_excluded and, if asked for, the normalisation.  The pairs' blocks
+// lie at out_base + plan.out_off (doubles); out_base null: in the history's own buffer, grown to plan.total.  ev_a is recorded
+// in front.  Nothing of the history's state is written.
+int history_excluded_launch(hx_history* h, const char* fn, const int which, const int n_pairs, const ExcludedPlan& plan, const int normalize, double* out_base,
+                            const void* extra, const size_t extra_bytes, const void** d_extra, const SpPlan& col_plan, const double* lse_tab, hipStream_t st) {
+  const int N = h->N, C = h->C, A = h->A;
+  // the slots of the state asked for: the pending proposal's messages of the walked nodes and matrices of the changed ones
+  // lie in the other slot (history_run's info words)
+  std::vector<int> info(N);
+  for (int r = 0; r < N; ++r) info[r] = h->eslot[r] | (h->mslot[r] << 1);
+  if (which == 1) {
+    for (int r : h->walked) info[r] ^= 1;
+    for (int r : h->changed) info[r] ^= 2;
+  }
+  // one block: the offsets and lengths (8-byte words first), the info words, the pairs, the paths
+  const size_t n_ll = 2 * (size_t)n_pairs, n_int = info.size() + plan.pair.size() + plan.path.size();
+  std::vector<long long> block(n_ll + (n_int + 1) / 2);
+  std::copy(plan.out_off.begin(), plan.out_off.end(), block.begin());
+  std::copy(plan.out_len.begin(), plan.out_len.end(), block.begin() + n_pairs);
+  int* words = reinterpret_cast<int*>(block.data() + n_ll);
+  std::copy(info.begin(), info.end(), words);
+  std::copy(plan.pair.begin(), plan.pair.end(), words + N);
+  std::copy(plan.path.begin(), plan.path.end(), words + N + plan.pair.size());
+  const size_t extra_at = block.size() * sizeof(long long);
+  block.resize(block.size() + (extra_bytes + 7) / 8);
+  if (extra_bytes) memcpy(reinterpret_cast<char*>(block.data()) + extra_at, extra, extra_bytes);
+  const size_t bytes = block.size() * sizeof(long long);
+  if (bytes > h->query_bytes) {
+    if (h->query.p) (void)hipFree(h->query.p);
+    h->query.p = nullptr;
+    h->query_bytes = 0;
+    if (hipMalloc(&h->query.p, bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    h->query_bytes = bytes;
+  }
+  if (!out_base && (size_t)plan.total > h->xout_doubles) {
+    if (h->xout.p) (void)hipFree(h->xout.p);
+    h->xout.p = nullptr;
+    h->xout_doubles = 0;
+    if (hipMalloc(&h->xout.p, (size_t)plan.total * sizeof(double)) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    h->xout_doubles = (size_t)plan.total;
+  }
+  if (!h->d_block_off.p) {
+    const size_t off_bytes = h->block_off.size() * sizeof(long long);
+    if (hipMalloc(&h->d_block_off.p, off_bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    if (hipMemcpy(h->d_block_off.p, h->block_off.data(), off_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(h->d_block_off.p);
+      h->d_block_off.p = nullptr;
+      return sp_fail(HX_ERR_HIP, fn, "copy failed");
+    }
+  }
+  if (hipMemcpy(h->query.p, block.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  const long long* d_ll = static_cast<const long long*>(h->query.p);
+  if (d_extra) *d_extra = static_cast<const char*>(h->query.p) + extra_at;
+  const int* d_words = reinterpret_cast<const int*>(d_ll + n_ll);
+  HxArgs a;
+  a.A = A; a.C = C; a.N = N; a.n_pairs = n_pairs;
+  a.n_cols = h->n_cols; a.ncp = h->ncp; a.n_blocks = h->ncp / 64; a.e_slot = h->e_slot; a.lg_slot = h->lg_slot;
+  a.tok = static_cast<const signed char*>(h->tok.p);
+  a.root = h->d_root; a.child = h->d_child;
+  a.info = d_words; a.pair = d_words + N; a.path = d_words + N + plan.pair.size();
+  a.out_off = d_ll; a.block_off = static_cast<const long long*>(h->d_block_off.p);
+  a.ins_prob = h->d_ins; a.log_cpt_weight = h->d_lcw;
+  a.mats = static_cast<const double*>(h->mats.p);
+  a.E = static_cast<const double*>(h->E.p); a.logE = static_cast<const double*>(h->logE.p);
+  a.out = out_base ? out_base : static_cast<double*>(h->xout.p);
+  const long long blocks64 = h->ncp / 64;
+  const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
+  const unsigned tpb = 64 * (unsigned)col_plan.waves;
+  (void)hipEventRecord(h->ev_a, st);
+  if (A == 4) hipLaunchKernelGGL(k_history_excluded<4>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
+  else if (A == 20) hipLaunchKernelGGL(k_history_excluded<20>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
+  else hipLaunchKernelGGL(k_history_excluded<0>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
+  if (normalize) {
+    const long long nb = (plan.max_len + 255) / 256;
+    hipLaunchKernelGGL(k_history_excluded_norm, dim3((unsigned)(nb > 65535 ? 65535 : nb), (unsigned)(n_pairs > 65535 ? 65535 : n_pairs)), dim3(256), 0, st, d_ll,
+                       d_ll + n_pairs, n_pairs, C * A, a.out, lse_tab);
+  }
   return HX_OK;
 }
 
@@ -721,7 +871,7 @@ int hx_history_excluded_profiles(hx_history* h, int32_t which, int32_t n_pairs, 
                                  void* stream) {
   const char* fn = "hx_history_excluded_profiles";
   if (!h || !node || !exclude || !out || n_pairs <= 0 || (which != 0 && which != 1)) return sp_fail(HX_ERR_INVALID_ARG, fn, "null argument, no pairs, or `which` not 0 or 1");
-  const int N = h->N, C = h->C, A = h->A;
+  const int C = h->C, A = h->A;
   ExcludedPlan plan;
   switch (history_excluded_plan(h->parent, h->row_len, (long long)C * A, n_pairs, node, exclude, plan)) {
     case 1: return sp_fail(HX_ERR_RANGE, fn, "a node or neighbour outside 0 .. N - 1");
@@ -739,82 +889,103 @@ int hx_history_excluded_profiles(hx_history* h, int32_t which, int32_t n_pairs, 
     h->ms = h->expm_ms = 0.f;
     return HX_OK;
   }
-  // the slots of the state asked for: the pending proposal's messages of the walked nodes and matrices of the changed ones
-  // lie in the other slot (history_run's info words)
-  std::vector<int> info(N);
-  for (int r = 0; r < N; ++r) info[r] = h->eslot[r] | (h->mslot[r] << 1);
-  if (which == 1) {
-    for (int r : h->walked) info[r] ^= 1;
-    for (int r : h->changed) info[r] ^= 2;
-  }
-  // one block: the offsets and lengths (8-byte words first), the info words, the pairs, the paths
-  const size_t n_ll = 2 * (size_t)n_pairs, n_int = info.size() + plan.pair.size() + plan.path.size();
-  std::vector<long long> block(n_ll + (n_int + 1) / 2);
-  std::copy(plan.out_off.begin(), plan.out_off.end(), block.begin());
-  std::copy(plan.out_len.begin(), plan.out_len.end(), block.begin() + n_pairs);
-  int* words = reinterpret_cast<int*>(block.data() + n_ll);
-  std::copy(info.begin(), info.end(), words);
-  std::copy(plan.pair.begin(), plan.pair.end(), words + N);
-  std::copy(plan.path.begin(), plan.path.end(), words + N + plan.pair.size());
-  const size_t bytes = block.size() * sizeof(long long);
-  if (bytes > h->query_bytes) {
-    if (h->query.p) (void)hipFree(h->query.p);
-    h->query.p = nullptr;
-    h->query_bytes = 0;
-    if (hipMalloc(&h->query.p, bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-    h->query_bytes = bytes;
-  }
-  if ((size_t)plan.total > h->xout_doubles) {
-    if (h->xout.p) (void)hipFree(h->xout.p);
-    h->xout.p = nullptr;
-    h->xout_doubles = 0;
-    if (hipMalloc(&h->xout.p, (size_t)plan.total * sizeof(double)) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-    h->xout_doubles = (size_t)plan.total;
-  }
-  if (!h->d_block_off.p) {
-    const size_t off_bytes = h->block_off.size() * sizeof(long long);
-    if (hipMalloc(&h->d_block_off.p, off_bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-    if (hipMemcpy(h->d_block_off.p, h->block_off.data(), off_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(h->d_block_off.p);
-      h->d_block_off.p = nullptr;
-      return sp_fail(HX_ERR_HIP, fn, "copy failed");
-    }
-  }
-  if (hipMemcpy(h->query.p, block.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
-  const long long* d_ll = static_cast<const long long*>(h->query.p);
-  const int* d_words = reinterpret_cast<const int*>(d_ll + n_ll);
-  HxArgs a;
-  a.A = A; a.C = C; a.N = N; a.n_pairs = n_pairs;
-  a.n_cols = h->n_cols; a.ncp = h->ncp; a.n_blocks = h->ncp / 64; a.e_slot = h->e_slot; a.lg_slot = h->lg_slot;
-  a.tok = static_cast<const signed char*>(h->tok.p);
-  a.root = h->d_root; a.child = h->d_child;
-  a.info = d_words; a.pair = d_words + N; a.path = d_words + N + plan.pair.size();
-  a.out_off = d_ll; a.block_off = static_cast<const long long*>(h->d_block_off.p);
-  a.ins_prob = h->d_ins; a.log_cpt_weight = h->d_lcw;
-  a.mats = static_cast<const double*>(h->mats.p);
-  a.E = static_cast<const double*>(h->E.p); a.logE = static_cast<const double*>(h->logE.p);
-  a.out = static_cast<double*>(h->xout.p);
+  const int rc = history_excluded_launch(h, fn, which, n_pairs, plan, normalize, nullptr, nullptr, 0, nullptr, col_plan, lse_tab, static_cast<hipStream_t>(stream));
+  if (rc != HX_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const long long blocks64 = h->ncp / 64;
-  const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
-  const unsigned tpb = 64 * (unsigned)col_plan.waves;
-  (void)hipEventRecord(h->ev_a, st);
-  if (A == 4) hipLaunchKernelGGL(k_history_excluded<4>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
-  else if (A == 20) hipLaunchKernelGGL(k_history_excluded<20>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
-  else hipLaunchKernelGGL(k_history_excluded<0>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
-  if (normalize) {
-    const long long nb = (plan.max_len + 255) / 256;
-    hipLaunchKernelGGL(k_history_excluded_norm, dim3((unsigned)(nb > 65535 ? 65535 : nb), (unsigned)(n_pairs > 65535 ? 65535 : n_pairs)), dim3(256), 0, st, d_ll,
-                       d_ll + n_pairs, n_pairs, C * A, a.out, lse_tab);
-  }
+  const double* xout = static_cast<const double*>(h->xout.p);
   (void)hipEventRecord(h->ev_b, st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
   (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
   h->expm_ms = 0.f;
   for (int k = 0; k < n_pairs; ++k)
     if (plan.out_len[k] > 0 &&
-        hipMemcpy(out[k], a.out + plan.out_off[k], (size_t)plan.out_len[k] * C * A * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(out[k], xout + plan.out_off[k], (size_t)plan.out_len[k] * C * A * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  return HX_OK;
+}
+
+int hx_history_branch_batch_create(hx_history* h, int32_t which, int32_t normalize, const hx_history_branch* branches, int32_t n_branches, void* stream,
+                                   hx_branch_batch** out) {
+  const char* fn = "hx_history_branch_batch_create";
+  if (out) *out = nullptr;
+  if (!h || !branches || !out || n_branches <= 0 || (which != 0 && which != 1))
+    return sp_fail(HX_ERR_INVALID_ARG, fn, "null argument, no branches, or `which` not 0 or 1");
+  const int C = h->C, A = h->A;
+  BranchHandoffPlan bp;
+  switch (history_branch_plan(h->parent, h->row_len, A, C, branches, n_branches, branch_max_x_len(), bp)) {
+    case 1: return sp_fail(HX_ERR_RANGE, fn, "a node outside 0 .. N - 2 (the root has no branch)");
+    case 2: return sp_fail(HX_ERR_INVALID_ARG, fn, "a null log_sub or log_ins, or a band without both envelopes");
+    case 3: return sp_fail(HX_ERR_RANGE, fn, "a parent row of more than 65535 positions");
+    default: break;
+  }
+  if (which == 1 && !h->pending) return sp_fail(HX_ERR_STATE, fn, "no proposal is pending");
+  const double* lse_tab = device_lse_table(h->device);
+  if (!lse_tab) return api_fail(HX_ERR_NOT_INITIALIZED, "hx_history: hx_init has not been called for the history's device");
+  const SpPlan col_plan = sp_column_plan(A, C, 1, true);
+  // k_history_pre_multiply's tile: 64 positions, 32 of a large alphabet (48 KB of LDS at A = 64)
+  const int P = A > 32 ? 32 : 64;
+  const size_t pm_lds = sizeof(double) * (size_t)A * (A + P);
+  if (col_plan.lds > HX_LDS_LIMIT || pm_lds > HX_LDS_LIMIT) return sp_fail(HX_ERR_INVALID_ARG, fn, "the LDS plan exceeds the LDS of a CU");
+  ExcludedPlan plan;
+  const int n_pairs = 2 * n_branches;
+  if (history_excluded_plan(h->parent, h->row_len, (long long)C * A, n_pairs, bp.node.data(), bp.exclude.data(), plan) != 0)
+    return sp_fail(HX_ERR_INVALID_ARG, fn, "the branches do not make a plan");
+  if (hipSetDevice(h->device) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "hipSetDevice failed");
+  // the batch: the small inputs and the caller's logs through the host image, room for what the kernels write
+  std::vector<const double*> log_sub(n_branches), log_ins(n_branches);
+  for (int k = 0; k < n_branches; ++k) { log_sub[k] = branches[k].log_sub; log_ins[k] = branches[k].log_ins; }
+  std::vector<BranchInputs> where(n_branches);
+  hx_branch_batch* b = nullptr;
+  if (const int rc = branch_batch_reserve(bp.jobs.data(), log_sub.data(), log_ins.data(), n_branches, &b, where.data())) return rc;
+  struct Guard { hx_branch_batch* b; ~Guard() { if (b) (void)hx_branch_batch_destroy(b); } } guard{b};
+  // the profiles go straight to x_pwm and y_sub: the pairs' blocks as offsets from the first job's x_pwm
+  double* base = where[0].x_pwm;
+  std::vector<HbJob> jobs(n_branches);
+  long long max_y = 0;
+  for (int k = 0; k < n_branches; ++k) {
+    plan.out_off[2 * k] = where[k].x_pwm - base;
+    plan.out_off[2 * k + 1] = where[k].y_sub - base;
+    jobs[k] = HbJob{where[k].log_sub, where[k].log_ins, where[k].y_sub, where[k].y_emit, plan.out_len[2 * k + 1]};
+    max_y = std::max(max_y, jobs[k].y_len);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  h->handoff_ms[0] = h->handoff_ms[1] = h->handoff_ms[2] = 0.f;
+  if (plan.total == 0) {                             // (no row has a position: nothing to compute)
+    h->ms = h->expm_ms = 0.f;
+    guard.b = nullptr;
+    *out = b;
+    return HX_OK;
+  }
+  const void* d_jobs_v = nullptr;
+  if (const int rc = history_excluded_launch(h, fn, which, n_pairs, plan, normalize, base, jobs.data(), sizeof(HbJob) * jobs.size(), &d_jobs_v, col_plan, lse_tab, st))
+    return rc;
+  const HbJob* d_jobs = static_cast<const HbJob*>(d_jobs_v);
+  (void)hipEventRecord(h->ev_c, st);
+  if (max_y > 0) {
+    const unsigned gz = (unsigned)(n_branches > 65535 ? 65535 : n_branches);
+    const long long nb = (max_y + 255) / 256, tiles = (max_y + P - 1) / P;
+    hipLaunchKernelGGL(k_history_ins_probs, dim3((unsigned)(nb > 65535 ? 65535 : nb), gz), dim3(256), 0, st, d_jobs, n_branches, C, A, h->d_lcw, lse_tab);
+    (void)hipEventRecord(h->ev_d, st);
+    hipLaunchKernelGGL(k_history_pre_multiply, dim3((unsigned)(tiles > 65535 ? 65535 : tiles), (unsigned)C, gz), dim3(256), pm_lds, st, d_jobs, n_branches, C, A, P,
+                       lse_tab);
+  } else {
+    (void)hipEventRecord(h->ev_d, st);
+  }
+  (void)hipEventRecord(h->ev_b, st);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
+  (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
+  (void)hipEventElapsedTime(&h->handoff_ms[0], h->ev_a, h->ev_c);
+  (void)hipEventElapsedTime(&h->handoff_ms[1], h->ev_c, h->ev_d);
+  (void)hipEventElapsedTime(&h->handoff_ms[2], h->ev_d, h->ev_b);
+  h->expm_ms = 0.f;
+  guard.b = nullptr;
+  *out = b;
+  return HX_OK;
+}
+
+int hx_history_last_handoff_ms(hx_history* h, float* ms) {
+  if (!h || !ms) return api_fail(HX_ERR_INVALID_ARG, "hx_history_last_handoff_ms: null argument");
+  for (int k = 0; k < 3; ++k) ms[k] = h->handoff_ms[k];
   return HX_OK;
 }
 

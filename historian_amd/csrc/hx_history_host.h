@@ -3,7 +3,9 @@
 // validation of the lengths, the closure of the changed nodes over their ancestors, the launch plan of k_branch_expm.
 #pragma once
 #include <cmath>
+#include <cstdint>
 #include <vector>
+#include "../../include/historian_hip.h"
 
 namespace hx {
 
@@ -139,6 +141,45 @@ inline int history_excluded_plan(const std::vector<int>& parent, const std::vect
     plan.out_len.push_back(len[r]);
     plan.total += len[r] * row;
     if (len[r] > plan.max_len) plan.max_len = len[r];
+  }
+  return 0;
+}
+
+// ---- the hand-off to the branch DP (hx_history_branch_batch_create): the host's share ----
+
+// The query's pairs - (parent, node) then (node, parent) per branch: x_pwm and the child's profile - and the jobs of the
+// batch with their lengths, transition scores and envelopes; the per-position arrays stay null, the device fills them.
+struct BranchHandoffPlan {
+  std::vector<int> node, exclude;
+  std::vector<hx_branch_job> jobs;
+};
+// 0: fine; 1: a node outside 0 .. N - 2; 2: a null log_sub or log_ins, or a band without both envelopes; 3: a parent row of
+// max_x_len positions or more (or a child row beyond 32 bits).  parent, len: as history_excluded_plan.
+inline int history_branch_plan(const std::vector<int>& parent, const std::vector<long long>& len, const int A, const int C, const hx_history_branch* br,
+                               const int n_branches, const long long max_x_len, BranchHandoffPlan& plan) {
+  const int N = (int)parent.size();
+  plan = BranchHandoffPlan();
+  for (int k = 0; k < n_branches; ++k)
+    if (br[k].node < 0 || br[k].node >= N - 1) return 1;
+  for (int k = 0; k < n_branches; ++k)
+    if (!br[k].log_sub || !br[k].log_ins || (br[k].max_distance >= 0 && (!br[k].x_env || !br[k].y_env))) return 2;
+  for (int k = 0; k < n_branches; ++k)
+    if (len[parent[br[k].node]] >= max_x_len || len[br[k].node] > 0x7ffffffe) return 3;
+  for (int k = 0; k < n_branches; ++k) {
+    const int r = br[k].node, p = parent[r];
+    plan.node.push_back(p); plan.exclude.push_back(r);
+    plan.node.push_back(r); plan.exclude.push_back(p);
+    hx_branch_job j = {};
+    j.x_len = (int32_t)len[p];
+    j.y_len = (int32_t)len[r];
+    j.components = C;
+    j.alphabet = A;
+    for (int s = 0; s < 3; ++s)
+      for (int d = 0; d < 4; ++d) j.trans[s][d] = br[k].trans[s][d];
+    j.x_env = br[k].x_env;
+    j.y_env = br[k].y_env;
+    j.max_distance = br[k].max_distance;
+    plan.jobs.push_back(j);
   }
   return 0;
 }

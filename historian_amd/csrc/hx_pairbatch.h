@@ -75,10 +75,17 @@ int api_fail(int code, const char* what);                  // hx_api.hip: sets h
 const double* device_lse_table(int device);               // hx_api.hip: the table hx_init uploaded, or nullptr
 
 // ---- the batch ---------------------------------------------------------------------------------------------------------------
-// The host image of a batch's inputs.  A job's pointers into it are set once the device copy has an address.
+// The host image of a batch's inputs.  A job's pointers into it are set once the device copy has an address.  Behind the
+// image (and lpEnd) the device arena holds what was reserved: arrays with no host copy, which kernels fill on the device.
 struct PairArena {
   std::vector<char> host;
   std::vector<std::pair<void*, size_t>> fix;      // (a pointer member of a job, offset of what it shall point to)
+  std::vector<std::pair<void*, size_t>> fix_reserved;      // (..., offset within the reserved part)
+  size_t reserved = 0;                            // bytes
+  template <class T> void reserve(const T*& member, size_t n) {
+    fix_reserved.emplace_back(&member, reserved);
+    reserved += (sizeof(T) * n + 15) & ~(size_t)15;
+  }
   size_t put(const void* p, size_t bytes) {
     const size_t off = (host.size() + 15) & ~(size_t)15;
     host.resize(off + bytes);
@@ -161,12 +168,17 @@ struct PairBatch {
     } catch (const std::bad_alloc&) {
       return api_fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed while building the batch");
     }
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_arena), a.host.size()) != hipSuccess ||
+    const size_t reserved_at = (a.host.size() + 15) & ~(size_t)15;
+    if (hipMalloc(reinterpret_cast<void**>(&b->d_arena), reserved_at + a.reserved) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&b->d_cells), sizeof(double) * (size_t)cells_total) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&b->d_jobs), sizeof(Job) * n_jobs) != hipSuccess)
       return fail(HX_ERR_OUT_OF_MEMORY, "_create: device allocation failed");
     for (const auto& f : a.fix) {
       const char* p = b->d_arena + f.second;
+      memcpy(f.first, &p, sizeof(p));
+    }
+    for (const auto& f : a.fix_reserved) {
+      const char* p = b->d_arena + reserved_at + f.second;
       memcpy(f.first, &p, sizeof(p));
     }
     int64_t at = 0;

@@ -24,7 +24,8 @@
  *     batch created with HX_KEEP_BACKWARD, hx_quick_batch_run, hx_branch_batch_run, hx_sibling_batch_run.
  *     hx_batch_backward without HX_KEEP_BACKWARD first waits for the batch's last stream (it allocates the Backward
  *     matrices), then queues; hx_sumprod_columns, hx_sumprod_ancestors, hx_distance_matrix, hx_distance_neg_log_like, hx_history_create,
- *     hx_history_create_from_lengths, hx_history_propose, hx_history_propose_lengths and hx_history_excluded_profiles run their kernels on `stream` and return when they are done.
+ *     hx_history_create_from_lengths, hx_history_propose, hx_history_propose_lengths, hx_history_excluded_profiles and
+ *     hx_history_branch_batch_create run their kernels on `stream` and return when they are done.
  *   - hx_batch_backward may be given another stream than the hx_batch_forward before it: the library orders it behind that
  *     Forward launch (an event), with no host synchronisation.
  *   - Readers (results, matrices, cells, tracebacks, walks, counts) synchronise with the batch's LAST stream only - the stream
@@ -597,6 +598,9 @@ int hx_branch_batch_results(hx_branch_batch* b, double* lp_end /* [n_jobs] */);
 /* dense [x_len + 1][y_len + 1][3] (Match, Insert, Delete); -inf outside the envelope, as SparseDPMatrix::cell() returns */
 int hx_branch_batch_read_matrix(hx_branch_batch* b, int32_t job, double* out);
 int64_t hx_branch_batch_total_cells(const hx_branch_batch* b);
+/* x_pwm [x_len][C][A], y_sub [y_len][C][A], y_emit [y_len] of one job of ANY branch batch, as the fill reads them;
+   each may be NULL */
+int hx_branch_batch_read_inputs(hx_branch_batch* b, int32_t job, double* x_pwm, double* y_sub, double* y_emit);
 int hx_branch_batch_last_kernel_ms(hx_branch_batch* b, float* ms);
 
 /* ---- row N4: a filled pair matrix consumed where it lies ------------------------------------------------------------------
@@ -637,6 +641,39 @@ typedef struct hx_pair_cell {
   int32_t xpos, ypos, state;
 } hx_pair_cell;
 int hx_branch_batch_read_cells(hx_branch_batch* b, int32_t job, int64_t n, const hx_pair_cell* at, double* cells, double* log_match);
+
+/* A branch batch (hx_branch_batch, above) made from a live history with every per-position input computed on the device
+ * and left there: no profile passes through host memory.  Job k holds x_pwm = the profile of parent(node) with node
+ * excluded, y_sub = TreeAlignFuncs::preMultiply (reference src/sampler.cpp:452-463) of the profile of node with its parent
+ * excluded, y_emit = calcInsProbs (:465-476) of that same child profile, x_len and y_len from hx_history_row_lengths.  The
+ * caller brings the logs, taken with the host's libm; the device adds and folds the table log_sum_exp of hx_init in the
+ * reference's order (b ascending from -inf; component major, residue minor from -inf, (log_cpt_weight[c] + log_ins[c][a]) +
+ * child), the component weights being the history's own: the inputs have the bits of preMultiply and calcInsProbs run on
+ * the profiles hx_history_excluded_profiles returns.  No atomics: two calls give the same bytes.
+ * which, normalize: as hx_history_excluded_profiles.  Runs on `stream`, returns when done; hx_history_last_kernel_ms then
+ * reports the query's kernels, hx_history_last_handoff_ms their split.  The batch owns its inputs: it stays valid after
+ * the history is proposed on, accepted, rejected or destroyed, and everything of hx_branch_batch_* works on it.  Nothing
+ * is written to the history.  A node or parent without positions is legal (a job with that length 0).
+ * Refused before anything is launched or allocated, the history unchanged and *out NULL: HX_ERR_RANGE (a node outside
+ * 0 .. N - 2; a parent row of 65536 positions or more), HX_ERR_INVALID_ARG (a null pointer, n_branches <= 0, max_distance
+ * >= 0 without both envelopes, `which` not 0 or 1), HX_ERR_STATE (which = 1 without a pending proposal),
+ * HX_ERR_NOT_INITIALIZED (no hx_init for the history's device). */
+typedef struct hx_history_branch {
+  int32_t node;              /* the child; the branch to its parent.  0 .. N - 2                                    */
+  const double* log_sub;     /* [C][A][A] log of the branch's exp(R t), row = parent residue (what the mirror's
+                                logOf(probModel.subMat) passes to preMultiply); -inf entries are legal               */
+  const double* log_ins;     /* [C][A] LogProbModel::logInsProb                                                      */
+  double trans[3][4];        /* as hx_branch_job::trans                                                              */
+  const int32_t* x_env;      /* [len(parent) + 1], [len(node) + 1], max_distance: as hx_branch_job                   */
+  const int32_t* y_env;
+  int32_t max_distance;
+} hx_history_branch;
+int hx_history_branch_batch_create(hx_history* h, int32_t which, int32_t normalize,
+                                   const hx_history_branch* branches, int32_t n_branches,
+                                   void* stream, hx_branch_batch** out);
+/* A measurement aid (tools/branch_handoff_bench.py): ms[3] = the profile kernels, the insertion scores and preMultiply
+ * of the most recent hx_history_branch_batch_create on this history (their sum is hx_history_last_kernel_ms). */
+int hx_history_last_handoff_ms(hx_history* h, float* ms);
 
 /* ---- row N4, second lattice: the sibling-pair parent-proposal DP ---------------------------------------------------------
  * Sampler::SiblingMatrix (reference src/sampler.h:226-325, src/sampler.cpp:1185-1342): a left child profile and a right
