@@ -128,7 +128,7 @@ EXPORTS = ["hx_init", "hx_shutdown", "hx_last_error", "hx_version", "hx_batch_cr
            "hx_history_log_like", "hx_history_indel_counts", "hx_history_last_kernel_ms", "hx_history_set_rates",
            "hx_history_propose_lengths", "hx_history_create_from_lengths", "hx_history_branch_matrix", "hx_expm_shape",
            "hx_history_last_expm_ms", "hx_history_row_lengths", "hx_history_excluded_profiles",
-           "hx_history_branch_batch_create", "hx_history_last_handoff_ms", "hx_branch_batch_read_inputs"]
+           "hx_history_branch_batch_create", "hx_history_last_handoff_ms", "hx_branch_batch_read_inputs", "hx_live_allocations"]
 
 
 class HxError(RuntimeError):
@@ -245,6 +245,8 @@ def load():
     lib.hx_batch_wait_read.argtypes = [vp, C.c_int32, C.c_int32]
     lib.hx_batch_indel_counts.argtypes = [vp, C.c_int32, _f64p, _f64p]
     lib.hx_batch_event_counts.argtypes = [vp, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]
+    if hasattr(lib, "hx_live_allocations"):          # (absent from an older library selected with HX_LIB_PATH)
+        lib.hx_live_allocations.argtypes, lib.hx_live_allocations.restype = [], C.c_int64
     _lib = lib
     return lib
 
@@ -347,6 +349,11 @@ def init(device=0, table=None):
 
 def shutdown():
     _check(load().hx_shutdown())
+
+
+def live_allocations():
+    """Device and page-locked allocations the library holds now (hx_live_allocations)."""
+    return int(load().hx_live_allocations())
 
 
 def slot_index(layout, i, j):

@@ -220,29 +220,29 @@ int hx_sumprod_ancestors(const hx_sumprod_model* hm, const int8_t* tokens, int64
   if (plan.lds > HX_LDS_LIMIT || row_lds > HX_LDS_LIMIT) return sp_fail(HX_ERR_INVALID_ARG, fn, "the LDS plan exceeds the LDS of a CU");
   hipStream_t st = static_cast<hipStream_t>(stream);
   SpUpload up;
-  SpBuf b_tok, b_scr, b_out, b_best;
-  if (!up.alloc(sp_tree_room(A, C, N, true)) || hipMalloc(&b_tok.p, (size_t)n_cols * N) != hipSuccess || hipMalloc(&b_best.p, (size_t)n_cols * N) != hipSuccess)
+  DevBuf b_tok, b_scr, b_out, b_best;
+  if (!up.alloc(sp_tree_room(A, C, N, true)) || !b_tok.alloc((size_t)n_cols * N) || !b_best.alloc((size_t)n_cols * N))
     return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
   const SpTree tr = sp_put_tree(up, A, C, N, hm->parent, child, hm->ins_prob, hm->log_cpt_weight, hm->branch_sub);
   AnModel m;
   m.A = A; m.C = C; m.N = N; m.parent = tr.parent; m.child = tr.child;
   m.ins_prob = tr.ins_prob; m.log_cpt_weight = tr.log_cpt_weight; m.branch_sub = tr.branch_sub;
-  if (!up.copied || hipMemcpy(b_tok.p, tokens, (size_t)n_cols * N, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  if (!up.copied || hipMemcpy(b_tok.as<void>(), tokens, (size_t)n_cols * N, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
   const int AP = (A + 1) & ~1;                     // message vectors are stored in pairs of entries
   const size_t per_col = 3 * (size_t)C * N * AP + 3 * (size_t)C * N;
   const long long chunk = sp_chunk(per_col, n_cols);
   const size_t n_out = (size_t)n_cols * (1 + (node_post ? (size_t)N * A : 0));
-  if (hipMalloc(&b_scr.p, per_col * (((size_t)chunk + 63) & ~(size_t)63) * sizeof(double)) != hipSuccess || hipMalloc(&b_out.p, n_out * sizeof(double)) != hipSuccess)
+  if (!b_scr.alloc(per_col * (((size_t)chunk + 63) & ~(size_t)63) * sizeof(double)) || !b_out.alloc(n_out * sizeof(double)))
     return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-  double* d_cll = static_cast<double*>(b_out.p);
+  double* d_cll = b_out.as<double>();
   double* d_post = node_post ? d_cll + n_cols : nullptr;
-  signed char* d_best = static_cast<signed char*>(b_best.p);
-  SpEvents ev;
+  signed char* d_best = b_best.as<signed char>();
+  DevEvents<2> ev;
   if (!ev.create()) return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
-  (void)hipEventRecord(ev.a, st);
+  (void)hipEventRecord(ev[0], st);
   for (long long first = 0; first < n_cols; first += chunk) {
     const long long nc = n_cols - first < chunk ? n_cols - first : chunk;
-    double* scr = static_cast<double*>(b_scr.p);
+    double* scr = b_scr.as<double>();
     const size_t nc64 = ((size_t)nc + 63) & ~(size_t)63;         // the scratch holds whole blocks of 64 columns
     const size_t msg = (size_t)C * N * AP * nc64, lg = (size_t)C * N * nc64;
     AnScratch s;
@@ -250,7 +250,7 @@ int hx_sumprod_ancestors(const hx_sumprod_model* hm, const int8_t* tokens, int64
     s.logE = scr + 3 * msg; s.logF = s.logE + lg; s.logG = s.logF + lg;
     const long long blocks64 = (nc + 63) / 64;
     const long long blocks = blocks64 > 65535 ? 65535 : blocks64;
-    const signed char* d_tok = static_cast<const signed char*>(b_tok.p) + first * N;
+    const signed char* d_tok = b_tok.as<const signed char>() + first * N;
 #define HX_AN_GO(TA_, LM_) hipLaunchKernelGGL((k_ancestor_columns<TA_, LM_>), dim3((unsigned)blocks), dim3(64 * plan.waves), plan.lds, st, m, d_tok, nc, s, lse_tab, d_cll + first)
     // (eight waves' matrices of A = 4 or 20 and 128 components' likelihoods fit the LDS plan: the fixed-size forms always have them)
     if (A == 4 && plan.lm) HX_AN_GO(4, true);
@@ -265,10 +265,10 @@ int hx_sumprod_ancestors(const hx_sumprod_model* hm, const int8_t* tokens, int64
     else
       hipLaunchKernelGGL(k_ancestor_combine<false>, dim3(cgrid), dim3(64 * cwaves), 0, st, m, d_tok, nc, s.T, lse_tab, d_best + first * N, (double*)nullptr);
   }
-  (void)hipEventRecord(ev.b, st);
+  (void)hipEventRecord(ev[1], st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
-  (void)hipEventElapsedTime(&g_sp_ms, ev.a, ev.b);
+  (void)hipEventElapsedTime(&g_sp_ms, ev[0], ev[1]);
   if (hipMemcpy(best, d_best, (size_t)n_cols * N, hipMemcpyDeviceToHost) != hipSuccess ||
       (col_log_like && hipMemcpy(col_log_like, d_cll, (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
       (node_post && hipMemcpy(node_post, d_post, (size_t)n_cols * N * A * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))

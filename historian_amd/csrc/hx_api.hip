@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <string>
 #include <unordered_map>
@@ -18,7 +19,9 @@
 #include <vector>
 
 #include "../../include/historian_hip.h"
+#include "hx_arena.h"
 #include "hx_device.h"
+#include "hx_devmem.h"
 #include "hx_kernels.h"
 
 using namespace hx;
@@ -40,10 +43,12 @@ thread_local char g_err[512] = "";
 // from one host thread or from one thread per device.
 #define HX_MAX_DEVICES 16
 struct DeviceTables {
-  double* tab = nullptr;      // device copy of the host-built log_sum_exp table (8-byte entries)
-  double* fast_tab = nullptr; // quadratic pieces of the fast fill mode (FastPiece, 16 bytes each)
-  double* log_tab = nullptr;  // {c, -log c} entries of the scaled-probability fills' logarithm (hx_linear.hip)
-  double* pair_tab = nullptr; // {lookup[n], lookup[n+1]-lookup[n]} pairs, 16-byte aligned (exact fill mode)
+  DevBuf tab;                 // device copy of the host-built log_sum_exp table (8-byte entries)
+  DevBuf fast_tab;            // quadratic pieces of the fast fill mode (FastPiece, 16 bytes each)
+  DevBuf log_tab;             // {c, -log c} entries of the scaled-probability fills' logarithm (hx_linear.hip)
+  DevBuf pair_tab;            // {lookup[n], lookup[n+1]-lookup[n]} pairs, 16-byte aligned (exact fill mode)
+  Tab8 tab8() const { return Tab8{tab.as<double>()}; }            // as the launchers take them
+  Tab16 log16() const { return Tab16{log_tab.as<double>()}; }
   // the stream of hx_batch_read_matrix_async, shared by the device's batches: a stream's queue is set up at its first use,
   // which costs a caller that makes a batch per fill (a reconstruction's internal nodes) a millisecond or two per matrix
   hipStream_t copy_stream = nullptr;
@@ -95,6 +100,13 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// A refused allocation, reported as HIP_TRY (below) reported the hipMalloc call it wrapped before the buffers had an owner:
+// `what` is that call's text, kept word for word because callers and tests compare messages - it names no live variable.
+int alloc_failed(const char* what) {
+  const hipError_t e = hipPeekAtLastError();
+  return fail(e == hipErrorOutOfMemory ? HX_ERR_OUT_OF_MEMORY : HX_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+}
+
 #define HIP_TRY(expr)                                                                 \
   do {                                                                                \
     hipError_t e_ = (expr);                                                           \
@@ -114,28 +126,14 @@ struct Policy {
       : fast((flags & HX_LSE_FAST) != 0), linear((flags & HX_LSE_LINEAR) == HX_LSE_LINEAR),
         trunc((flags & HX_LSE_TRUNC) == HX_LSE_TRUNC), band_mode(linear ? (trunc ? 3 : 0) : (fast ? 1 : 2)) {}
   // the table of the log-sum-exp fills: FastPiece table, or the exact mode's {f0, df} pairs
-  Tab16 lse_tab(const DeviceTables& D) const { return Tab16{fast ? D.fast_tab : D.pair_tab}; }
+  Tab16 lse_tab(const DeviceTables& D) const { return Tab16{(fast ? D.fast_tab : D.pair_tab).as<double>()}; }
   // the table of the banded rotating-row sweep's policy
-  Tab16 band_tab(const DeviceTables& D) const { return linear ? Tab16{D.log_tab} : lse_tab(D); }
+  Tab16 band_tab(const DeviceTables& D) const { return linear ? D.log16() : lse_tab(D); }
 };
 
-// Grows a host staging image of the device arena; returns byte offsets.
-struct Arena {
-  std::vector<char> host;
-  size_t put(const void* src, size_t bytes) {
-    size_t off = (host.size() + 255) & ~size_t(255);
-    host.resize(off + bytes);
-    if (src && bytes) memcpy(host.data() + off, src, bytes);
-    return off;
-  }
-  size_t reserve(size_t bytes) { return put(nullptr, bytes); }
-};
-
-// offsets into the arena for one profile
+// what the host keeps of a flattened profile: arena offsets (hx_arena.h, 256-byte pieces) of the arrays it reads again, and facts
 struct ProfOff {
-  size_t flags, in_off, in_src, in_lp, in_idx, ao_off, ao_dst, ao_lp, no_off, no_dst, no_lp;
-  size_t lp_absorb, sub, ins, rootsub, env, cls, cls_rep, pack, ecls, subc, insc, rootsubc, fpack;
-  bool has_env;
+  size_t flags, in_idx, ecls;
   int n, n_trans, empty, n_cls, chain, interior_emit, lp_zero;
 };
 
@@ -150,7 +148,7 @@ int check_csr(const int32_t* off, const int32_t* idx, int N, int T, const char* 
   return HX_OK;
 }
 
-int flatten_profile(const hx_profile* p, int CA, bool need_env, bool is_y, Arena& ar, ProfOff& o) {
+int flatten_profile(const hx_profile* p, int CA, bool need_env, bool is_y, Arena& ar, ProfOff& o, DevProfile& d) {
   if (!p) return fail(HX_ERR_INVALID_ARG, "null profile");
   const int N = p->n_states, T = p->n_trans;
   if (N < 2 || T < 0) return fail(HX_ERR_INVALID_ARG, "profile needs >= 2 states (got %d)", N);
@@ -239,42 +237,41 @@ int flatten_profile(const hx_profile* p, int CA, bool need_env, bool is_y, Arena
   o.empty = any_emit ? 0 : 1;
   o.n_cls = (int)cls_rep.size();
   o.chain = chain;
-  o.flags = ar.put(flags.data(), N);
-  o.in_off = ar.put(p->in_off, sizeof(int32_t) * (N + 1));
-  o.in_src = ar.put(in_src.data(), sizeof(int32_t) * in_src.size());
-  o.in_lp = ar.put(in_lp.data(), sizeof(double) * in_lp.size());
+  ar.point(d.flags, o.flags = ar.put(flags.data(), N));
+  ar.put(d.in_off, p->in_off, (size_t)N + 1);
+  ar.put(d.in_src, in_src.data(), in_src.size());
+  ar.put(d.in_lp, in_lp.data(), in_lp.size());
   o.in_idx = ar.put(p->in_idx, sizeof(int32_t) * in_src.size());   // in-slot -> transition index (hx_batch_event_counts)
   o.n_trans = T;
-  o.ao_off = ar.put(p->aout_off, sizeof(int32_t) * (N + 1));
-  o.ao_dst = ar.put(ao_dst.data(), sizeof(int32_t) * ao_dst.size());
-  o.ao_lp = ar.put(ao_lp.data(), sizeof(double) * ao_lp.size());
-  o.no_off = ar.put(p->nout_off, sizeof(int32_t) * (N + 1));
-  o.no_dst = ar.put(no_dst.data(), sizeof(int32_t) * no_dst.size());
-  o.no_lp = ar.put(no_lp.data(), sizeof(double) * no_lp.size());
+  ar.put(d.ao_off, p->aout_off, (size_t)N + 1);
+  ar.put(d.ao_dst, ao_dst.data(), ao_dst.size());
+  ar.put(d.ao_lp, ao_lp.data(), ao_lp.size());
+  ar.put(d.no_off, p->nout_off, (size_t)N + 1);
+  ar.put(d.no_dst, no_dst.data(), no_dst.size());
+  ar.put(d.no_lp, no_lp.data(), no_lp.size());
   {
     // null rows are never read by the reference; give them a defined value
     std::vector<double> raw((size_t)N * CA, NEG_INF);
     for (int i = 0; i < N; ++i)
       if (!p->is_null[i]) memcpy(&raw[(size_t)i * CA], p->lp_absorb + (size_t)i * CA, sizeof(double) * CA);
-    o.lp_absorb = ar.put(raw.data(), sizeof(double) * raw.size());
+    ar.put(d.lp_absorb, raw.data(), raw.size());
   }
-  o.sub = ar.reserve(sizeof(double) * (size_t)N * CA);
-  o.ins = ar.reserve(sizeof(double) * N);
-  o.rootsub = ar.reserve(sizeof(double) * N);
-  o.has_env = need_env;
-  o.env = need_env ? ar.put(p->env_pos, sizeof(int32_t) * N) : 0;
-  o.cls = ar.put(cls.data(), sizeof(int32_t) * N);
-  o.cls_rep = ar.put(cls_rep.data(), sizeof(int32_t) * cls_rep.size());
+  ar.point(d.sub, ar.reserve(sizeof(double) * (size_t)N * CA));
+  ar.point(d.ins, ar.reserve(sizeof(double) * N));
+  ar.point(d.rootsub, ar.reserve(sizeof(double) * N));
+  if (need_env) ar.put(d.env, p->env_pos, (size_t)N);             // (else it stays null)
+  ar.put(d.cls, cls.data(), (size_t)N);
+  ar.put(d.cls_rep, cls_rep.data(), cls_rep.size());
   {
     std::vector<int32_t> ecls(N);
     for (int i = 0; i < N; ++i) ecls[i] = cls[i] < 0 ? (int32_t)cls_rep.size() : cls[i];
-    o.ecls = ar.put(ecls.data(), sizeof(int32_t) * N);
+    ar.point(d.ecls, o.ecls = ar.put(ecls.data(), sizeof(int32_t) * N));
   }
-  o.pack = ar.reserve(sizeof(double) * 4 * (size_t)N);
-  o.fpack = ar.reserve(sizeof(FwdPack) * (size_t)N);
-  o.subc = ar.reserve(sizeof(double) * cls_rep.size() * (size_t)CA);
-  o.insc = ar.reserve(sizeof(double) * cls_rep.size());
-  o.rootsubc = ar.reserve(sizeof(double) * cls_rep.size());
+  ar.point(d.pack, ar.reserve(sizeof(double) * 4 * (size_t)N));
+  ar.point(d.fpack, ar.reserve(sizeof(FwdPack) * (size_t)N));
+  ar.point(d.subc, ar.reserve(sizeof(double) * cls_rep.size() * (size_t)CA));
+  ar.point(d.insc, ar.reserve(sizeof(double) * cls_rep.size()));
+  ar.point(d.rootsubc, ar.reserve(sizeof(double) * cls_rep.size()));
   o.lp_zero = 1;
   for (int t = 0; t < T; ++t)
     if (p->trans_lp[t] != 0.0) o.lp_zero = 0;
@@ -284,40 +281,9 @@ int flatten_profile(const hx_profile* p, int CA, bool need_env, bool is_y, Arena
   return HX_OK;
 }
 
-void bind_profile(DevProfile& d, const ProfOff& o, char* base) {
-  d.n = o.n;
-  d.empty = o.empty;
-  d.flags = reinterpret_cast<uint8_t*>(base + o.flags);
-  d.in_off = reinterpret_cast<int32_t*>(base + o.in_off);
-  d.in_src = reinterpret_cast<int32_t*>(base + o.in_src);
-  d.in_lp = reinterpret_cast<double*>(base + o.in_lp);
-  d.ao_off = reinterpret_cast<int32_t*>(base + o.ao_off);
-  d.ao_dst = reinterpret_cast<int32_t*>(base + o.ao_dst);
-  d.ao_lp = reinterpret_cast<double*>(base + o.ao_lp);
-  d.no_off = reinterpret_cast<int32_t*>(base + o.no_off);
-  d.no_dst = reinterpret_cast<int32_t*>(base + o.no_dst);
-  d.no_lp = reinterpret_cast<double*>(base + o.no_lp);
-  d.lp_absorb = reinterpret_cast<double*>(base + o.lp_absorb);
-  d.sub = reinterpret_cast<double*>(base + o.sub);
-  d.ins = reinterpret_cast<double*>(base + o.ins);
-  d.rootsub = reinterpret_cast<double*>(base + o.rootsub);
-  d.env = o.has_env ? reinterpret_cast<int32_t*>(base + o.env) : nullptr;
-  d.cls = reinterpret_cast<int32_t*>(base + o.cls);
-  d.cls_rep = reinterpret_cast<int32_t*>(base + o.cls_rep);
-  d.n_cls = o.n_cls;
-  d.pad_ = 0;
-  d.pack = reinterpret_cast<double*>(base + o.pack);
-  d.fpack = reinterpret_cast<FwdPack*>(base + o.fpack);
-  d.subc = reinterpret_cast<double*>(base + o.subc);
-  d.insc = reinterpret_cast<double*>(base + o.insc);
-  d.rootsubc = reinterpret_cast<double*>(base + o.rootsubc);
-  d.ecls = reinterpret_cast<int32_t*>(base + o.ecls);
-}
-
 struct JobOff {
   ProfOff x, y;
-  size_t log_root, log_sub_l, log_sub_r, log_ins_l, log_ins_r, log_cptw_l, log_cptw_r, emis, emis_pad;
-  size_t fwd_windows, bwd_windows, strip_base, yword, yword_bwd, band_rows, band_rows_bwd;
+  size_t band_rows_bwd;   // arena offset of the Backward sweep's row records, or 0: the pair has none
   bool compressed;
   bool chain, leaf_like;  // both profiles are chains; ... of leaves (choose_class)
   int64_t compact_plane;
@@ -568,13 +534,12 @@ struct hx_batch {
   std::vector<hx_layout> layouts;
   std::vector<int> order;           // class-ordered table position -> caller's job index
   ClassRange cls[KC_COUNT];
-  DevJob* d_jobs = nullptr;         // the caller's job order (readers, traceback, prep)
-  DevJob* d_jobs_cls = nullptr;     // class order (fills)
-  char* d_arena = nullptr;
-  double* d_fwd = nullptr;
-  double* d_bwd = nullptr;
-  double* d_eplane = nullptr;       // per-cell emission planes of the jobs without a class-pair table
-  double* d_agg = nullptr;          // outgoing-sum planes of the general-profile Forward pipeline (KC_DAG* jobs only)
+  DevBuf d_jobs;                    // [n_jobs] DevJob in the caller's job order (readers, traceback, prep)
+  DevBuf d_jobs_cls;                // ... in class order (fills)
+  DevBuf d_arena;                   // the inputs' image (hx_arena.h)
+  DevBuf d_fwd, d_bwd;              // doubles
+  DevBuf d_eplane;                  // per-cell emission planes of the jobs without a class-pair table
+  DevBuf d_agg;                     // outgoing-sum planes of the general-profile Forward pipeline (KC_DAG* jobs only)
   int64_t fwd_total = 0, max_eplane = 0;
   int max_states = 0, max_ca = 0, max_cls_pairs = 0, max_cls = 0;
   bool any_compressed = false;
@@ -587,16 +552,16 @@ struct hx_batch {
   int relaunches = 0;                    // fills repeated for that reason
   bool sub_scattered = false;        // subx / suby of table-emission jobs exist per state (k_scatter_sub, on demand)
   hipStream_t last_stream = nullptr;
-  hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  hipEvent_t ev_side[2] = {nullptr, nullptr};   // fork / join of the device's side stream (banded sweep's edge kernel)
+  DevEvents<2> ev[2];                           // [Forward, Backward]: in front of the fill's launches, behind them
+  DevEvents<2> ev_side;                         // fork / join of the device's side stream (banded sweep's edge kernel), made at the first fork
   bool dag_linear = false;                      // general-profile classes run the scaled-probability fill (hx_daglin.hip)
   hipStream_t copy_stream = nullptr;            // hx_batch_read_matrix_async: the device's copy stream (DeviceTables)
-  int* d_multi = nullptr;                       // progress counters of a pair dealt to several workgroups (hx_dag.hip MULTI)
-  std::vector<hipEvent_t> copied[2];            // per job: the event behind its asynchronous matrix copy, or null
+  DevBuf d_multi;                               // int progress counters of a pair dealt to several workgroups (hx_dag.hip MULTI)
+  std::vector<DevEvents<1>> copied[2];          // per job: the event behind its asynchronous matrix copy, made at the job's first copy
   bool records_valid = false;        // the per-state records (FwdPack) of the device job tables are built (launch_prep / ensure_state_records)
-  int32_t* d_trace = nullptr;        // hx_batch_best_trace: path buffers, kept between calls
-  int64_t* d_trace_n = nullptr;
-  void* h_trace = nullptr;
+  DevBuf d_trace;                    // hx_batch_best_trace: path buffers (int32_t), kept between calls
+  DevBuf d_trace_n;                  // (int64_t)
+  PinnedBuf h_trace;
   int64_t trace_cap = 0;
   bool trace_ties_valid = false;     // the near-tie flags of the last hx_batch_best_trace are in d_trace_n's third block
   struct TransIndex {                // per job: in-slot -> transition index of both profiles (hx_batch_event_counts)
@@ -605,17 +570,20 @@ struct hx_batch {
     int32_t x_trans, y_trans;
   };
   std::vector<TransIndex> trans_index;
-  double* d_events = nullptr;        // hx_batch_event_counts: scratch kept with the batch, grown on demand
+  DevBuf d_events;                   // hx_batch_event_counts: scratch (doubles) kept with the batch, grown on demand
   size_t events_doubles = 0;
+  const DevJob* device_jobs() const { return d_jobs.as<DevJob>(); }
+  // what is in flight on the batch's device is done before the members release their memory (they do so after this body)
+  ~hx_batch() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }
 };
 
 namespace {
 // (re)upload both job tables: the caller's order and the class order
 int publish_jobs(hx_batch* b) {
-  HIP_TRY(hipMemcpy(b->d_jobs, b->jobs.data(), sizeof(DevJob) * b->n_jobs, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_jobs.as<void>(), b->jobs.data(), sizeof(DevJob) * b->n_jobs, hipMemcpyHostToDevice));
   std::vector<DevJob> sorted((size_t)b->n_jobs);
   for (int p = 0; p < b->n_jobs; ++p) sorted[p] = b->jobs[b->order[p]];
-  HIP_TRY(hipMemcpy(b->d_jobs_cls, sorted.data(), sizeof(DevJob) * b->n_jobs, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_jobs_cls.as<void>(), sorted.data(), sizeof(DevJob) * b->n_jobs, hipMemcpyHostToDevice));
   return HX_OK;
 }
 // every entry point that touches a batch runs on the batch's device
@@ -646,7 +614,7 @@ int open_reader(const hx_batch* b, bool args_ok, const int32_t* job, unsigned ne
 namespace hx {
 // hx_sumprod.hip: the 8-byte log_sum_exp table of an initialised device, or null
 const double* device_lse_table(int device) {
-  return device >= 0 && device < HX_MAX_DEVICES && g_dev[device].ready ? g_dev[device].tab : nullptr;
+  return device >= 0 && device < HX_MAX_DEVICES && g_dev[device].ready ? g_dev[device].tab.as<double>() : nullptr;
 }
 int api_fail(int code, const char* what) { return fail(code, "%s", what); }
 }  // namespace hx
@@ -661,11 +629,7 @@ namespace {
 // keep_stream: hx_init on an ordinal that is already initialised replaces the tables only - batches created before keep the
 // device's copy stream (hx_batch::copy_stream) and their events on it
 void free_tables(DeviceTables& t, bool keep_stream = false) {
-  if (t.tab) (void)hipFree(t.tab);
-  if (t.fast_tab) (void)hipFree(t.fast_tab);
-  if (t.log_tab) (void)hipFree(t.log_tab);
-  if (t.pair_tab) (void)hipFree(t.pair_tab);
-  t.tab = t.fast_tab = t.log_tab = t.pair_tab = nullptr;
+  t.tab.reset(); t.fast_tab.reset(); t.log_tab.reset(); t.pair_tab.reset();
   if (!keep_stream) {
     if (t.copy_stream) (void)hipStreamDestroy(t.copy_stream);
     if (t.side_stream) (void)hipStreamDestroy(t.side_stream);
@@ -673,9 +637,9 @@ void free_tables(DeviceTables& t, bool keep_stream = false) {
   }
   t.ready = false;
 }
-int upload(double** dst, const std::vector<double>& src) {
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), src.size() * sizeof(double)));
-  HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
+int upload(DevBuf& dst, const std::vector<double>& src) {
+  if (!dst.alloc(src.size() * sizeof(double))) return alloc_failed("hipMalloc(reinterpret_cast<void**>(dst), src.size() * sizeof(double))");
+  HIP_TRY(hipMemcpy(dst.as<void>(), src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice));
   return HX_OK;
 }
 }  // namespace
@@ -698,19 +662,19 @@ int hx_init(int device_ordinal, const double* lse_table, size_t n_entries) {
   free_tables(D, /*keep_stream*/ true);
   try {
     int rc;
-    if ((rc = upload(&D.tab, std::vector<double>(lse_table, lse_table + n_entries))) != HX_OK) { free_tables(D); return rc; }
+    if ((rc = upload(D.tab, std::vector<double>(lse_table, lse_table + n_entries))) != HX_OK) { free_tables(D); return rc; }
     std::vector<double> pairs(2 * n_entries, 0.0);
     for (size_t n = 0; n < n_entries; ++n) {
       pairs[2 * n] = lse_table[n];
       pairs[2 * n + 1] = n + 1 < n_entries ? lse_table[n + 1] - lse_table[n] : 0.0;
     }
-    if ((rc = upload(&D.pair_tab, pairs)) != HX_OK) { free_tables(D); return rc; }
+    if ((rc = upload(D.pair_tab, pairs)) != HX_OK) { free_tables(D); return rc; }
     std::vector<double> lt((size_t)log_table_doubles());
     build_log_table(lt.data());
-    if ((rc = upload(&D.log_tab, lt)) != HX_OK) { free_tables(D); return rc; }
+    if ((rc = upload(D.log_tab, lt)) != HX_OK) { free_tables(D); return rc; }
     std::vector<double> ft;
     build_fast_table(ft);
-    if ((rc = upload(&D.fast_tab, ft)) != HX_OK) { free_tables(D); return rc; }
+    if ((rc = upload(D.fast_tab, ft)) != HX_OK) { free_tables(D); return rc; }
   } catch (const std::bad_alloc&) {
     free_tables(D);
     return fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -735,8 +699,8 @@ int hx_shutdown(void) {
 namespace {
 // ---- the steps of hx_batch_create ----
 
-// Validates job k and puts its profiles and model into the staging image.
-int flatten_job(const hx_pair_job& pj, int k, Arena& ar, JobOff& jo) {
+// Validates job k and puts its profiles and model into the staging image; J's pointers to them are the arena's to set.
+int flatten_job(const hx_pair_job& pj, int k, Arena& ar, JobOff& jo, DevJob& J) {
   const hx_hmm* h = pj.hmm;
   if (!h || !pj.x || !pj.y) return fail(HX_ERR_INVALID_ARG, "job %d has null members", k);
   const int A = h->alph_size, C = h->components, CA = A * C;
@@ -745,20 +709,22 @@ int flatten_job(const hx_pair_job& pj, int k, Arena& ar, JobOff& jo) {
     return fail(HX_ERR_INVALID_ARG, "job %d: null hmm arrays", k);
   const bool need_env = pj.max_distance >= 0;
   int rc;
-  if ((rc = flatten_profile(pj.x, CA, need_env, false, ar, jo.x)) != HX_OK) return rc;
-  if ((rc = flatten_profile(pj.y, CA, need_env, true, ar, jo.y)) != HX_OK) return rc;
-  jo.log_root = ar.put(h->log_root, sizeof(double) * CA);
-  jo.log_sub_l = ar.put(h->log_sub_l, sizeof(double) * CA * A);
-  jo.log_sub_r = ar.put(h->log_sub_r, sizeof(double) * CA * A);
-  jo.log_ins_l = ar.put(h->log_ins_l, sizeof(double) * CA);
-  jo.log_ins_r = ar.put(h->log_ins_r, sizeof(double) * CA);
-  jo.log_cptw_l = ar.put(h->log_cptw_l, sizeof(double) * C);
-  jo.log_cptw_r = ar.put(h->log_cptw_r, sizeof(double) * C);
+  if ((rc = flatten_profile(pj.x, CA, need_env, false, ar, jo.x, J.x)) != HX_OK) return rc;
+  if ((rc = flatten_profile(pj.y, CA, need_env, true, ar, jo.y, J.y)) != HX_OK) return rc;
+  ar.put(J.log_root, h->log_root, (size_t)CA);
+  ar.put(J.log_sub_l, h->log_sub_l, (size_t)CA * A);
+  ar.put(J.log_sub_r, h->log_sub_r, (size_t)CA * A);
+  ar.put(J.log_ins_l, h->log_ins_l, (size_t)CA);
+  ar.put(J.log_ins_r, h->log_ins_r, (size_t)CA);
+  ar.put(J.log_cptw_l, h->log_cptw_l, (size_t)C);
+  ar.put(J.log_cptw_r, h->log_cptw_r, (size_t)C);
   const int64_t pairs = (int64_t)jo.x.n_cls * jo.y.n_cls;
   jo.table_emission = pairs > 0 && pairs <= (1 << 16);
-  jo.emis = jo.table_emission ? ar.reserve(sizeof(double) * pairs) : 0;
-  jo.emis_pad = jo.table_emission ? ar.reserve(sizeof(double) * (jo.x.n_cls + 1) * (jo.y.n_cls + 1)) : 0;
-  jo.fwd_windows = jo.bwd_windows = jo.strip_base = jo.yword = jo.yword_bwd = jo.band_rows = jo.band_rows_bwd = 0;
+  if (jo.table_emission) {                                        // (else both stay null: per-cell emission planes)
+    ar.point(J.emis, ar.reserve(sizeof(double) * pairs));
+    ar.point(J.emis_pad, ar.reserve(sizeof(double) * (jo.x.n_cls + 1) * (jo.y.n_cls + 1)));
+  }
+  jo.band_rows_bwd = 0;
   jo.compressed = false;
   jo.compact_plane = 0;
   return HX_OK;
@@ -790,7 +756,7 @@ std::vector<int32_t> staged_ecls(const Arena& ar, const ProfOff& o) {
 
 // Per-column words of the banded scaled-probability fill (hx_linear.hip): {emission class : 8, not ready : 1, always in
 // envelope : 1, envelope coordinate : 22}, with 64 words of padding on either side (the edge columns').
-void put_ywords(Arena& ar, JobOff& jo, const hx_pair_job& pj) {
+void put_ywords(Arena& ar, const JobOff& jo, DevJob& J, const hx_pair_job& pj) {
   const bool need_env = pj.max_distance >= 0;
   const int Cc = jo.y.n - 1;
   const std::vector<uint8_t> yf = staged_flags(ar, jo.y);
@@ -802,7 +768,7 @@ void put_ywords(Arena& ar, JobOff& jo, const hx_pair_job& pj) {
     const uint32_t env = (need_env && pj.y->env_pos) ? (uint32_t)pj.y->env_pos[j] : 0u;
     yw[jp] = (uint32_t)ecls[j] | (ready ? 0u : 0x100u) | ((yf[j] & F_EDGE) ? 0x200u : 0u) | (env << 10);
   }
-  jo.yword = ar.put(yw.data(), sizeof(uint32_t) * yw.size());
+  ar.put(J.yword, yw.data(), yw.size());
   // Backward: sweep column j is y state jc = Cc-1-j; its own readiness, edge flag and envelope coordinate, and the
   // emission class of state jc+1
   for (int jp = 0; jp < Cc + 328; ++jp) {
@@ -811,22 +777,22 @@ void put_ywords(Arena& ar, JobOff& jo, const hx_pair_job& pj) {
     const uint32_t env = (need_env && pj.y->env_pos) ? (uint32_t)pj.y->env_pos[jc] : 0u;
     yw[jp] = (uint32_t)ecls[jc + 1] | (ready ? 0u : 0x100u) | ((yf[jc] & F_EDGE) ? 0x200u : 0u) | (env << 10);
   }
-  jo.yword_bwd = ar.put(yw.data(), sizeof(uint32_t) * yw.size());
+  ar.put(J.yword_bwd, yw.data(), yw.size());
 }
 
 // The step windows of a banded job's strips (strip_windows), Forward and Backward.  Band-compressed storage: a strip keeps
 // only the step windows it sweeps.  The windows are put into the form the fill uses them in (whole step pairs, clipped,
 // merged when they touch - k_fill_leaf_linear), which that kernel's own widening leaves unchanged, and every window gets
 // its offset in the state plane; cwin / cbase receive them.
-void put_windows(Arena& ar, JobOff& jo, const hx_pair_job& pj, uint32_t flags, std::vector<int32_t>& cwin,
+void put_windows(Arena& ar, JobOff& jo, DevJob& J, const hx_pair_job& pj, uint32_t flags, std::vector<int32_t>& cwin,
                  std::vector<int64_t>& cbase) {
   const int R = jo.x.n - 1, Cc = jo.y.n - 1;
   const std::vector<uint8_t> xf = staged_flags(ar, jo.x), yf = staged_flags(ar, jo.y);
   const std::vector<int32_t> wf = strip_windows(xf.data(), pj.x->env_pos, yf.data(), pj.y->env_pos, R, Cc, pj.max_distance, false);
   const std::vector<int32_t> wb = strip_windows(xf.data(), pj.x->env_pos, yf.data(), pj.y->env_pos, R, Cc, pj.max_distance, true);
-  jo.bwd_windows = ar.put(wb.data(), sizeof(int32_t) * wb.size());
+  ar.put(J.bwd_windows, wb.data(), wb.size());
   if (!(flags & HX_BAND_COMPRESSED)) {
-    jo.fwd_windows = ar.put(wf.data(), sizeof(int32_t) * wf.size());
+    ar.put(J.fwd_windows, wf.data(), wf.size());
     return;
   }
   std::vector<int32_t> we(wf);
@@ -849,8 +815,8 @@ void put_windows(Arena& ar, JobOff& jo, const hx_pair_job& pj, uint32_t flags, s
       off += (int64_t)((hi[w] - lo[w]) >> 1) * (2 * HX_STRIP);
     }
   }
-  jo.fwd_windows = ar.put(we.data(), sizeof(int32_t) * we.size());
-  jo.strip_base = ar.put(sb.data(), sizeof(int64_t) * sb.size());
+  ar.put(J.fwd_windows, we.data(), we.size());
+  ar.put(J.strip_base, sb.data(), sb.size());
   cwin = we; cbase = sb;
   jo.compressed = true;
   jo.compact_plane = (off + 1) & ~(int64_t)1;
@@ -860,6 +826,8 @@ void put_windows(Arena& ar, JobOff& jo, const hx_pair_job& pj, uint32_t flags, s
 void init_job(DevJob& J, hx_layout& L, const JobOff& jo, const hx_pair_job& pj, bool interleaved) {
   const hx_hmm* h = pj.hmm;
   memset(&J, 0, sizeof(J));
+  J.x.n = jo.x.n; J.x.empty = jo.x.empty; J.x.n_cls = jo.x.n_cls;
+  J.y.n = jo.y.n; J.y.empty = jo.y.empty; J.y.n_cls = jo.y.n_cls;
   for (int s = 0; s < 5; ++s)
     for (int d = 0; d < 6; ++d) J.T[s][d] = h->lp_trans[s][d];
   J.A = h->alph_size; J.C = h->components; J.CA = J.A * J.C;
@@ -923,8 +891,8 @@ bool plan_band_sweep(Arena& ar, JobOff& jo, DevJob& J, const hx_pair_job& pj, in
   const bool fits = band_kernel_fits(band_mode, J.n_rows, J.n_cols, std::max(jo.x.n_cls, jo.y.n_cls));
   const bool trimmed = fits && jo.compressed && forward_rows(twin.data(), tbase.data());
   if (trimmed) {
-    jo.fwd_windows = ar.put(twin.data(), sizeof(int32_t) * twin.size());
-    jo.strip_base = ar.put(tbase.data(), sizeof(int64_t) * tbase.size());
+    ar.put(J.fwd_windows, twin.data(), twin.size());              // (in place of put_windows': the arena binds in the order of the puts)
+    ar.put(J.strip_base, tbase.data(), tbase.size());
     jo.compact_plane = tplane;
     J.plane = tplane;
     J.matrix_doubles = 5 * J.plane;
@@ -940,13 +908,13 @@ bool plan_band_sweep(Arena& ar, JobOff& jo, DevJob& J, const hx_pair_job& pj, in
       build_band_rows_bwd(pj.x->env_pos, pj.y->env_pos, xf.data(), yf.data(), xecls.data(), jo.x.empty != 0, jo.y.empty != 0, J.n_rows, J.n_cols,
                           pj.max_distance, J.strip_stride, J.blk, rows_b, n_steps_b);
   if (!bwd_ok) return false;
-  jo.band_rows = ar.put(rows.data(), sizeof(int32_t) * rows.size());
+  ar.point(J.band_rows, ar.put(rows.data(), sizeof(int32_t) * rows.size()));
   J.band_steps = n_steps;
   J.band_w32 = (J.blk == 2 * HX_STRIP && ring32(rows, J.n_rows) && (jo.compressed || ring32(rows_b, J.n_rows)) &&
                 band2_kernel_fits(J.n_rows, J.n_cols, std::max(jo.x.n_cls, jo.y.n_cls))) ? 1 : 0;
   J.band_steps_bwd = 0;
   if (!jo.compressed) {
-    jo.band_rows_bwd = ar.put(rows_b.data(), sizeof(int32_t) * rows_b.size());
+    ar.point(J.band_rows_bwd, jo.band_rows_bwd = ar.put(rows_b.data(), sizeof(int32_t) * rows_b.size()));
     J.band_steps_bwd = n_steps_b;
   }
   return true;
@@ -1017,64 +985,43 @@ void order_classes(hx_batch* b, const hx_pair_job* jobs, const std::vector<JobOf
   }
 }
 
-// hipMalloc of n doubles, with the error the ABI reports for it
-int alloc_doubles(double** p, int64_t n, const char* what) {
-  if (hipMalloc(reinterpret_cast<void**>(p), sizeof(double) * (size_t)n) == hipSuccess) return HX_OK;
+// n doubles on the device, with the error the ABI reports for it
+int alloc_doubles(DevBuf& buf, int64_t n, const char* what) {
+  if (buf.alloc(sizeof(double) * (size_t)n)) return HX_OK;
   return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld %s bytes failed", (long long)(n * 8), what);
 }
 
 // Device memory of the batch: the staging image, the matrices and scratch planes; the device pointers of every job.
 int allocate_and_bind(hx_batch* b, const Arena& ar, const std::vector<JobOff>& offs, const std::vector<int64_t>& mat_off,
                       const std::vector<int64_t>& agg_off, int64_t mat_total, int64_t eplane_total, int64_t agg_total) {
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_arena), ar.host.size() + 256) != hipSuccess)
-    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %zu input bytes failed", ar.host.size());
-  if (hipMemcpy(b->d_arena, ar.host.data(), ar.host.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(HX_ERR_HIP, "input upload failed");
+  if (!b->d_arena.alloc(ar.host.size() + 256)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %zu input bytes failed", ar.host.size());
+  if (hipMemcpy(b->d_arena.as<void>(), ar.host.data(), ar.host.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(HX_ERR_HIP, "input upload failed");
   int rc;
-  if ((rc = alloc_doubles(&b->d_fwd, mat_total, "Forward-matrix")) != HX_OK) return rc;
+  if ((rc = alloc_doubles(b->d_fwd, mat_total, "Forward-matrix")) != HX_OK) return rc;
   b->fwd_total = mat_total;
-  if (eplane_total > 0 && (rc = alloc_doubles(&b->d_eplane, eplane_total, "emission-plane")) != HX_OK) return rc;
-  if (agg_total > 0 && (rc = alloc_doubles(&b->d_agg, agg_total, "scratch")) != HX_OK) return rc;
-  if ((b->flags & HX_KEEP_BACKWARD) && (rc = alloc_doubles(&b->d_bwd, mat_total, "Backward-matrix")) != HX_OK) return rc;
+  if (eplane_total > 0 && (rc = alloc_doubles(b->d_eplane, eplane_total, "emission-plane")) != HX_OK) return rc;
+  if (agg_total > 0 && (rc = alloc_doubles(b->d_agg, agg_total, "scratch")) != HX_OK) return rc;
+  if ((b->flags & HX_KEEP_BACKWARD) && (rc = alloc_doubles(b->d_bwd, mat_total, "Backward-matrix")) != HX_OK) return rc;
 
   ClassRange& rot = b->cls[KC_LEAF_ROT_BANDED];
   rot.bwd_band = rot.n > 0 && !getenv("HX_BAND_BWD_OLD");
   for (int p = rot.begin; p < rot.begin + rot.n; ++p)
     if (!offs[b->order[p]].band_rows_bwd) rot.bwd_band = false;
   b->trans_index.resize((size_t)b->n_jobs);
+  char* const base = b->d_arena.as<char>();
+  ar.bind(base);                      // what flatten_job put: the profiles' arrays and the model's
   for (int k = 0; k < b->n_jobs; ++k) {
     DevJob& J = b->jobs[k];
     const JobOff& jo = offs[k];
-    char* base = b->d_arena;
-    bind_profile(J.x, jo.x, base);
-    bind_profile(J.y, jo.y, base);
     b->trans_index[k] = {reinterpret_cast<int32_t*>(base + jo.x.in_idx), reinterpret_cast<int32_t*>(base + jo.y.in_idx), jo.x.n_trans, jo.y.n_trans};
-    J.log_root = reinterpret_cast<double*>(base + jo.log_root);
-    J.log_sub_l = reinterpret_cast<double*>(base + jo.log_sub_l);
-    J.log_sub_r = reinterpret_cast<double*>(base + jo.log_sub_r);
-    J.log_ins_l = reinterpret_cast<double*>(base + jo.log_ins_l);
-    J.log_ins_r = reinterpret_cast<double*>(base + jo.log_ins_r);
-    J.log_cptw_l = reinterpret_cast<double*>(base + jo.log_cptw_l);
-    J.log_cptw_r = reinterpret_cast<double*>(base + jo.log_cptw_r);
-    J.emis = jo.table_emission ? reinterpret_cast<double*>(base + jo.emis) : nullptr;
-    J.emis_pad = jo.table_emission ? reinterpret_cast<double*>(base + jo.emis_pad) : nullptr;
-    J.emis_plane = jo.eplane_off >= 0 ? b->d_eplane + jo.eplane_off : nullptr;
-    J.agg = agg_off[k] >= 0 ? b->d_agg + agg_off[k] : nullptr;
-    J.fwd_windows = J.max_dist >= 0 ? reinterpret_cast<int32_t*>(base + jo.fwd_windows) : nullptr;
-    J.bwd_windows = J.max_dist >= 0 ? reinterpret_cast<int32_t*>(base + jo.bwd_windows) : nullptr;
-    J.strip_base = jo.compressed ? reinterpret_cast<int64_t*>(base + jo.strip_base) : nullptr;
-    J.yword = jo.yword ? reinterpret_cast<uint32_t*>(base + jo.yword) : nullptr;
-    J.yword_bwd = jo.yword_bwd ? reinterpret_cast<uint32_t*>(base + jo.yword_bwd) : nullptr;
-    J.band_rows = jo.band_rows ? base + jo.band_rows : nullptr;
-    J.band_rows_bwd = jo.band_rows_bwd ? base + jo.band_rows_bwd : nullptr;
+    J.emis_plane = jo.eplane_off >= 0 ? b->d_eplane.as<double>() + jo.eplane_off : nullptr;
+    J.agg = agg_off[k] >= 0 ? b->d_agg.as<double>() + agg_off[k] : nullptr;
     J.lp_end = reinterpret_cast<double*>(base + b->lp_end_off) + k;
     J.lp_start = reinterpret_cast<double*>(base + b->lp_start_off) + k;
-    J.fwd = b->d_fwd + mat_off[k];
-    J.bwd = b->d_bwd ? b->d_bwd + mat_off[k] : nullptr;
+    J.fwd = b->d_fwd.as<double>() + mat_off[k];
+    J.bwd = b->d_bwd ? b->d_bwd.as<double>() + mat_off[k] : nullptr;
   }
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_jobs), sizeof(DevJob) * b->n_jobs) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&b->d_jobs_cls), sizeof(DevJob) * b->n_jobs) != hipSuccess)
-    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of job table failed");
+  if (!b->d_jobs.alloc(sizeof(DevJob) * b->n_jobs) || !b->d_jobs_cls.alloc(sizeof(DevJob) * b->n_jobs)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of job table failed");
   return HX_OK;
 }
 }  // namespace
@@ -1092,16 +1039,18 @@ static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs
   const auto tick = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tc0 = tick();
 
-  hx_batch* b = new (std::nothrow) hx_batch;
+  // (from here to the release at the end the batch frees itself on every way out, a std::bad_alloc's included)
+  std::unique_ptr<hx_batch> owner(new (std::nothrow) hx_batch);
+  hx_batch* const b = owner.get();
   if (!b) return fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed");
   b->device = device;
   b->n_jobs = n_jobs;
   b->flags = flags;
   b->pol = Policy(flags);
-  b->jobs.resize(n_jobs);
+  b->jobs.resize(n_jobs);             // (not resized again: the arena keeps the addresses of the jobs' pointer members)
   b->layouts.resize(n_jobs);
 
-  Arena ar;
+  Arena ar(256);
   std::vector<JobOff> offs(n_jobs);
   std::vector<int> kclass(n_jobs);
   int64_t eplane_total = 0;
@@ -1109,7 +1058,7 @@ static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs
   for (int k = 0; k < n_jobs; ++k) {
     const hx_pair_job& pj = jobs[k];
     JobOff& jo = offs[k];
-    if ((rc = flatten_job(pj, k, ar, jo)) != HX_OK) break;
+    if ((rc = flatten_job(pj, k, ar, jo, b->jobs[k])) != HX_OK) break;
     const bool need_env = pj.max_distance >= 0;
     int kc = choose_class(jo, need_env, flags);
     if ((flags & HX_BAND_COMPRESSED) && (kc >= KC_DAG || (flags & HX_KEEP_BACKWARD))) {
@@ -1117,11 +1066,11 @@ static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs
                                     "no general profiles (job %d), no HX_KEEP_BACKWARD / HX_FORCE_GENERIC", k);
       break;
     }
-    if (b->pol.linear && (kc == KC_LEAF_LDS || kc == KC_LEAF_LDS_BANDED) && jo.y.n >= 2) put_ywords(ar, jo, pj);
+    DevJob& J = b->jobs[k];
+    if (b->pol.linear && (kc == KC_LEAF_LDS || kc == KC_LEAF_LDS_BANDED) && jo.y.n >= 2) put_ywords(ar, jo, J, pj);
     std::vector<int32_t> cwin;
     std::vector<int64_t> cbase;
-    if (need_env) put_windows(ar, jo, pj, flags, cwin, cbase);
-    DevJob& J = b->jobs[k];
+    if (need_env) put_windows(ar, jo, J, pj, flags, cwin, cbase);
     hx_layout& L = b->layouts[k];
     // Unbanded leaf pairs of the scaled-probability fills keep the five states of a step pair adjacent: a wavefront then
     // writes 5 KiB contiguous per iteration instead of 1 KiB into each of five planes (hx_linear.hip; same total size).
@@ -1135,7 +1084,7 @@ static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs
     L.mirrored = 0; L.compressed = jo.compressed ? 1 : 0;
     tally_job(b, kc, jo, J, eplane_total);
   }
-  if (rc != HX_OK) { delete b; return rc; }
+  if (rc != HX_OK) return rc;
 
   int64_t mat_total = 0, agg_total = 0;
   std::vector<int64_t> mat_off(n_jobs), agg_off(n_jobs, -1);
@@ -1144,18 +1093,16 @@ static int batch_create_impl(int device, const hx_pair_job* jobs, int32_t n_jobs
   b->lp_end_off = ar.reserve(sizeof(double) * n_jobs);
   b->lp_start_off = ar.reserve(sizeof(double) * n_jobs);
 
-  auto cleanup = [&](int code) { hx_batch_destroy(b); return code; };
   const double tc1 = tick();
-  if ((rc = allocate_and_bind(b, ar, offs, mat_off, agg_off, mat_total, eplane_total, agg_total)) != HX_OK) return cleanup(rc);
+  if ((rc = allocate_and_bind(b, ar, offs, mat_off, agg_off, mat_total, eplane_total, agg_total)) != HX_OK) return rc;
   const double tc2 = tick();
-  if ((rc = publish_jobs(b)) != HX_OK) return cleanup(rc);
+  if ((rc = publish_jobs(b)) != HX_OK) return rc;
   if (timing)
     fprintf(stderr, "timing: hx_batch_create of %d jobs: host images and plans %.4f s, allocations and upload of %zu bytes %.4f s, job tables %.4f s\n",
             n_jobs, tc1 - tc0, ar.host.size(), tc2 - tc1, tick() - tc2);
   for (int w = 0; w < 2; ++w)
-    for (int e = 0; e < 2; ++e)
-      if (hipEventCreate(&b->ev[w][e]) != hipSuccess) return cleanup(fail(HX_ERR_HIP, "hipEventCreate failed"));
-  *out = b;
+    if (!b->ev[w].create()) return fail(HX_ERR_HIP, "hipEventCreate failed");
+  *out = owner.release();
   return HX_OK;
 }
 
@@ -1166,8 +1113,8 @@ int hx_batch_create_on(int device, const hx_pair_job* jobs, int32_t n_jobs, uint
   else if (!(flags & HX_LSE_TRUNC)) flags |= HX_LSE_TRUNC;
   try {
     return batch_create_impl(device, jobs, n_jobs, flags, out);
-  } catch (const std::bad_alloc&) {         // (std::vector / Arena growth: nothing throws across the ABI)
-    if (out) *out = nullptr;
+  } catch (const std::bad_alloc&) {         // (std::vector / Arena growth: nothing throws across the ABI, and nothing leaks -
+    if (out) *out = nullptr;                //  batch_create_impl holds the batch in a unique_ptr, which has released it by now)
     return fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed while building the batch");
   }
 }
@@ -1179,33 +1126,7 @@ int hx_batch_create(const hx_pair_job* jobs, int32_t n_jobs, uint32_t flags, hx_
 
 int hx_batch_device(const hx_batch* b) { return b ? b->device : -1; }
 
-int hx_batch_destroy(hx_batch* b) {
-  if (!b) return HX_OK;
-  (void)hipSetDevice(b->device);
-  (void)hipDeviceSynchronize();
-  for (int w = 0; w < 2; ++w)
-    for (int e = 0; e < 2; ++e)
-      if (b->ev[w][e]) (void)hipEventDestroy(b->ev[w][e]);
-  for (int e = 0; e < 2; ++e)
-    if (b->ev_side[e]) (void)hipEventDestroy(b->ev_side[e]);
-  for (int w = 0; w < 2; ++w)
-    for (hipEvent_t e : b->copied[w])
-      if (e) (void)hipEventDestroy(e);
-  if (b->d_multi) (void)hipFree(b->d_multi);
-  if (b->d_jobs) (void)hipFree(b->d_jobs);
-  if (b->d_jobs_cls) (void)hipFree(b->d_jobs_cls);
-  if (b->d_arena) (void)hipFree(b->d_arena);
-  if (b->d_fwd) (void)hipFree(b->d_fwd);
-  if (b->d_bwd) (void)hipFree(b->d_bwd);
-  if (b->d_eplane) (void)hipFree(b->d_eplane);
-  if (b->d_agg) (void)hipFree(b->d_agg);
-  if (b->d_trace) (void)hipFree(b->d_trace);
-  if (b->d_trace_n) (void)hipFree(b->d_trace_n);
-  if (b->h_trace) (void)hipHostFree(b->h_trace);
-  if (b->d_events) (void)hipFree(b->d_events);
-  delete b;
-  return HX_OK;
-}
+int hx_batch_destroy(hx_batch* b) { delete b; return HX_OK; }
 
 // a launcher refused the shape (LDS plan over budget, grid too large ...): an error code, never a faulting launch
 #define LAUNCH_TRY(expr)                                                                             \
@@ -1240,8 +1161,7 @@ static hipStream_t side_fork(hx_batch* b, hipStream_t st) {
     side = D.side_stream;
   }
   if (!side) return st;
-  for (int e = 0; e < 2; ++e)
-    if (!b->ev_side[e] && hipEventCreateWithFlags(&b->ev_side[e], hipEventDisableTiming) != hipSuccess) { b->ev_side[e] = nullptr; return st; }
+  if (!b->ev_side.create(hipEventDisableTiming)) return st;
   if (hipEventRecord(b->ev_side[0], st) != hipSuccess || hipStreamWaitEvent(side, b->ev_side[0], 0) != hipSuccess) return st;
   return side;
 }
@@ -1256,7 +1176,7 @@ static int side_join(hx_batch* b, hipStream_t st, hipStream_t side) {
 // the preparation): built on first demand for a batch of leaf pairs, and with every preparation from then on.
 static void ensure_state_records(hx_batch* b, hipStream_t st) {
   if (b->records_valid) return;
-  launch_state_records(b->d_jobs, b->n_jobs, b->max_states, st);
+  launch_state_records(b->device_jobs(), b->n_jobs, b->max_states, st);
   b->records_valid = true;
 }
 
@@ -1279,9 +1199,9 @@ static void prefill_neg_inf(const hx_batch* b, double* mat, const ClassRange& cr
 // and hx_daglin.hip MULTI): allocated on first use; the Forward fill (dir 0) uses the first half of the buffer, the Backward
 // fill the second (a caller may run the two fills on two streams).  The first `ints` of the fill's half are zeroed on st.
 static int zeroed_counters(hx_batch* b, int dir, size_t ints, hipStream_t st, int** counters) {
-  if (!b->d_multi && hipMalloc(reinterpret_cast<void**>(&b->d_multi), 2 * HX_MULTI_COUNTER_PAIRS * 256 * sizeof(int)) != hipSuccess)
+  if (!b->d_multi && !b->d_multi.alloc(2 * HX_MULTI_COUNTER_PAIRS * 256 * sizeof(int)))
     return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of the progress counters failed");
-  *counters = b->d_multi + (size_t)dir * HX_MULTI_COUNTER_PAIRS * 256;
+  *counters = b->d_multi.as<int>() + (size_t)dir * HX_MULTI_COUNTER_PAIRS * 256;
   HIP_TRY(hipMemsetAsync(*counters, 0, ints * sizeof(int), st));
   return HX_OK;
 }
@@ -1290,19 +1210,19 @@ static int zeroed_counters(hx_batch* b, int dir, size_t ints, hipStream_t st, in
 // with its edge kernel on the side stream.
 static int fill_band_sweep(hx_batch* b, const ClassRange& cr, int dir, hipStream_t st) {
   const DeviceTables& D = g_dev[b->device];
-  const DevJob* jobs = b->d_jobs_cls + cr.begin;
+  const DevJob* jobs = b->d_jobs_cls.as<DevJob>() + cr.begin;
   const bool sparse = (b->flags & (HX_SPARSE_ENVELOPE | HX_BAND_COMPRESSED)) != 0;
   if (band2_wanted(b->pol.linear, cr.n, cr.n_w32)) {
     const hipStream_t side = side_fork(b, st);
     LAUNCH_TRY((dir ? launch_backward_band2 : launch_forward_band2)(jobs, cr.n, b->pol.trunc, cr.max_rows, cr.max_cols, cr.max_cls,
-                                                                    Tab8{D.tab}, Tab16{D.log_tab}, sparse, st, side));
+                                                                    D.tab8(), D.log16(), sparse, st, side));
     int rc;
     if ((rc = side_join(b, st, side)) != HX_OK) return rc;
-    launch_band2_result(jobs, cr.n, dir, Tab8{D.tab}, st);
+    launch_band2_result(jobs, cr.n, dir, D.tab8(), st);
     return HX_OK;
   }
   LAUNCH_TRY((dir ? launch_backward_band : launch_forward_band)(jobs, cr.n, b->pol.band_mode, cr.max_rows, cr.max_cols, cr.max_cls,
-                                                                Tab8{D.tab}, b->pol.band_tab(D), sparse, st));
+                                                                D.tab8(), b->pol.band_tab(D), sparse, st));
   return HX_OK;
 }
 
@@ -1340,7 +1260,7 @@ static bool linear_fold_admits(const hx_batch* b, const ClassRange& cr) {
 static int fill_strips(hx_batch* b, int c, int dir, hipStream_t st) {
   const DeviceTables& D = g_dev[b->device];
   const ClassRange& cr = b->cls[c];
-  const DevJob* jobs = b->d_jobs_cls + cr.begin;
+  const DevJob* jobs = b->d_jobs_cls.as<DevJob>() + cr.begin;
   const bool banded = banded_class(c);
   const int leaf = (c == KC_LEAF_LDS || c == KC_LEAF_LDS_BANDED || c == KC_LEAF_ROT_BANDED) ? 2 : ((c == KC_LEAF || c == KC_LEAF_BANDED) ? 1 : 0);
   const int multi = (leaf == 2 && !banded && cr.n <= HX_MULTI_COUNTER_PAIRS && !b->no_multi) ? chain_multi_groups(cr.n, cr.max_rows, b->pol.linear ? 64 : 128) : 1;
@@ -1353,13 +1273,13 @@ static int fill_strips(hx_batch* b, int c, int dir, hipStream_t st) {
   if (b->pol.linear && leaf == 2 && dir == 0) {
     const bool fold = !banded && multi <= 1 && linear_fold_admits(b, cr);
     if (!banded) b->forward_folded = fold;
-    LAUNCH_TRY(launch_forward_leaf_linear(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab}, cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi,
+    LAUNCH_TRY(launch_forward_leaf_linear(jobs, cr.n, cr.max_rows, banded, D.tab8(), D.log16(), cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi,
                                           counters, b->pol.trunc, fold, st));
   } else if (b->pol.linear && leaf == 2)
-    LAUNCH_TRY(launch_backward_leaf_linear(jobs, cr.n, cr.max_rows, banded, Tab8{D.tab}, Tab16{D.log_tab}, cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi,
+    LAUNCH_TRY(launch_backward_leaf_linear(jobs, cr.n, cr.max_rows, banded, D.tab8(), D.log16(), cr.yl_cols, cr.yl_emis, cr.max_cls + 1, multi,
                                            counters, b->pol.trunc, st));
   else
-    LAUNCH_TRY((dir ? launch_backward_chain : launch_forward_chain)(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, leaf, banded,
+    LAUNCH_TRY((dir ? launch_backward_chain : launch_forward_chain)(jobs, cr.n, cr.max_rows, D.tab8(), b->pol.lse_tab(D), b->pol.fast, leaf, banded,
                                                                     cr.yl_cols, cr.yl_emis, multi, counters, st));
   return HX_OK;
 }
@@ -1408,48 +1328,48 @@ int hx_batch_forward(hx_batch* b, void* stream) {
   // counting kernel first asks (ensure_state_records)
   const bool records_now = b->cls[KC_DAG].n > 0 || b->cls[KC_DAG_BANDED].n > 0 || b->cls[KC_GENERIC].n > 0 || b->records_valid ||
                            (b->flags & HX_FORCE_GENERIC) != 0 || getenv("HX_FORCE_DAG") != nullptr;
-  LAUNCH_TRY(launch_prep(b->d_jobs, b->n_jobs, b->max_states, b->max_cls, b->max_ca, b->max_cls_pairs, Tab8{D.tab}, records_now, st));
+  LAUNCH_TRY(launch_prep(b->device_jobs(), b->n_jobs, b->max_states, b->max_cls, b->max_ca, b->max_cls_pairs, D.tab8(), records_now, st));
   b->records_valid = records_now;
   b->used_multi[0] = false;
   // test hook: every byte of the Forward matrices is 0xFF (a NaN) in front of the fills, so that a slot a fill does not write
   // can be told from one it does (tests/test_gpu_linear_padding.py)
   if (const char* v = getenv("HX_POISON_MATRIX"))
-    if (atoi(v) != 0) HIP_TRY(hipMemsetAsync(b->d_fwd, 0xFF, sizeof(double) * (size_t)b->fwd_total, st));
+    if (atoi(v) != 0) HIP_TRY(hipMemsetAsync(b->d_fwd.as<void>(), 0xFF, sizeof(double) * (size_t)b->fwd_total, st));
   HIP_TRY(hipEventRecord(b->ev[0][0], st));
   // per-cell emission terms of the jobs without a class-pair table (general profiles).  Part of the fill:
   // the reference evaluates them inside its fill loop, so the launch is inside the timed region.
-  if (!(b->flags & HX_FORCE_GENERIC)) launch_emission_plane(b->d_jobs, b->n_jobs, b->max_eplane, Tab8{D.tab}, Tab16{D.fast_tab}, b->pol.fast && !getenv("HX_EXACT_EMISSION"), st);
+  if (!(b->flags & HX_FORCE_GENERIC)) launch_emission_plane(b->device_jobs(), b->n_jobs, b->max_eplane, D.tab8(), Tab16{D.fast_tab.as<double>()}, b->pol.fast && !getenv("HX_EXACT_EMISSION"), st);
   for (int c = 0; c < KC_COUNT; ++c) {
     const ClassRange& cr = b->cls[c];
     if (cr.n == 0) continue;
-    const DevJob* jobs = b->d_jobs_cls + cr.begin;
+    const DevJob* jobs = b->d_jobs_cls.as<DevJob>() + cr.begin;
     const bool banded = banded_class(c);
     switch (c) {
       case KC_LEAF_ROT_BANDED:
-        prefill_neg_inf(b, b->d_fwd, cr, true, st);
+        prefill_neg_inf(b, b->d_fwd.as<double>(), cr, true, st);
         if ((rc = fill_band_sweep(b, cr, 0, st)) != HX_OK) return rc;
         break;
       case KC_LEAF_LDS: case KC_LEAF_LDS_BANDED: case KC_LEAF: case KC_LEAF_BANDED: case KC_CHAIN: case KC_CHAIN_BANDED:
-        if (banded) prefill_neg_inf(b, b->d_fwd, cr, true, st);
+        if (banded) prefill_neg_inf(b, b->d_fwd.as<double>(), cr, true, st);
         if ((rc = fill_strips(b, c, 0, st)) != HX_OK) return rc;
         break;
       case KC_DAG: case KC_DAG_BANDED: {
         // general profiles: the strip pipeline; with a band it only visits in-envelope windows, the rest is -inf
         if (banded) {
-          prefill_neg_inf(b, b->d_fwd, cr, false, st);
+          prefill_neg_inf(b, b->d_fwd.as<double>(), cr, false, st);
           if (b->dag_linear) launch_dag_linear_clear(jobs, cr.n, st);
-          else launch_fill_neg_inf(b->d_agg + cr.agg_begin, cr.agg_doubles, st);
+          else launch_fill_neg_inf(b->d_agg.as<double>() + cr.agg_begin, cr.agg_doubles, st);
         }
         int multi, waves, *counters;
         if ((rc = plan_dag_multi(b, cr, 0, true, st, &multi, &waves, &counters)) != HX_OK) return rc;
         if (b->dag_linear)
-          LAUNCH_TRY(launch_forward_dag_linear(jobs, cr.n, cr.max_rows, Tab8{D.tab}, Tab16{D.log_tab}, multi, waves, counters, st));
+          LAUNCH_TRY(launch_forward_dag_linear(jobs, cr.n, cr.max_rows, D.tab8(), D.log16(), multi, waves, counters, st));
         else
-          LAUNCH_TRY(launch_forward_dag_pipe(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, multi, waves, counters, st));
+          LAUNCH_TRY(launch_forward_dag_pipe(jobs, cr.n, cr.max_rows, D.tab8(), b->pol.lse_tab(D), b->pol.fast, multi, waves, counters, st));
         break;
       }
       default:
-        LAUNCH_TRY(launch_forward_dag(jobs, cr.n, cr.max_rows, Tab8{D.tab}, st));
+        LAUNCH_TRY(launch_forward_dag(jobs, cr.n, cr.max_rows, D.tab8(), st));
     }
   }
   HIP_TRY(hipEventRecord(b->ev[0][1], st));
@@ -1470,8 +1390,8 @@ int hx_batch_backward(hx_batch* b, void* stream) {
   if (!b->d_bwd) {
     // not pre-allocated with HX_KEEP_BACKWARD: allocate the Backward matrices now and re-publish the job tables
     HIP_TRY(hipStreamSynchronize(b->last_stream));
-    if ((rc = alloc_doubles(&b->d_bwd, b->fwd_total, "Backward-matrix")) != HX_OK) return rc;
-    for (int k = 0; k < b->n_jobs; ++k) b->jobs[k].bwd = b->d_bwd + (b->jobs[k].fwd - b->d_fwd);
+    if ((rc = alloc_doubles(b->d_bwd, b->fwd_total, "Backward-matrix")) != HX_OK) return rc;
+    for (int k = 0; k < b->n_jobs; ++k) b->jobs[k].bwd = b->d_bwd.as<double>() + (b->jobs[k].fwd - b->d_fwd.as<double>());
     if ((rc = publish_jobs(b)) != HX_OK) return rc;
   } else if (st != b->last_stream) {
     // the Backward fill reads what the Forward launch prepared (and, for the posterior, follows it): order the streams
@@ -1487,28 +1407,28 @@ int hx_batch_backward(hx_batch* b, void* stream) {
   for (int c = 0; c < KC_COUNT; ++c) {
     const ClassRange& cr = b->cls[c];
     if (cr.n == 0) continue;
-    const DevJob* jobs = b->d_jobs_cls + cr.begin;
+    const DevJob* jobs = b->d_jobs_cls.as<DevJob>() + cr.begin;
     const bool banded = banded_class(c);
     switch (c) {
       case KC_LEAF_LDS: case KC_LEAF_LDS_BANDED: case KC_LEAF_ROT_BANDED: case KC_LEAF: case KC_LEAF_BANDED:
-        if (banded) prefill_neg_inf(b, b->d_bwd, cr, true, st);
+        if (banded) prefill_neg_inf(b, b->d_bwd.as<double>(), cr, true, st);
         // the rotating-row sweep in mirrored coordinates (hx_band.hip), when every pair of the class has its records
         rc = (c == KC_LEAF_ROT_BANDED && cr.bwd_band) ? fill_band_sweep(b, cr, 1, st) : fill_strips(b, c, 1, st);
         if (rc != HX_OK) return rc;
         break;
       case KC_CHAIN: case KC_CHAIN_BANDED: case KC_DAG: case KC_DAG_BANDED: {
-        if (banded) prefill_neg_inf(b, b->d_bwd, cr, false, st);
+        if (banded) prefill_neg_inf(b, b->d_bwd.as<double>(), cr, false, st);
         // the state-record formulation needs the pair's scratch planes (general-profile classes have them: five planes
         // per pair - twelve in the scaled-probability mode - of no use once the Forward fill is done: a later Forward
         // launch rebuilds its per-state packs (k_lin_pack) and, with a band, clears the planes again (k_lin_clear))
         const bool records = c == KC_DAG || c == KC_DAG_BANDED;
         int multi, waves, *counters;
         if ((rc = plan_dag_multi(b, cr, 1, records, st, &multi, &waves, &counters)) != HX_OK) return rc;
-        LAUNCH_TRY(launch_backward_dag_pipe(jobs, cr.n, cr.max_rows, Tab8{D.tab}, b->pol.lse_tab(D), b->pol.fast, records, multi, waves, st));
+        LAUNCH_TRY(launch_backward_dag_pipe(jobs, cr.n, cr.max_rows, D.tab8(), b->pol.lse_tab(D), b->pol.fast, records, multi, waves, st));
         break;
       }
       default:
-        LAUNCH_TRY(launch_backward_dag(jobs, cr.n, cr.max_rows, Tab8{D.tab}, st));
+        LAUNCH_TRY(launch_backward_dag(jobs, cr.n, cr.max_rows, D.tab8(), st));
     }
   }
   HIP_TRY(hipEventRecord(b->ev[1][1], st));
@@ -1535,7 +1455,7 @@ int hx_batch_last_kernel_ms(hx_batch* b, int32_t which, float* ms) {
 static int read_scalars(hx_batch* b, double* out, int which) {
   if (const int rc = open_reader(b, out != nullptr, nullptr, need_fill(which), "fill has not been launched")) return rc;
   HIP_TRY(hipStreamSynchronize(b->last_stream));
-  HIP_TRY(hipMemcpy(out, b->d_arena + (which == 0 ? b->lp_end_off : b->lp_start_off), sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, b->d_arena.as<char>() + (which == 0 ? b->lp_end_off : b->lp_start_off), sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost));
   return HX_OK;
 }
 
@@ -1643,19 +1563,20 @@ int hx_batch_read_matrix_async(hx_batch* b, int32_t job, int32_t which, double* 
     if (!D.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking));
     b->copy_stream = D.copy_stream;
   }
-  if (b->copied[which].empty()) b->copied[which].assign((size_t)b->n_jobs, nullptr);
-  hipEvent_t& e = b->copied[which][job];
-  if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (b->copied[which].empty()) b->copied[which].resize((size_t)b->n_jobs);
+  DevEvents<1>& e = b->copied[which][job];
+  if (!e.create(hipEventDisableTiming))       // (the message of the HIP_TRY that stood here, kept word for word)
+    return fail(HX_ERR_HIP, "hipEventCreateWithFlags(&e, hipEventDisableTiming) failed: %s", hipGetErrorString(hipGetLastError()));
   HIP_TRY(hipMemcpyAsync(out, matrix_of(b, job, which), sizeof(double) * (size_t)b->jobs[job].matrix_doubles, hipMemcpyDeviceToHost, b->copy_stream));
-  HIP_TRY(hipEventRecord(e, b->copy_stream));
+  HIP_TRY(hipEventRecord(e[0], b->copy_stream));
   return HX_OK;
 }
 
 int hx_batch_wait_read(hx_batch* b, int32_t job, int32_t which) {
   if (const int rc = check_reader(b, which >= 0 && which <= 1, &job)) return rc;
-  if (b->copied[which].empty() || !b->copied[which][job]) return fail(HX_ERR_STATE, "no asynchronous read of job %d was started", job);
+  if (b->copied[which].empty() || !b->copied[which][job][0]) return fail(HX_ERR_STATE, "no asynchronous read of job %d was started", job);
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
-  HIP_TRY(hipEventSynchronize(b->copied[which][job]));
+  HIP_TRY(hipEventSynchronize(b->copied[which][job][0]));
   return HX_OK;
 }
 
@@ -1667,16 +1588,17 @@ struct hx_quick_batch {
   int n_jobs = 0;
   std::vector<DevQuick> jobs;
   std::vector<hx_layout> layouts;
-  DevQuick* d_jobs = nullptr;
-  char* d_arena = nullptr;
-  double* d_cells = nullptr;
+  DevBuf d_jobs;                    // [n_jobs] DevQuick
+  DevBuf d_arena;                   // the inputs' image (hx_arena.h), the rows' best cells, the results
+  DevBuf d_cells;                   // doubles
   int max_rows = 0, max_cols = 0;
   bool all_full = true;
   bool done = false;
   int64_t total_cells = 0;
   hipStream_t last_stream = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  DevEvents<2> ev;
   size_t res_off = 0, xy_off = 0;
+  ~hx_quick_batch() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }      // (as ~hx_batch)
 };
 
 static int quick_create_impl(int device, const hx_quick_job* jobs, int32_t n_jobs, hx_quick_batch** out) {
@@ -1686,16 +1608,15 @@ static int quick_create_impl(int device, const hx_quick_job* jobs, int32_t n_job
     return fail(HX_ERR_NOT_INITIALIZED, "hx_init has not been called for device %d", device);
   if (!jobs || n_jobs <= 0) return fail(HX_ERR_INVALID_ARG, "no jobs");
   HIP_TRY(hipSetDevice(device));
-  hx_quick_batch* b = new (std::nothrow) hx_quick_batch;
+  std::unique_ptr<hx_quick_batch> owner(new (std::nothrow) hx_quick_batch);      // (as in batch_create_impl)
+  hx_quick_batch* const b = owner.get();
   if (!b) return fail(HX_ERR_OUT_OF_MEMORY, "out of host memory");
   b->device = device;
   b->n_jobs = n_jobs;
-  b->jobs.resize(n_jobs);
+  b->jobs.resize(n_jobs);           // (not resized again: the arena keeps the addresses of the jobs' pointer members)
   b->layouts.resize(n_jobs);
-  struct Off { size_t xtok, ytok, submat, env, best, bestj, cols; bool has_env; };
-  std::vector<Off> offs(n_jobs);
   std::vector<int64_t> cell_off(n_jobs);
-  Arena ar;
+  Arena ar(256);
   int64_t cells_total = 0;
   int rc = HX_OK;
   for (int k = 0; k < n_jobs && rc == HX_OK; ++k) {
@@ -1707,13 +1628,12 @@ static int quick_create_impl(int device, const hx_quick_job* jobs, int32_t n_job
     for (int p = 0; p < q.y_len && rc == HX_OK; ++p)
       if (q.y_tok[p] >= q.alph_size) rc = fail(HX_ERR_RANGE, "job %d: y token %d out of range", k, q.y_tok[p]);
     if (rc != HX_OK) break;
-    Off& o = offs[k];
-    o.xtok = ar.put(q.x_tok, sizeof(int32_t) * q.x_len);
-    o.ytok = ar.put(q.y_tok, sizeof(int32_t) * q.y_len);
-    o.submat = ar.put(q.submat, sizeof(double) * q.alph_size * q.alph_size);
-    o.has_env = q.diagonals != nullptr;
-    o.env = 0;
-    if (o.has_env) {
+    DevQuick& J = b->jobs[k];
+    memset(&J, 0, sizeof(J));       // (in_env stays null without diagonals: the full envelope)
+    ar.put(J.xtok, q.x_tok, (size_t)q.x_len);
+    ar.put(J.ytok, q.y_tok, (size_t)q.y_len);
+    ar.put(J.submat, q.submat, (size_t)q.alph_size * q.alph_size);
+    if (q.diagonals) {
       std::vector<uint8_t> bits((size_t)q.x_len + q.y_len + 1, 0);
       for (int d = 0; d < q.n_diagonals; ++d) {
         const int64_t idx = (int64_t)q.diagonals[d] + q.y_len;
@@ -1721,13 +1641,11 @@ static int quick_create_impl(int device, const hx_quick_job* jobs, int32_t n_job
         bits[(size_t)idx] = 1;
       }
       if (rc != HX_OK) break;
-      o.env = ar.put(bits.data(), bits.size());
+      ar.put(J.in_env, bits.data(), bits.size());
       b->all_full = false;
     }
-    o.best = ar.reserve(sizeof(double) * q.x_len);
-    o.bestj = ar.reserve(sizeof(int32_t) * q.x_len);
-    DevQuick& J = b->jobs[k];
-    memset(&J, 0, sizeof(J));
+    ar.point(J.best_score, ar.reserve(sizeof(double) * q.x_len));
+    ar.point(J.best_j, ar.reserve(sizeof(int32_t) * q.x_len));
     J.xlen = q.x_len; J.ylen = q.y_len; J.alph = q.alph_size;
     J.n_strips = (q.x_len + HX_STRIP - 1) / HX_STRIP;
     // the three states of a step pair adjacent (a wavefront writes 3 KiB contiguous per iteration)
@@ -1746,49 +1664,35 @@ static int quick_create_impl(int device, const hx_quick_job* jobs, int32_t n_job
     if (q.x_len > b->max_rows) b->max_rows = q.x_len;
     if (q.y_len > b->max_cols) b->max_cols = q.y_len;
   }
-  if (rc != HX_OK) { delete b; return rc; }
+  if (rc != HX_OK) return rc;
   // per-column constants of the pairs in global memory when the longest y does not fit the kernel's LDS tables
-  for (int k = 0; k < n_jobs; ++k)
-    offs[k].cols = b->max_cols > 7000 ? ar.reserve((sizeof(double) * 2 + sizeof(int32_t)) * (size_t)jobs[k].y_len + 16) : 0;
+  for (int k = 0; k < n_jobs && b->max_cols > 7000; ++k)
+    ar.point(b->jobs[k].col_scratch, ar.reserve((sizeof(double) * 2 + sizeof(int32_t)) * (size_t)jobs[k].y_len + 16));
   // scores and end coordinates of all pairs, contiguous: one copy back per batch
   b->res_off = ar.reserve(sizeof(double) * n_jobs);
   b->xy_off = ar.reserve(sizeof(int32_t) * 2 * n_jobs);
-  auto cleanup = [&](int code) { hx_quick_batch_destroy(b); return code; };
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_arena), ar.host.size() + 256) != hipSuccess)
-    return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %zu input bytes failed", ar.host.size()));
-  if (hipMemcpy(b->d_arena, ar.host.data(), ar.host.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(HX_ERR_HIP, "input upload failed"));
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_cells), sizeof(double) * (size_t)cells_total) != hipSuccess)
-    return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld matrix bytes failed", (long long)(cells_total * 8)));
+  if (!b->d_arena.alloc(ar.host.size() + 256)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %zu input bytes failed", ar.host.size());
+  if (hipMemcpy(b->d_arena.as<void>(), ar.host.data(), ar.host.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(HX_ERR_HIP, "input upload failed");
+  if (!b->d_cells.alloc(sizeof(double) * (size_t)cells_total)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of %lld matrix bytes failed", (long long)(cells_total * 8));
+  char* base = b->d_arena.as<char>();
+  ar.bind(base);
   for (int k = 0; k < n_jobs; ++k) {
     DevQuick& J = b->jobs[k];
-    const Off& o = offs[k];
-    char* base = b->d_arena;
-    J.xtok = reinterpret_cast<int32_t*>(base + o.xtok);
-    J.ytok = reinterpret_cast<int32_t*>(base + o.ytok);
-    J.submat = reinterpret_cast<double*>(base + o.submat);
-    J.in_env = o.has_env ? reinterpret_cast<uint8_t*>(base + o.env) : nullptr;
-    J.col_scratch = b->max_cols > 7000 ? reinterpret_cast<double*>(base + o.cols) : nullptr;
-    J.best_score = reinterpret_cast<double*>(base + o.best);
-    J.best_j = reinterpret_cast<int32_t*>(base + o.bestj);
     J.result = reinterpret_cast<double*>(base + b->res_off) + k;
     J.xy_end = reinterpret_cast<int32_t*>(base + b->xy_off) + 2 * k;
-    J.cells = b->d_cells + cell_off[k];
+    J.cells = b->d_cells.as<double>() + cell_off[k];
   }
-  if (hipMalloc(reinterpret_cast<void**>(&b->d_jobs), sizeof(DevQuick) * n_jobs) != hipSuccess)
-    return cleanup(fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of job table failed"));
-  if (hipMemcpy(b->d_jobs, b->jobs.data(), sizeof(DevQuick) * n_jobs, hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail(HX_ERR_HIP, "job table upload failed"));
-  for (int e = 0; e < 2; ++e)
-    if (hipEventCreate(&b->ev[e]) != hipSuccess) return cleanup(fail(HX_ERR_HIP, "hipEventCreate failed"));
-  *out = b;
+  if (!b->d_jobs.alloc(sizeof(DevQuick) * n_jobs)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc of job table failed");
+  if (hipMemcpy(b->d_jobs.as<void>(), b->jobs.data(), sizeof(DevQuick) * n_jobs, hipMemcpyHostToDevice) != hipSuccess) return fail(HX_ERR_HIP, "job table upload failed");
+  if (!b->ev.create()) return fail(HX_ERR_HIP, "hipEventCreate failed");
+  *out = owner.release();
   return HX_OK;
 }
 
 int hx_quick_batch_create_on(int device, const hx_quick_job* jobs, int32_t n_jobs, hx_quick_batch** out) {
   try {
     return quick_create_impl(device, jobs, n_jobs, out);
-  } catch (const std::bad_alloc&) {
+  } catch (const std::bad_alloc&) {         // (nothing leaks: quick_create_impl's unique_ptr has released the batch)
     if (out) *out = nullptr;
     return fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed while building the batch");
   }
@@ -1799,25 +1703,14 @@ int hx_quick_batch_create(const hx_quick_job* jobs, int32_t n_jobs, hx_quick_bat
   return hx_quick_batch_create_on(g_device, jobs, n_jobs, out);
 }
 
-int hx_quick_batch_destroy(hx_quick_batch* b) {
-  if (!b) return HX_OK;
-  (void)hipSetDevice(b->device);
-  (void)hipDeviceSynchronize();
-  for (int e = 0; e < 2; ++e)
-    if (b->ev[e]) (void)hipEventDestroy(b->ev[e]);
-  if (b->d_jobs) (void)hipFree(b->d_jobs);
-  if (b->d_arena) (void)hipFree(b->d_arena);
-  if (b->d_cells) (void)hipFree(b->d_cells);
-  delete b;
-  return HX_OK;
-}
+int hx_quick_batch_destroy(hx_quick_batch* b) { delete b; return HX_OK; }
 
 int hx_quick_batch_run(hx_quick_batch* b, void* stream) {
   if (!b) return fail(HX_ERR_INVALID_ARG, "batch is null");
   if (hipSetDevice(b->device) != hipSuccess) return fail(HX_ERR_HIP, "hipSetDevice(%d) failed", b->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipEventRecord(b->ev[0], st));
-  LAUNCH_TRY(launch_quickalign(b->d_jobs, b->n_jobs, b->max_rows, b->max_cols, b->all_full, st));
+  LAUNCH_TRY(launch_quickalign(b->d_jobs.as<DevQuick>(), b->n_jobs, b->max_rows, b->max_cols, b->all_full, st));
   HIP_TRY(hipEventRecord(b->ev[1], st));
   HIP_TRY(hipGetLastError());
   b->done = true;
@@ -1830,9 +1723,9 @@ int hx_quick_batch_results(hx_quick_batch* b, double* score, int32_t* x_end, int
   if (!b->done) return fail(HX_ERR_STATE, "hx_quick_batch_run has not been launched");
   if (hipSetDevice(b->device) != hipSuccess) return fail(HX_ERR_HIP, "hipSetDevice(%d) failed", b->device);
   HIP_TRY(hipStreamSynchronize(b->last_stream));
-  if (score) HIP_TRY(hipMemcpy(score, b->d_arena + b->res_off, sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost));
+  if (score) HIP_TRY(hipMemcpy(score, b->d_arena.as<char>() + b->res_off, sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost));
   std::vector<int32_t> xy(2 * (size_t)b->n_jobs);
-  HIP_TRY(hipMemcpy(xy.data(), b->d_arena + b->xy_off, sizeof(int32_t) * xy.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(xy.data(), b->d_arena.as<char>() + b->xy_off, sizeof(int32_t) * xy.size(), hipMemcpyDeviceToHost));
   for (int k = 0; k < b->n_jobs; ++k) {
     if (x_end) x_end[k] = xy[2 * k];
     if (y_end) y_end[k] = xy[2 * k + 1];
@@ -1884,29 +1777,22 @@ int hx_host_free(void* p) {
   return HX_OK;
 }
 
+int64_t hx_live_allocations(void) { return g_live_allocations.load(std::memory_order_relaxed); }
+
 int hx_batch_read_cells(hx_batch* b, int32_t job, int32_t which, const int32_t* ij, int64_t n, double* out) {
   if (const int rc = check_reader(b, out && ij && n >= 0 && which >= 0 && which <= 1, &job, need_fill(which), "fill has not been launched"))
     return rc;
   if (n == 0) return HX_OK;
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
-  int32_t* d_ij = nullptr;
-  double* d_out = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_ij), sizeof(int32_t) * 2 * n));
-  if (hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(double) * 5 * n) != hipSuccess) {
-    (void)hipFree(d_ij);
-    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc failed");
-  }
-  int rc = HX_OK;
-  if (hipMemcpy(d_ij, ij, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) rc = fail(HX_ERR_HIP, "upload failed");
-  if (rc == HX_OK) {
-    launch_gather_cells(b->d_jobs, job, matrix_of(b, job, which), which, d_ij, n, d_out, b->last_stream);
-    if (hipStreamSynchronize(b->last_stream) != hipSuccess ||
-        hipMemcpy(out, d_out, sizeof(double) * 5 * n, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(HX_ERR_HIP, "cell gather failed");
-  }
-  (void)hipFree(d_ij);
-  (void)hipFree(d_out);
-  return rc;
+  DevBuf d_ij, d_out;
+  if (!d_ij.alloc(sizeof(int32_t) * 2 * n)) return alloc_failed("hipMalloc(reinterpret_cast<void**>(&d_ij), sizeof(int32_t) * 2 * n)");
+  if (!d_out.alloc(sizeof(double) * 5 * n)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+  if (hipMemcpy(d_ij.as<void>(), ij, sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice) != hipSuccess) return fail(HX_ERR_HIP, "upload failed");
+  launch_gather_cells(b->device_jobs(), job, matrix_of(b, job, which), which, d_ij.as<int32_t>(), n, d_out.as<double>(), b->last_stream);
+  if (hipStreamSynchronize(b->last_stream) != hipSuccess ||
+      hipMemcpy(out, d_out.as<void>(), sizeof(double) * 5 * n, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(HX_ERR_HIP, "cell gather failed");
+  return HX_OK;
 }
 
 // Device-side ForwardMatrix::bestTrace for every job of the batch (hx_trace.hip).
@@ -1917,27 +1803,24 @@ int hx_batch_best_trace(hx_batch* b, hx_trace_cell* cells, int64_t cap, int32_t*
   // device buffers and the page-locked staging buffer are kept with the batch (a host mirror asks once per fill batch,
   // a benchmark many times)
   if (cap > b->trace_cap) {
-    if (b->d_trace) (void)hipFree(b->d_trace);
-    if (b->d_trace_n) (void)hipFree(b->d_trace_n);
-    if (b->h_trace) (void)hipHostFree(b->h_trace);
-    b->d_trace = nullptr; b->d_trace_n = nullptr; b->h_trace = nullptr; b->trace_cap = 0;
+    b->d_trace.reset(); b->d_trace_n.reset(); b->h_trace.reset(); b->trace_cap = 0;
     // [n][cap][3] as walked (END cell first) + the same amount for the compacted, start-first copy; [2n] lengths + offsets
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_trace), sizeof(int32_t) * 6 * (size_t)cap * n) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&b->d_trace_n), sizeof(int64_t) * 3 * (size_t)n) != hipSuccess ||      // lengths, offsets, near-tie flags
-        hipHostMalloc(&b->h_trace, sizeof(int32_t) * 3 * (size_t)cap * n, hipHostMallocDefault) != hipSuccess)
+    if (!b->d_trace.alloc(sizeof(int32_t) * 6 * (size_t)cap * n) ||
+        !b->d_trace_n.alloc(sizeof(int64_t) * 3 * (size_t)n) ||      // lengths, offsets, near-tie flags
+        !b->h_trace.alloc(sizeof(int32_t) * 3 * (size_t)cap * n, hipHostMallocDefault))
       return fail(HX_ERR_OUT_OF_MEMORY, "allocating %zu path bytes failed", sizeof(int32_t) * 9 * (size_t)cap * n);
     b->trace_cap = cap;
   }
-  int32_t* d_paths = b->d_trace;
-  int32_t* d_out = b->d_trace + 3 * (size_t)cap * n;
-  int32_t* d_n = reinterpret_cast<int32_t*>(b->d_trace_n);
-  int64_t* d_off = b->d_trace_n + n;
-  int32_t* d_ties = reinterpret_cast<int32_t*>(b->d_trace_n + 2 * (size_t)n);
+  int32_t* d_paths = b->d_trace.as<int32_t>();
+  int32_t* d_out = d_paths + 3 * (size_t)cap * n;
+  int32_t* d_n = b->d_trace_n.as<int32_t>();
+  int64_t* d_off = b->d_trace_n.as<int64_t>() + n;
+  int32_t* d_ties = reinterpret_cast<int32_t*>(b->d_trace_n.as<int64_t>() + 2 * (size_t)n);
   b->trace_ties_valid = false;
   hipStream_t st = b->last_stream;
   // the per-cell emission plane is only filled by the strip pipelines (hx_batch_forward)
   ensure_state_records(b, st);
-  launch_best_trace(b->d_jobs, n, d_paths, cap, d_n, Tab8{g_dev[b->device].tab}, !(b->flags & HX_FORCE_GENERIC), d_ties, st);
+  launch_best_trace(b->device_jobs(), n, d_paths, cap, d_n, g_dev[b->device].tab8(), !(b->flags & HX_FORCE_GENERIC), d_ties, st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
       hipMemcpy(n_cells, d_n, sizeof(int32_t) * n, hipMemcpyDeviceToHost) != hipSuccess)
     return fail(HX_ERR_HIP, "best-trace kernel failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1953,9 +1836,9 @@ int hx_batch_best_trace(hx_batch* b, hx_trace_cell* cells, int64_t cap, int32_t*
   HIP_TRY(hipMemcpy(d_off, off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice));
   launch_reverse_paths(d_paths, cap, d_n, d_off, d_out, n, st);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(b->h_trace, d_out, sizeof(int32_t) * 3 * (size_t)off[n], hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(b->h_trace.as<void>(), d_out, sizeof(int32_t) * 3 * (size_t)off[n], hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const hx_trace_cell* src = static_cast<const hx_trace_cell*>(b->h_trace);
+  const hx_trace_cell* src = b->h_trace.as<const hx_trace_cell>();
   for (int k = 0; k < n; ++k)
     if (n_cells[k] > 0) memcpy(cells + (size_t)cap * k, src + off[k], sizeof(hx_trace_cell) * (size_t)n_cells[k]);
   return HX_OK;
@@ -1965,7 +1848,7 @@ int hx_batch_best_trace_ties(hx_batch* b, int32_t* near_tie) {
   if (const int rc = check_reader(b, near_tie != nullptr, nullptr)) return rc;
   if (!b->trace_ties_valid) return fail(HX_ERR_STATE, "hx_batch_best_trace_ties needs a previous hx_batch_best_trace");
   { const int rc_ = use_device(b); if (rc_ != HX_OK) return rc_; }
-  HIP_TRY(hipMemcpy(near_tie, reinterpret_cast<const int32_t*>(b->d_trace_n + 2 * (size_t)b->n_jobs), sizeof(int32_t) * b->n_jobs, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(near_tie, reinterpret_cast<const int32_t*>(b->d_trace_n.as<int64_t>() + 2 * (size_t)b->n_jobs), sizeof(int32_t) * b->n_jobs, hipMemcpyDeviceToHost));
   return HX_OK;
 }
 
@@ -1974,25 +1857,19 @@ int hx_batch_sample_traces(hx_batch* b, int32_t job, int32_t n_walks, const doub
   if (const int rc = open_reader(b, uniforms && cells && n_cells && draws_used && n_walks >= 1 && n_uniforms >= 0 && cap >= 1, &job,
                                   NEED_FORWARD, "hx_batch_sample_traces needs a previous hx_batch_forward"))
     return rc;
-  struct Dev {                                       // released on every way out
-    void* p = nullptr;
-    ~Dev() { if (p) (void)hipFree(p); }
-  } d_u, d_paths, d_n, d_draws;
+  DevBuf d_u, d_paths, d_n, d_draws;
   const size_t path_ints = 3 * (size_t)cap * (size_t)n_walks;
-  if (hipMalloc(&d_u.p, sizeof(double) * (size_t)(n_uniforms > 0 ? n_uniforms : 1)) != hipSuccess ||
-      hipMalloc(&d_paths.p, sizeof(int32_t) * path_ints) != hipSuccess ||
-      hipMalloc(&d_n.p, sizeof(int32_t) * (size_t)n_walks) != hipSuccess ||
-      hipMalloc(&d_draws.p, sizeof(int64_t) * (size_t)n_walks) != hipSuccess)
+  if (!d_u.alloc(sizeof(double) * (size_t)(n_uniforms > 0 ? n_uniforms : 1)) || !d_paths.alloc(sizeof(int32_t) * path_ints) ||
+      !d_n.alloc(sizeof(int32_t) * (size_t)n_walks) || !d_draws.alloc(sizeof(int64_t) * (size_t)n_walks))
     return fail(HX_ERR_OUT_OF_MEMORY, "allocating the buffers of %d sampled walks failed", n_walks);
   hipStream_t st = b->last_stream;
-  HIP_TRY(hipMemcpyAsync(d_u.p, uniforms, sizeof(double) * (size_t)n_uniforms, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_u.as<void>(), uniforms, sizeof(double) * (size_t)n_uniforms, hipMemcpyHostToDevice, st));
   ensure_state_records(b, st);
-  launch_sample_traces(b->d_jobs, job, n_walks, static_cast<const double*>(d_u.p), n_uniforms, static_cast<int32_t*>(d_paths.p), cap,
-                       static_cast<int32_t*>(d_n.p), static_cast<int64_t*>(d_draws.p), Tab8{g_dev[b->device].tab},
-                       !(b->flags & HX_FORCE_GENERIC), st);
+  launch_sample_traces(b->device_jobs(), job, n_walks, d_u.as<const double>(), n_uniforms, d_paths.as<int32_t>(), cap, d_n.as<int32_t>(),
+                       d_draws.as<int64_t>(), g_dev[b->device].tab8(), !(b->flags & HX_FORCE_GENERIC), st);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(n_cells, d_n.p, sizeof(int32_t) * (size_t)n_walks, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(draws_used, d_draws.p, sizeof(int64_t) * (size_t)n_walks, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(n_cells, d_n.as<void>(), sizeof(int32_t) * (size_t)n_walks, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(draws_used, d_draws.as<void>(), sizeof(int64_t) * (size_t)n_walks, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   // the kernel walks from the END cell backwards; the reference's Path starts at the start cell
   std::vector<int32_t> raw;
@@ -2000,7 +1877,7 @@ int hx_batch_sample_traces(hx_batch* b, int32_t job, int32_t n_walks, const doub
     const int n = n_cells[w];
     if (n <= 0) continue;
     raw.resize(3 * (size_t)n);
-    HIP_TRY(hipMemcpy(raw.data(), static_cast<const int32_t*>(d_paths.p) + 3 * (size_t)cap * w, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(raw.data(), d_paths.as<const int32_t>() + 3 * (size_t)cap * w, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToHost));
     hx_trace_cell* dst = cells + (size_t)cap * w;
     for (int c = 0; c < n; ++c) {
       const int32_t* t = &raw[3 * (size_t)(n - 1 - c)];
@@ -2015,22 +1892,20 @@ int hx_batch_indel_counts(hx_batch* b, int32_t job, const double* branch_times, 
                                   "hx_batch_indel_counts needs the Forward and the Backward fill"))
     return rc;
   hipStream_t st = b->last_stream;
-  double* d = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&d), 12 * sizeof(double)) != hipSuccess) return fail(HX_ERR_OUT_OF_MEMORY, "device allocation failed");
-  int rc = HX_OK;
+  DevBuf buf;
+  if (!buf.alloc(12 * sizeof(double))) return fail(HX_ERR_OUT_OF_MEMORY, "device allocation failed");
+  double* const d = buf.as<double>();
   double host[12];
   for (int k = 0; k < 6; ++k) { host[k] = branch_times[k]; host[6 + k] = 0.; }
-  if (hipMemcpyAsync(d, host, sizeof(host), hipMemcpyHostToDevice, st) != hipSuccess) rc = HX_ERR_HIP;
-  if (rc == HX_OK) {
+  bool ok = hipMemcpyAsync(d, host, sizeof(host), hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) {
     const DevJob& J = b->jobs[job];
     ensure_state_records(b, st);
-    launch_indel_counts(b->d_jobs, job, d, d + 6, (int64_t)J.n_rows * J.n_cols, Tab8{g_dev[b->device].tab}, !(b->flags & HX_FORCE_GENERIC), st);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d + 6, 6 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-      rc = HX_ERR_HIP;
+    launch_indel_counts(b->device_jobs(), job, d, d + 6, (int64_t)J.n_rows * J.n_cols, g_dev[b->device].tab8(), !(b->flags & HX_FORCE_GENERIC), st);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(out, d + 6, 6 * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+         hipStreamSynchronize(st) == hipSuccess;
   }
-  (void)hipFree(d);
-  return rc == HX_OK ? HX_OK : fail(rc, "indel-count kernel failed: %s", hipGetErrorString(hipGetLastError()));
+  return ok ? HX_OK : fail(HX_ERR_HIP, "indel-count kernel failed: %s", hipGetErrorString(hipGetLastError()));
 }
 
 int hx_batch_event_counts(hx_batch* b, int32_t job, const double* x_counts, const double* y_counts, const double* branch_times, double* out,
@@ -2047,22 +1922,20 @@ int hx_batch_event_counts(hx_batch* b, int32_t job, const double* x_counts, cons
   const size_t o_xp = 12, o_yp = o_xp + n_x, o_xc = o_yp + n_y, o_yc = o_xc + 6 * n_x, o_part = o_yc + 6 * n_y;
   const size_t total = o_part + 12 * (size_t)grid;
   if (total > b->events_doubles) {                 // (a count / fit loop calls this per root and iteration: no per-call hipFree)
-    if (b->d_events) (void)hipFree(b->d_events);
-    b->d_events = nullptr;
-    b->events_doubles = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_events), sizeof(double) * total) != hipSuccess)
+    b->d_events.reset(); b->events_doubles = 0;
+    if (!b->d_events.alloc(sizeof(double) * total))
       return fail(HX_ERR_OUT_OF_MEMORY, "device allocation of %zu event-count doubles failed", total);
     b->events_doubles = total;
   }
-  double* const d = b->d_events;
+  double* const d = b->d_events.as<double>();
   hipStream_t st = b->last_stream;
   HIP_TRY(hipMemsetAsync(d, 0, sizeof(double) * o_xc, st));
   HIP_TRY(hipMemcpyAsync(d, branch_times, 6 * sizeof(double), hipMemcpyHostToDevice, st));
   if (x_counts && n_x) HIP_TRY(hipMemcpyAsync(d + o_xc, x_counts, 6 * n_x * sizeof(double), hipMemcpyHostToDevice, st));
   if (y_counts && n_y) HIP_TRY(hipMemcpyAsync(d + o_yc, y_counts, 6 * n_y * sizeof(double), hipMemcpyHostToDevice, st));
   ensure_state_records(b, st);
-  launch_event_counts(b->d_jobs, job, d, ti.x_in_idx, ti.y_in_idx, d + o_xp, d + o_yp, x_counts ? d + o_xc : nullptr, xT,
-                      y_counts ? d + o_yc : nullptr, yT, d + o_part, grid, d + 6, Tab8{g_dev[b->device].tab},
+  launch_event_counts(b->device_jobs(), job, d, ti.x_in_idx, ti.y_in_idx, d + o_xp, d + o_yp, x_counts ? d + o_xc : nullptr, xT,
+                      y_counts ? d + o_yc : nullptr, yT, d + o_part, grid, d + 6, g_dev[b->device].tab8(),
                       !(b->flags & HX_FORCE_GENERIC), st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, d + 6, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2078,7 +1951,7 @@ int hx_batch_read_prepared(hx_batch* b, int32_t job, double* subx, double* suby,
   if (const int rc = open_reader(b, true, &job, NEED_FORWARD, "hx_batch_forward has not been launched")) return rc;
   if ((subx || suby) && !b->sub_scattered) {
     // the fills use per-class tables; the per-state leftMultiply rows are produced when somebody asks for them
-    launch_scatter_sub(b->d_jobs, b->n_jobs, b->max_states, b->last_stream);
+    launch_scatter_sub(b->device_jobs(), b->n_jobs, b->max_states, b->last_stream);
     HIP_TRY(hipGetLastError());
     b->sub_scattered = true;
   }
@@ -2099,31 +1972,20 @@ int hx_batch_posterior_scan(hx_batch* b, int32_t job, double min_post_prob, hx_c
     return rc;
   static_assert(sizeof(PostCell) == sizeof(hx_cell), "hx_cell layout");
   const double thr = std::log(min_post_prob);   // host libm, as reference src/forward.cpp:1304
-  PostCell* d_out = nullptr;
-  unsigned long long* d_cnt = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(unsigned long long)));
-  if (cap > 0 && hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(PostCell) * cap) != hipSuccess) {
-    (void)hipFree(d_cnt);
-    return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc failed");
-  }
-  int rc = HX_OK;
+  DevBuf b_cnt, b_out;
+  if (!b_cnt.alloc(sizeof(unsigned long long))) return alloc_failed("hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(unsigned long long))");
+  if (cap > 0 && !b_out.alloc(sizeof(PostCell) * cap)) return fail(HX_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+  unsigned long long* const d_cnt = b_cnt.as<unsigned long long>();
   unsigned long long cnt = 0;
-  if (hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), b->last_stream) != hipSuccess) rc = fail(HX_ERR_HIP, "memset failed");
-  if (rc == HX_OK) {
-    launch_posterior_scan(b->d_jobs, job, thr, d_out, (unsigned long long)cap, d_cnt, b->last_stream);
-    if (hipStreamSynchronize(b->last_stream) != hipSuccess ||
-        hipMemcpy(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(HX_ERR_HIP, "posterior scan failed: %s", hipGetErrorString(hipGetLastError()));
-  }
-  if (rc == HX_OK) {
-    *n_out = (int64_t)cnt;
-    const int64_t n_copy = (int64_t)cnt < cap ? (int64_t)cnt : cap;
-    if (n_copy > 0 && hipMemcpy(out, d_out, sizeof(PostCell) * n_copy, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(HX_ERR_HIP, "result download failed");
-  }
-  (void)hipFree(d_cnt);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  if (hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), b->last_stream) != hipSuccess) return fail(HX_ERR_HIP, "memset failed");
+  launch_posterior_scan(b->device_jobs(), job, thr, b_out.as<PostCell>(), (unsigned long long)cap, d_cnt, b->last_stream);
+  if (hipStreamSynchronize(b->last_stream) != hipSuccess || hipMemcpy(&cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(HX_ERR_HIP, "posterior scan failed: %s", hipGetErrorString(hipGetLastError()));
+  *n_out = (int64_t)cnt;
+  const int64_t n_copy = (int64_t)cnt < cap ? (int64_t)cnt : cap;
+  if (n_copy > 0 && hipMemcpy(out, b_out.as<void>(), sizeof(PostCell) * n_copy, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(HX_ERR_HIP, "result download failed");
+  return HX_OK;
 }
 
 }  // extern "C"

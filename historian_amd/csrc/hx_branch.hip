@@ -90,7 +90,7 @@ struct BranchCell {
 
 // one job of the ABI -> its device job and its arrays in the arena; `reserved`: the per-position inputs have no host copy,
 // the device fills their space
-int fill_job(DevBranch& J, const hx_branch_job& j, PairArena& a, const bool reserved) {
+int fill_job(DevBranch& J, const hx_branch_job& j, Arena& a, const bool reserved) {
   if (j.x_len >= 64 * HXBR_MAX_STRIPS)
     return api_fail(HX_ERR_RANGE, "hx_branch_batch_create: a parent profile of more than 65535 positions");
   if (j.x_len < 0 || j.y_len < 0 || j.components < 1 || j.alphabet < 1 ||
@@ -111,7 +111,7 @@ int fill_job(DevBranch& J, const hx_branch_job& j, PairArena& a, const bool rese
     a.put(J.y_sub, j.y_sub, (size_t)j.y_len * J.CA);
     a.put(J.y_emit, j.y_emit, (size_t)j.y_len);
   }
-  a.put_env(J, j.x_env, j.y_env, !getenv("HX_BRANCH_NO_WINDOWS"));
+  put_env(a, J, j.x_env, j.y_env, !getenv("HX_BRANCH_NO_WINDOWS"));
   return HX_OK;
 }
 
@@ -128,7 +128,7 @@ long long hx::branch_max_x_len() { return 64LL * HXBR_MAX_STRIPS; }
 
 int hx::branch_batch_reserve(const hx_branch_job* jobs, const double* const* log_sub, const double* const* log_ins, const int32_t n_jobs,
                              hx_branch_batch** out, BranchInputs* where) {
-  const int rc = hx_branch_batch::create(jobs, n_jobs, out, [&](DevBranch& J, const hx_branch_job& j, PairArena& a) {
+  const int rc = hx_branch_batch::create(jobs, n_jobs, out, [&](DevBranch& J, const hx_branch_job& j, Arena& a) {
     if (const int bad = fill_job(J, j, a, true)) return bad;
     BranchInputs& w = where[&j - jobs];
     a.put(w.log_sub, log_sub[&j - jobs], (size_t)j.components * j.alphabet * j.alphabet);
@@ -150,7 +150,7 @@ extern "C" {
 int hx_branch_batch_destroy(hx_branch_batch* b) { delete b; return HX_OK; }
 
 int hx_branch_batch_create(const hx_branch_job* jobs, int32_t n_jobs, hx_branch_batch** out) {
-  return hx_branch_batch::create(jobs, n_jobs, out, [](DevBranch& J, const hx_branch_job& j, PairArena& a) { return fill_job(J, j, a, false); });
+  return hx_branch_batch::create(jobs, n_jobs, out, [](DevBranch& J, const hx_branch_job& j, Arena& a) { return fill_job(J, j, a, false); });
 }
 
 int hx_branch_batch_read_inputs(hx_branch_batch* b, int32_t job, double* x_pwm, double* y_sub, double* y_emit) {

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/historian_hip.h"
+#include "hx_devmem.h"
 
 namespace hx {
 namespace {
@@ -300,18 +301,6 @@ __global__ void __launch_bounds__(64) k_distance_nll(DistModel m, const int* cou
 thread_local float g_dist_ms = 0.f;
 thread_local long long g_dist_products = 0;
 
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
-};
-
-struct Events {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~Events() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-  bool create() { for (auto& x : e) if (hipEventCreate(&x) != hipSuccess) return false; return true; }
-};
-
 const std::vector<double>& shrink_table() {
   static const std::vector<double> tab = [] {
     std::vector<double> v(kShrinkEntries);
@@ -344,21 +333,21 @@ namespace {
 
 // the model's arrays on the device; false with `rc` set on failure
 struct DeviceModel {
-  Buf rate, weight, shrink;
+  DevBuf rate, weight, shrink;
   DistModel m;
   int upload(const hx_distance_model* hm, hipStream_t st) {
     const int A = hm->alph_size, C = hm->n_components;
     const size_t AA = (size_t)A * A;
     if (!rate.alloc(C * AA * sizeof(double)) || !weight.alloc(C * sizeof(double)) || !shrink.alloc(kShrinkEntries * sizeof(double)))
       return HX_ERR_OUT_OF_MEMORY;
-    if (hipMemcpyAsync(rate.p, hm->sub_rate, C * AA * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(weight.p, hm->cpt_weight, C * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(shrink.p, shrink_table().data(), kShrinkEntries * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(rate.as<void>(), hm->sub_rate, C * AA * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(weight.as<void>(), hm->cpt_weight, C * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(shrink.as<void>(), shrink_table().data(), kShrinkEntries * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
       return HX_ERR_HIP;
     m.A = A; m.C = C;
-    m.rate = static_cast<const double*>(rate.p);
-    m.weight = static_cast<const double*>(weight.p);
-    m.shrink = static_cast<const double*>(shrink.p);
+    m.rate = rate.as<const double>();
+    m.weight = weight.as<const double>();
+    m.shrink = shrink.as<const double>();
     return HX_OK;
   }
 };
@@ -391,29 +380,29 @@ int hx_distance_matrix(const hx_distance_model* hm, const int8_t* tokens, int32_
   g_dist_ms = 0.f;
   DeviceModel dm;
   if (int rc = dm.upload(hm, st)) return api_fail(rc, "hx_distance_matrix: device allocation or copy failed");
-  Buf b_tok, b_sd, b_tjc, b_dist, b_ev, b_prod;
+  DevBuf b_tok, b_sd, b_tjc, b_dist, b_ev, b_prod;
   g_dist_products = 0;
-  if (!b_tok.alloc((size_t)n_seqs * n_cols) || !b_sd.alloc(pairs * sizeof(int2)) || !b_tjc.alloc(pairs * sizeof(double)) ||
+  if (!b_tok.alloc(n_cols ? (size_t)n_seqs * n_cols : 1) || !b_sd.alloc(pairs * sizeof(int2)) || !b_tjc.alloc(pairs * sizeof(double)) ||
       !b_dist.alloc((size_t)n_seqs * n_seqs * sizeof(double)) || !b_ev.alloc(pairs * sizeof(int)) || !b_prod.alloc(sizeof(unsigned long long)))
     return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_distance_matrix: device allocation failed");
-  Events ev;
+  DevEvents<4> ev;
   if (!ev.create()) return api_fail(HX_ERR_HIP, "hx_distance_matrix: HIP call failed");
   if ((size_t)n_seqs * n_cols &&
-      hipMemcpyAsync(b_tok.p, tokens, (size_t)n_seqs * n_cols, hipMemcpyHostToDevice, st) != hipSuccess)
+      hipMemcpyAsync(b_tok.as<void>(), tokens, (size_t)n_seqs * n_cols, hipMemcpyHostToDevice, st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_distance_matrix: copy failed");
-  const signed char* d_tok = static_cast<const signed char*>(b_tok.p);
-  (void)hipEventRecord(ev.e[0], st);
-  hipLaunchKernelGGL(k_same_diff, dim3((unsigned)pairs), dim3(64), 0, st, d_tok, n_seqs, (long long)n_cols, static_cast<int2*>(b_sd.p));
-  (void)hipEventRecord(ev.e[1], st);
+  const signed char* d_tok = b_tok.as<const signed char>();
+  (void)hipEventRecord(ev[0], st);
+  hipLaunchKernelGGL(k_same_diff, dim3((unsigned)pairs), dim3(64), 0, st, d_tok, n_seqs, (long long)n_cols, b_sd.as<int2>());
+  (void)hipEventRecord(ev[1], st);
   std::vector<int2> sd(pairs);
   if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(sd.data(), b_sd.p, pairs * sizeof(int2), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(sd.data(), b_sd.as<void>(), pairs * sizeof(int2), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_distance_matrix: counting kernel or copy failed");
   std::vector<double> tjc(pairs);
   for (long long p = 0; p < pairs; ++p) tjc[p] = clamped_tjc(sd[p].x, sd[p].y, A, hm->expected_sub_rate);
   float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, ev.e[0], ev.e[1]);
+  (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
   g_dist_ms = ms;
   if (max_iterations <= 0) {
     long long p = 0;
@@ -425,30 +414,30 @@ int hx_distance_matrix(const hx_distance_model* hm, const int8_t* tokens, int32_
       for (long long q = 0; q < pairs; ++q) evaluations[q] = 0;
     return HX_OK;
   }
-  if (hipMemcpyAsync(b_tjc.p, tjc.data(), pairs * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemsetAsync(b_dist.p, 0, (size_t)n_seqs * n_seqs * sizeof(double), st) != hipSuccess ||
-      hipMemsetAsync(b_prod.p, 0, sizeof(unsigned long long), st) != hipSuccess)
+  if (hipMemcpyAsync(b_tjc.as<void>(), tjc.data(), pairs * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(b_dist.as<void>(), 0, (size_t)n_seqs * n_seqs * sizeof(double), st) != hipSuccess ||
+      hipMemsetAsync(b_prod.as<void>(), 0, sizeof(unsigned long long), st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_distance_matrix: copy failed");
   const int R = (A * A + 63) / 64;
   const size_t lds = lds_bytes(A);
-  (void)hipEventRecord(ev.e[2], st);
+  (void)hipEventRecord(ev[2], st);
 #define HX_DIST_GO(R_) hipLaunchKernelGGL((k_distance_search<R_>), dim3((unsigned)pairs), dim3(64), lds, st, dm.m, d_tok, n_seqs, (long long)n_cols, \
-                                          static_cast<const double*>(b_tjc.p), max_iterations, static_cast<double*>(b_dist.p), static_cast<int*>(b_ev.p), \
-                                          static_cast<unsigned long long*>(b_prod.p))
+                                          b_tjc.as<const double>(), max_iterations, b_dist.as<double>(), b_ev.as<int>(), \
+                                          b_prod.as<unsigned long long>())
   if (R <= 1) HX_DIST_GO(1);
   else if (R <= 4) HX_DIST_GO(4);
   else if (R <= 7) HX_DIST_GO(7);
   else HX_DIST_GO(16);
 #undef HX_DIST_GO
-  (void)hipEventRecord(ev.e[3], st);
+  (void)hipEventRecord(ev[3], st);
   unsigned long long products = 0;
   if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(dist, b_dist.p, (size_t)n_seqs * n_seqs * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      (evaluations && hipMemcpyAsync(evaluations, b_ev.p, pairs * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-      hipMemcpyAsync(&products, b_prod.p, sizeof products, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(dist, b_dist.as<void>(), (size_t)n_seqs * n_seqs * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (evaluations && hipMemcpyAsync(evaluations, b_ev.as<void>(), pairs * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) ||
+      hipMemcpyAsync(&products, b_prod.as<void>(), sizeof products, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_distance_matrix: search kernel or copy failed");
-  (void)hipEventElapsedTime(&ms, ev.e[2], ev.e[3]);
+  (void)hipEventElapsedTime(&ms, ev[2], ev[3]);
   g_dist_ms += ms;
   g_dist_products = (long long)products;
   return HX_OK;
@@ -466,30 +455,30 @@ int hx_distance_neg_log_like(const hx_distance_model* hm, const int32_t* counts,
   g_dist_ms = 0.f;
   DeviceModel dm;
   if (int rc = dm.upload(hm, st)) return api_fail(rc, "hx_distance_neg_log_like: device allocation or copy failed");
-  Buf b_cnt, b_t, b_f;
+  DevBuf b_cnt, b_t, b_f;
   if (!b_cnt.alloc(n * AA * sizeof(int)) || !b_t.alloc(n * sizeof(double)) || !b_f.alloc(n * sizeof(double)))
     return api_fail(HX_ERR_OUT_OF_MEMORY, "hx_distance_neg_log_like: device allocation failed");
-  Events ev;
+  DevEvents<2> ev;
   if (!ev.create()) return api_fail(HX_ERR_HIP, "hx_distance_neg_log_like: HIP call failed");
-  if (hipMemcpyAsync(b_cnt.p, counts, n * AA * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(b_t.p, t, n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+  if (hipMemcpyAsync(b_cnt.as<void>(), counts, n * AA * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(b_t.as<void>(), t, n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_distance_neg_log_like: copy failed");
   const int R = (A * A + 63) / 64;
   const size_t lds = lds_bytes(A);
-  (void)hipEventRecord(ev.e[0], st);
-#define HX_NLL_GO(R_) hipLaunchKernelGGL((k_distance_nll<R_>), dim3((unsigned)n), dim3(64), lds, st, dm.m, static_cast<const int*>(b_cnt.p), \
-                                         static_cast<const double*>(b_t.p), static_cast<double*>(b_f.p))
+  (void)hipEventRecord(ev[0], st);
+#define HX_NLL_GO(R_) hipLaunchKernelGGL((k_distance_nll<R_>), dim3((unsigned)n), dim3(64), lds, st, dm.m, b_cnt.as<const int>(), \
+                                         b_t.as<const double>(), b_f.as<double>())
   if (R <= 1) HX_NLL_GO(1);
   else if (R <= 4) HX_NLL_GO(4);
   else if (R <= 7) HX_NLL_GO(7);
   else HX_NLL_GO(16);
 #undef HX_NLL_GO
-  (void)hipEventRecord(ev.e[1], st);
+  (void)hipEventRecord(ev[1], st);
   if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(f, b_f.p, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(f, b_f.as<void>(), n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_distance_neg_log_like: kernel or copy failed");
-  (void)hipEventElapsedTime(&g_dist_ms, ev.e[0], ev.e[1]);
+  (void)hipEventElapsedTime(&g_dist_ms, ev[0], ev[1]);
   return HX_OK;
 }
 

@@ -434,7 +434,7 @@ struct hx_history {
   bool pending = false, have_counts = false;
   int cur = 0;                                       // which of d_cll / d_sum is current
   SpUpload model;                                    // the roots, the tree, the info words, the walk and the changed nodes, the mixture
-  SpBuf tok, mats, stage, E, logE, cll, sum, counts, rate;
+  DevBuf tok, mats, stage, E, logE, cll, sum, counts, rate;
   std::vector<double> max_abs;                       // [C] the largest |element| of each rate matrix; empty: no rates are set
   ExpmPlan expm = {};                                // k_branch_expm's workgroup, made when the rates were set
   const int *d_root = nullptr, *d_child = nullptr, *d_parent = nullptr;
@@ -445,18 +445,12 @@ struct hx_history {
   size_t lds = 0;
   float ms = 0.f, expm_ms = 0.f;                      // of the last evaluation: all its kernels; k_branch_expm alone
   float handoff_ms[3] = {0.f, 0.f, 0.f};             // of the last hx_history_branch_batch_create: profiles, insertion scores, preMultiply
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr;
+  DevEvents<4> ev;                                   // around the kernels of the last call: first, last, and two in between
   // excluded-neighbour queries: the positions of every node (host, from the tokens at create), their block offsets on the
   // device from the first query on, the query's plan and its output (both grow to the largest query so far)
   std::vector<long long> row_len, block_off;
-  SpBuf d_block_off, query, xout;
+  DevBuf d_block_off, query, xout;
   size_t query_bytes = 0, xout_doubles = 0;
-  ~hx_history() {
-    if (ev_a) (void)hipEventDestroy(ev_a);
-    if (ev_b) (void)hipEventDestroy(ev_b);
-    if (ev_c) (void)hipEventDestroy(ev_c);
-    if (ev_d) (void)hipEventDestroy(ev_d);
-  }
 };
 
 namespace {
@@ -500,40 +494,40 @@ int history_run(hx_history* h, const std::vector<int>& changed, const std::vecto
   // (the info words, the walk, the arriving nodes and the shapes are adjacent on the device: one copy; the matrices: another)
   const size_t CAA = (size_t)h->C * h->A * h->A;
   if (hipMemcpy(h->d_info, info.data(), info.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      (new_mats && hipMemcpy(h->stage.p, new_mats, changed.size() * CAA * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
+      (new_mats && hipMemcpy(h->stage.as<void>(), new_mats, changed.size() * CAA * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
     return api_fail(HX_ERR_HIP, "hx_history: copy failed");
   HsArgs a;
   a.A = h->A; a.C = h->C; a.N = N; a.n_walk = (int)walked.size();
   a.n_cols = h->n_cols; a.ncp = h->ncp; a.e_slot = h->e_slot; a.lg_slot = h->lg_slot;
-  a.tok = static_cast<const signed char*>(h->tok.p);
+  a.tok = h->tok.as<const signed char>();
   a.root = h->d_root; a.child = h->d_child; a.walk = h->d_walk; a.info = h->d_info;
   a.ins_prob = h->d_ins; a.log_cpt_weight = h->d_lcw;
-  a.mats = static_cast<const double*>(h->mats.p);
-  a.E = static_cast<double*>(h->E.p); a.logE = static_cast<double*>(h->logE.p);
-  double* cll = static_cast<double*>(h->cll.p);
-  double* sum = static_cast<double*>(h->sum.p);
+  a.mats = h->mats.as<const double>();
+  a.E = h->E.as<double>(); a.logE = h->logE.as<double>();
+  double* cll = h->cll.as<double>();
+  double* sum = h->sum.as<double>();
   a.cll_cur = cll + h->cur * h->ncp;
   a.cll_new = cll + (h->cur ^ 1) * h->ncp;
   const long long blocks64 = h->ncp / 64;
   const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
-  (void)hipEventRecord(h->ev_a, st);
-  if (lengths && launch_branch_expm(h->expm, static_cast<const double*>(h->rate.p), reinterpret_cast<const ExpmShape*>(h->d_info + n_words), h->d_walk + walked.size(),
-                                    h->d_info, (int)arriving.size(), h->A, h->C, N, static_cast<double*>(h->mats.p), st) != 0)
+  (void)hipEventRecord(h->ev[0], st);
+  if (lengths && launch_branch_expm(h->expm, h->rate.as<const double>(), reinterpret_cast<const ExpmShape*>(h->d_info + n_words), h->d_walk + walked.size(),
+                                    h->d_info, (int)arriving.size(), h->A, h->C, N, h->mats.as<double>(), st) != 0)
     return api_fail(HX_ERR_INVALID_ARG, launch_error());
-  if (lengths) (void)hipEventRecord(h->ev_c, st);
+  if (lengths) (void)hipEventRecord(h->ev[2], st);
   if (new_mats)
-    hipLaunchKernelGGL(k_history_scatter, dim3((unsigned)(changed.size() * h->C)), dim3(256), 0, st, static_cast<const double*>(h->stage.p),
-                       h->d_walk + walked.size(), h->d_info, h->C, N, h->A * h->A, static_cast<double*>(h->mats.p));
+    hipLaunchKernelGGL(k_history_scatter, dim3((unsigned)(changed.size() * h->C)), dim3(256), 0, st, h->stage.as<const double>(),
+                       h->d_walk + walked.size(), h->d_info, h->C, N, h->A * h->A, h->mats.as<double>());
   if (h->A == 4) hipLaunchKernelGGL(k_history_columns<4>, dim3(blocks), dim3(h->tpb), h->lds, st, a, lse_tab);
   else if (h->A == 20) hipLaunchKernelGGL(k_history_columns<20>, dim3(blocks), dim3(h->tpb), h->lds, st, a, lse_tab);
   else hipLaunchKernelGGL(k_history_columns<0>, dim3(blocks), dim3(h->tpb), h->lds, st, a, lse_tab);
   hipLaunchKernelGGL(k_history_sum, dim3(1), dim3(1024), 0, st, a.cll_new, h->n_cols, sum + (h->cur ^ 1));
-  (void)hipEventRecord(h->ev_b, st);
+  (void)hipEventRecord(h->ev[1], st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_history: kernel launch or execution failed");
-  (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
+  (void)hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]);
   h->expm_ms = 0.f;
-  if (lengths) (void)hipEventElapsedTime(&h->expm_ms, h->ev_a, h->ev_c);
+  if (lengths) (void)hipEventElapsedTime(&h->expm_ms, h->ev[0], h->ev[2]);
   if (lp_sub && hipMemcpy(lp_sub, sum + (h->cur ^ 1), sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_history: copy failed");
   return HX_OK;
@@ -549,8 +543,8 @@ void history_commit(hx_history* h, const std::vector<int>& changed, const std::v
 // (history_check_rates) before anything is allocated.
 int history_put_rates(hx_history* h, const char* fn, const double* rate, const std::vector<double>& max_abs, const ExpmPlan& plan) {
   const size_t bytes = (size_t)h->C * h->A * h->A * sizeof(double);
-  if (!h->rate.p && hipMalloc(&h->rate.p, bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-  if (hipMemcpy(h->rate.p, rate, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+  if (!h->rate && !h->rate.alloc(bytes)) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+  if (hipMemcpy(h->rate.as<void>(), rate, bytes, hipMemcpyHostToDevice) != hipSuccess) {
     h->max_abs.clear();                              // (what the buffer holds is unknown: no rates are set)
     return sp_fail(HX_ERR_HIP, fn, "copy failed");
   }
@@ -627,12 +621,12 @@ int history_create(const char* fn, const hx_history_model* hm, const int8_t* tok
   // [N] info words, the walk [<= N], the arriving nodes [<= N], a word of padding, six words per (node, component) of shapes
   const size_t n_info = 3 * (size_t)N + 2 + 6 * (size_t)N * C;
   SpUpload& up = h->model;
-  if (hipMalloc(&h->tok.p, (size_t)N * ncp) != hipSuccess ||
+  if (!h->tok.alloc((size_t)N * ncp) ||
       !up.alloc(SpUpload::room((size_t)ncp * sizeof(int)) + sp_tree_room(A, C, N, false) + SpUpload::room(n_info * sizeof(int))) ||
-      hipMalloc(&h->mats.p, 2 * n_mat * sizeof(double)) != hipSuccess || hipMalloc(&h->stage.p, n_mat * sizeof(double)) != hipSuccess ||
-      hipMalloc(&h->E.p, 2 * (size_t)h->e_slot * sizeof(double)) != hipSuccess || hipMalloc(&h->logE.p, 2 * (size_t)h->lg_slot * sizeof(double)) != hipSuccess ||
-      hipMalloc(&h->cll.p, 2 * (size_t)ncp * sizeof(double)) != hipSuccess || hipMalloc(&h->sum.p, 2 * sizeof(double)) != hipSuccess ||
-      hipMalloc(&h->counts.p, (size_t)N * 12 * sizeof(long long)) != hipSuccess)
+      !h->mats.alloc(2 * n_mat * sizeof(double)) || !h->stage.alloc(n_mat * sizeof(double)) ||
+      !h->E.alloc(2 * (size_t)h->e_slot * sizeof(double)) || !h->logE.alloc(2 * (size_t)h->lg_slot * sizeof(double)) ||
+      !h->cll.alloc(2 * (size_t)ncp * sizeof(double)) || !h->sum.alloc(2 * sizeof(double)) ||
+      !h->counts.alloc((size_t)N * 12 * sizeof(long long)))
     return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
   h->d_root = up.put(root.data(), root.size());
   const SpTree tr = sp_put_tree(up, A, C, N, hm->parent, child, hm->ins_prob, hm->log_cpt_weight, nullptr);
@@ -640,14 +634,13 @@ int history_create(const char* fn, const hx_history_model* hm, const int8_t* tok
   h->d_info = up.reserve<int>(n_info);
   h->d_walk = h->d_info + N;
   // the root's matrix is never read; the caller's [C][N][A][A] goes to slot 0 whole, or exp(R t) of every branch is computed there
-  if (!up.copied || hipMemcpy(h->tok.p, tokT.data(), tokT.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      (branch_sub && hipMemcpy(h->mats.p, branch_sub, n_mat * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemset(h->cll.p, 0, 2 * (size_t)ncp * sizeof(double)) != hipSuccess)
+  if (!up.copied || hipMemcpy(h->tok.as<void>(), tokT.data(), tokT.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      (branch_sub && hipMemcpy(h->mats.as<void>(), branch_sub, n_mat * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemset(h->cll.as<void>(), 0, 2 * (size_t)ncp * sizeof(double)) != hipSuccess)
     return sp_fail(HX_ERR_HIP, fn, "copy failed");
   if (rate)
     if (int rc = history_put_rates(h, fn, rate, max_abs, expm)) return rc;
-  if (hipEventCreate(&h->ev_a) != hipSuccess || hipEventCreate(&h->ev_b) != hipSuccess || hipEventCreate(&h->ev_c) != hipSuccess ||
-      hipEventCreate(&h->ev_d) != hipSuccess)
+  if (!h->ev.create())
     return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
   // the full evaluation: the proposal that changes and walks every node, accepted
   std::vector<int> all(N);
@@ -685,7 +678,7 @@ int history_propose(const char* fn, hx_history* h, const int n_changed, const in
 
 // The kernels of an excluded-neighbour query on `st`, not waited for: the plan to the device (with `extra`, which the
 // caller's further kernels read at *d_extra), k_history_excluded and, if asked for, the normalisation.  The pairs' blocks
-// lie at out_base + plan.out_off (doubles); out_base null: in the history's own buffer, grown to plan.total.  ev_a is recorded
+// lie at out_base + plan.out_off (doubles); out_base null: in the history's own buffer, grown to plan.total.  ev[0] is recorded
 // in front.  Nothing of the history's state is written.
 int history_excluded_launch(hx_history* h, const char* fn, const int which, const int n_pairs, const ExcludedPlan& plan, const int normalize, double* out_base,
                             const void* extra, const size_t extra_bytes, const void** d_extra, const SpPlan& col_plan, const double* lse_tab, hipStream_t st) {
@@ -712,47 +705,42 @@ int history_excluded_launch(hx_history* h, const char* fn, const int which, cons
   if (extra_bytes) memcpy(reinterpret_cast<char*>(block.data()) + extra_at, extra, extra_bytes);
   const size_t bytes = block.size() * sizeof(long long);
   if (bytes > h->query_bytes) {
-    if (h->query.p) (void)hipFree(h->query.p);
-    h->query.p = nullptr;
-    h->query_bytes = 0;
-    if (hipMalloc(&h->query.p, bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    h->query.reset(); h->query_bytes = 0;
+    if (!h->query.alloc(bytes)) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
     h->query_bytes = bytes;
   }
   if (!out_base && (size_t)plan.total > h->xout_doubles) {
-    if (h->xout.p) (void)hipFree(h->xout.p);
-    h->xout.p = nullptr;
-    h->xout_doubles = 0;
-    if (hipMalloc(&h->xout.p, (size_t)plan.total * sizeof(double)) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    h->xout.reset(); h->xout_doubles = 0;
+    if (!h->xout.alloc((size_t)plan.total * sizeof(double))) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
     h->xout_doubles = (size_t)plan.total;
   }
-  if (!h->d_block_off.p) {
+  if (!h->d_block_off) {
     const size_t off_bytes = h->block_off.size() * sizeof(long long);
-    if (hipMalloc(&h->d_block_off.p, off_bytes) != hipSuccess) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-    if (hipMemcpy(h->d_block_off.p, h->block_off.data(), off_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(h->d_block_off.p);
-      h->d_block_off.p = nullptr;
+    if (!h->d_block_off.alloc(off_bytes)) return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
+    if (hipMemcpy(h->d_block_off.as<void>(), h->block_off.data(), off_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      h->d_block_off.reset();
       return sp_fail(HX_ERR_HIP, fn, "copy failed");
     }
   }
-  if (hipMemcpy(h->query.p, block.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
-  const long long* d_ll = static_cast<const long long*>(h->query.p);
-  if (d_extra) *d_extra = static_cast<const char*>(h->query.p) + extra_at;
+  if (hipMemcpy(h->query.as<void>(), block.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
+  const long long* d_ll = h->query.as<const long long>();
+  if (d_extra) *d_extra = h->query.as<const char>() + extra_at;
   const int* d_words = reinterpret_cast<const int*>(d_ll + n_ll);
   HxArgs a;
   a.A = A; a.C = C; a.N = N; a.n_pairs = n_pairs;
   a.n_cols = h->n_cols; a.ncp = h->ncp; a.n_blocks = h->ncp / 64; a.e_slot = h->e_slot; a.lg_slot = h->lg_slot;
-  a.tok = static_cast<const signed char*>(h->tok.p);
+  a.tok = h->tok.as<const signed char>();
   a.root = h->d_root; a.child = h->d_child;
   a.info = d_words; a.pair = d_words + N; a.path = d_words + N + plan.pair.size();
-  a.out_off = d_ll; a.block_off = static_cast<const long long*>(h->d_block_off.p);
+  a.out_off = d_ll; a.block_off = h->d_block_off.as<const long long>();
   a.ins_prob = h->d_ins; a.log_cpt_weight = h->d_lcw;
-  a.mats = static_cast<const double*>(h->mats.p);
-  a.E = static_cast<const double*>(h->E.p); a.logE = static_cast<const double*>(h->logE.p);
-  a.out = out_base ? out_base : static_cast<double*>(h->xout.p);
+  a.mats = h->mats.as<const double>();
+  a.E = h->E.as<const double>(); a.logE = h->logE.as<const double>();
+  a.out = out_base ? out_base : h->xout.as<double>();
   const long long blocks64 = h->ncp / 64;
   const unsigned blocks = (unsigned)(blocks64 > 65535 ? 65535 : blocks64);
   const unsigned tpb = 64 * (unsigned)col_plan.waves;
-  (void)hipEventRecord(h->ev_a, st);
+  (void)hipEventRecord(h->ev[0], st);
   if (A == 4) hipLaunchKernelGGL(k_history_excluded<4>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
   else if (A == 20) hipLaunchKernelGGL(k_history_excluded<20>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
   else hipLaunchKernelGGL(k_history_excluded<0>, dim3(blocks), dim3(tpb), col_plan.lds, st, a);
@@ -817,7 +805,7 @@ int hx_history_branch_matrix(hx_history* h, int32_t which, int32_t node, double*
   if (which == 1 && std::find(h->changed.begin(), h->changed.end(), (int)node) != h->changed.end()) slot ^= 1;
   // the node's C matrices lie N matrices apart
   const size_t mat = (size_t)h->A * h->A * sizeof(double);
-  const double* src = static_cast<const double*>(h->mats.p) + ((size_t)slot * h->C * h->N + node) * h->A * h->A;
+  const double* src = h->mats.as<const double>() + ((size_t)slot * h->C * h->N + node) * h->A * h->A;
   if (hipMemcpy2D(out, mat, src, mat * h->N, mat, (size_t)h->C, hipMemcpyDeviceToHost) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "copy failed");
   return HX_OK;
 }
@@ -841,8 +829,8 @@ int hx_history_log_like(hx_history* h, int32_t which, double* lp_sub, double* co
   if (!h || (which != 0 && which != 1)) return api_fail(HX_ERR_INVALID_ARG, "hx_history_log_like: null argument, or `which` not 0 or 1");
   if (which == 1 && !h->pending) return api_fail(HX_ERR_STATE, "hx_history_log_like: no proposal is pending");
   const int s = h->cur ^ which;
-  if ((lp_sub && hipMemcpy(lp_sub, static_cast<double*>(h->sum.p) + s, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-      (col_log_like && hipMemcpy(col_log_like, static_cast<double*>(h->cll.p) + s * h->ncp, (size_t)h->n_cols * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+  if ((lp_sub && hipMemcpy(lp_sub, h->sum.as<double>() + s, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (col_log_like && hipMemcpy(col_log_like, h->cll.as<double>() + s * h->ncp, (size_t)h->n_cols * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
     return api_fail(HX_ERR_HIP, "hx_history_log_like: copy failed");
   return HX_OK;
 }
@@ -850,13 +838,13 @@ int hx_history_log_like(hx_history* h, int32_t which, double* lp_sub, double* co
 int hx_history_indel_counts(hx_history* h, int64_t* counts) {
   if (!h || !counts) return api_fail(HX_ERR_INVALID_ARG, "hx_history_indel_counts: null argument");
   if (!h->have_counts) {                             // (the alignment is fixed: counted once, on the null stream)
-    hipLaunchKernelGGL(k_history_indels, dim3((unsigned)((h->N + 3) / 4)), dim3(256), 0, (hipStream_t) nullptr, static_cast<const signed char*>(h->tok.p),
-                       h->d_parent, h->N, h->n_cols, h->ncp, static_cast<long long*>(h->counts.p));
+    hipLaunchKernelGGL(k_history_indels, dim3((unsigned)((h->N + 3) / 4)), dim3(256), 0, (hipStream_t) nullptr, h->tok.as<const signed char>(),
+                       h->d_parent, h->N, h->n_cols, h->ncp, h->counts.as<long long>());
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
       return api_fail(HX_ERR_HIP, "hx_history_indel_counts: kernel launch or execution failed");
     h->have_counts = true;
   }
-  if (hipMemcpy(counts, h->counts.p, (size_t)h->N * 12 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess)
+  if (hipMemcpy(counts, h->counts.as<void>(), (size_t)h->N * 12 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess)
     return api_fail(HX_ERR_HIP, "hx_history_indel_counts: copy failed");
   return HX_OK;
 }
@@ -892,10 +880,10 @@ int hx_history_excluded_profiles(hx_history* h, int32_t which, int32_t n_pairs, 
   const int rc = history_excluded_launch(h, fn, which, n_pairs, plan, normalize, nullptr, nullptr, 0, nullptr, col_plan, lse_tab, static_cast<hipStream_t>(stream));
   if (rc != HX_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const double* xout = static_cast<const double*>(h->xout.p);
-  (void)hipEventRecord(h->ev_b, st);
+  const double* xout = h->xout.as<const double>();
+  (void)hipEventRecord(h->ev[1], st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
-  (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
+  (void)hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]);
   h->expm_ms = 0.f;
   for (int k = 0; k < n_pairs; ++k)
     if (plan.out_len[k] > 0 &&
@@ -960,23 +948,23 @@ int hx_history_branch_batch_create(hx_history* h, int32_t which, int32_t normali
   if (const int rc = history_excluded_launch(h, fn, which, n_pairs, plan, normalize, base, jobs.data(), sizeof(HbJob) * jobs.size(), &d_jobs_v, col_plan, lse_tab, st))
     return rc;
   const HbJob* d_jobs = static_cast<const HbJob*>(d_jobs_v);
-  (void)hipEventRecord(h->ev_c, st);
+  (void)hipEventRecord(h->ev[2], st);
   if (max_y > 0) {
     const unsigned gz = (unsigned)(n_branches > 65535 ? 65535 : n_branches);
     const long long nb = (max_y + 255) / 256, tiles = (max_y + P - 1) / P;
     hipLaunchKernelGGL(k_history_ins_probs, dim3((unsigned)(nb > 65535 ? 65535 : nb), gz), dim3(256), 0, st, d_jobs, n_branches, C, A, h->d_lcw, lse_tab);
-    (void)hipEventRecord(h->ev_d, st);
+    (void)hipEventRecord(h->ev[3], st);
     hipLaunchKernelGGL(k_history_pre_multiply, dim3((unsigned)(tiles > 65535 ? 65535 : tiles), (unsigned)C, gz), dim3(256), pm_lds, st, d_jobs, n_branches, C, A, P,
                        lse_tab);
   } else {
-    (void)hipEventRecord(h->ev_d, st);
+    (void)hipEventRecord(h->ev[3], st);
   }
-  (void)hipEventRecord(h->ev_b, st);
+  (void)hipEventRecord(h->ev[1], st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
-  (void)hipEventElapsedTime(&h->ms, h->ev_a, h->ev_b);
-  (void)hipEventElapsedTime(&h->handoff_ms[0], h->ev_a, h->ev_c);
-  (void)hipEventElapsedTime(&h->handoff_ms[1], h->ev_c, h->ev_d);
-  (void)hipEventElapsedTime(&h->handoff_ms[2], h->ev_d, h->ev_b);
+  (void)hipEventElapsedTime(&h->ms, h->ev[0], h->ev[1]);
+  (void)hipEventElapsedTime(&h->handoff_ms[0], h->ev[0], h->ev[2]);
+  (void)hipEventElapsedTime(&h->handoff_ms[1], h->ev[2], h->ev[3]);
+  (void)hipEventElapsedTime(&h->handoff_ms[2], h->ev[3], h->ev[1]);
   h->expm_ms = 0.f;
   guard.b = nullptr;
   *out = b;

@@ -12,6 +12,8 @@
 #include <type_traits>
 #include <utility>
 #include <vector>
+#include "hx_arena.h"
+#include "hx_devmem.h"
 #include "hx_pairdp.h"
 
 namespace hx {
@@ -75,34 +77,16 @@ int api_fail(int code, const char* what);                  // hx_api.hip: sets h
 const double* device_lse_table(int device);               // hx_api.hip: the table hx_init uploaded, or nullptr
 
 // ---- the batch ---------------------------------------------------------------------------------------------------------------
-// The host image of a batch's inputs.  A job's pointers into it are set once the device copy has an address.  Behind the
-// image (and lpEnd) the device arena holds what was reserved: arrays with no host copy, which kernels fill on the device.
-struct PairArena {
-  std::vector<char> host;
-  std::vector<std::pair<void*, size_t>> fix;      // (a pointer member of a job, offset of what it shall point to)
-  std::vector<std::pair<void*, size_t>> fix_reserved;      // (..., offset within the reserved part)
-  size_t reserved = 0;                            // bytes
-  template <class T> void reserve(const T*& member, size_t n) {
-    fix_reserved.emplace_back(&member, reserved);
-    reserved += (sizeof(T) * n + 15) & ~(size_t)15;
-  }
-  size_t put(const void* p, size_t bytes) {
-    const size_t off = (host.size() + 15) & ~(size_t)15;
-    host.resize(off + bytes);
-    if (bytes) memcpy(host.data() + off, p, bytes);
-    return off;
-  }
-  template <class T> void put(const T*& member, const T* p, size_t n) { fix.emplace_back(&member, put(p, sizeof(T) * n)); }
-  // envelope coordinates of a banded job and, with `windows`, the step windows of its strips
-  template <class Job> void put_env(Job& J, const int32_t* x_env, const int32_t* y_env, bool windows) {
-    if (J.max_dist < 0) return;
-    put(J.x_env, x_env, (size_t)J.X);
-    put(J.y_env, y_env, (size_t)J.Y);
-    if (!windows) return;
-    const std::vector<int32_t> w = branch_windows(x_env, y_env, J.X, J.Y, J.max_dist);
-    put(J.win, w.data(), w.size());
-  }
-};
+// Envelope coordinates of a banded job into the batch's arena (hx_arena.h: 16-byte pieces) and, with `windows`, the step
+// windows of its strips
+template <class Job> void put_env(Arena& a, Job& J, const int32_t* x_env, const int32_t* y_env, bool windows) {
+  if (J.max_dist < 0) return;
+  a.put(J.x_env, x_env, (size_t)J.X);
+  a.put(J.y_env, y_env, (size_t)J.Y);
+  if (!windows) return;
+  const std::vector<int32_t> w = branch_windows(x_env, y_env, J.X, J.Y, J.max_dist);
+  a.put(J.win, w.data(), w.size());
+}
 
 // What hx_branch_batch and hx_sibling_batch are: n jobs of one lattice family resident on the device - inputs, NS state
 // planes and an emission plane per job, lpEnd - and the C ABI's calls on them but for what a lattice validates and fills in
@@ -111,12 +95,13 @@ template <class Job, int NS>
 struct PairBatch {
   int device = 0, n_jobs = 0;
   std::vector<Job> jobs;
-  Job* d_jobs = nullptr;
-  char* d_arena = nullptr;          // inputs + lpEnd
-  double* d_cells = nullptr;        // matrices + emission planes
+  DevBuf d_jobs;                    // [n_jobs] Job
+  DevBuf d_arena;                   // inputs + lpEnd, then what the jobs reserved
+  DevBuf d_cells;                   // matrices + emission planes
   size_t lp_off = 0;
   int max_x = 0, max_y = 0;         // rows / columns of the longest job
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};       // before the step, before the fill, after it
+  DevEvents<3> ev;                  // before the step, before the fill, after it
+  Job* device_jobs() const { return d_jobs.template as<Job>(); }
   hipStream_t last_stream = nullptr;
   bool done = false;
   float walk_ms = -1.f;             // the walk kernel of the last best_paths / sample_paths (HIP events)
@@ -127,15 +112,7 @@ struct PairBatch {
     return api_fail(code, msg);
   }
 
-  ~PairBatch() {
-    (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize();
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (d_jobs) (void)hipFree(d_jobs);
-    if (d_arena) (void)hipFree(d_arena);
-    if (d_cells) (void)hipFree(d_cells);
-  }
+  ~PairBatch() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }      // (the members release after it: nothing is in flight by then)
 
   // fill(J, abi_job, arena): validates one job of the ABI, sets X, Y, CA, C, max_dist and T and puts the job's arrays; returns
   // HX_OK or what api_fail returned
@@ -150,7 +127,7 @@ struct PairBatch {
     if (!b) return api_fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed");
     b->device = device;
     b->n_jobs = n_jobs;
-    PairArena a;
+    Arena a(16);
     int64_t cells_total = 0;
     try {
       b->jobs.resize(n_jobs);                       // (zeroed: what a job does not put stays null)
@@ -163,35 +140,23 @@ struct PairBatch {
         b->max_x = std::max(b->max_x, (int)J.X);
         b->max_y = std::max(b->max_y, (int)J.Y);
       }
-      b->lp_off = a.put(nullptr, 0);
-      a.host.resize(b->lp_off + sizeof(double) * n_jobs);
+      b->lp_off = a.reserve(sizeof(double) * n_jobs);
     } catch (const std::bad_alloc&) {
       return api_fail(HX_ERR_OUT_OF_MEMORY, "host allocation failed while building the batch");
     }
-    const size_t reserved_at = (a.host.size() + 15) & ~(size_t)15;
-    if (hipMalloc(reinterpret_cast<void**>(&b->d_arena), reserved_at + a.reserved) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&b->d_cells), sizeof(double) * (size_t)cells_total) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&b->d_jobs), sizeof(Job) * n_jobs) != hipSuccess)
+    if (!b->d_arena.alloc(a.device_bytes()) || !b->d_cells.alloc(sizeof(double) * (size_t)cells_total) || !b->d_jobs.alloc(sizeof(Job) * n_jobs))
       return fail(HX_ERR_OUT_OF_MEMORY, "_create: device allocation failed");
-    for (const auto& f : a.fix) {
-      const char* p = b->d_arena + f.second;
-      memcpy(f.first, &p, sizeof(p));
-    }
-    for (const auto& f : a.fix_reserved) {
-      const char* p = b->d_arena + reserved_at + f.second;
-      memcpy(f.first, &p, sizeof(p));
-    }
+    a.bind(b->d_arena.template as<char>());
     int64_t at = 0;
     for (int k = 0; k < n_jobs; ++k) {
       Job& J = b->jobs[k];
-      J.cells = b->d_cells + at;
-      J.emis = b->d_cells + at + NS * J.plane;
+      J.cells = b->d_cells.template as<double>() + at;
+      J.emis = J.cells + NS * J.plane;
       at += (NS + 1) * J.plane;
-      J.lp_end = reinterpret_cast<double*>(b->d_arena + b->lp_off) + k;
+      J.lp_end = reinterpret_cast<double*>(b->d_arena.template as<char>() + b->lp_off) + k;
     }
-    if (hipMemcpy(b->d_arena, a.host.data(), a.host.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b->d_jobs, b->jobs.data(), sizeof(Job) * n_jobs, hipMemcpyHostToDevice) != hipSuccess ||
-        hipEventCreate(&b->ev[0]) != hipSuccess || hipEventCreate(&b->ev[1]) != hipSuccess || hipEventCreate(&b->ev[2]) != hipSuccess)
+    if (hipMemcpy(b->d_arena.template as<void>(), a.host.data(), a.host.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->d_jobs.template as<void>(), b->jobs.data(), sizeof(Job) * n_jobs, hipMemcpyHostToDevice) != hipSuccess || !b->ev.create())
       return fail(HX_ERR_HIP, "_create: copy to the device failed");
     *out = b.release();
     return HX_OK;
@@ -209,8 +174,8 @@ struct PairBatch {
     if (hipEventRecord(b->ev[0], st) != hipSuccess) return api_fail(HX_ERR_HIP, "hipEventRecord failed");
     for (int j0 = 0; j0 < b->n_jobs; j0 += 16384) {        // (grid.x of at most 16384 jobs per launch)
       const int n = b->n_jobs - j0 < 16384 ? b->n_jobs - j0 : 16384;
-      hipLaunchKernelGGL((k_pair_clear<Job, NS>), dim3(n, 16), dim3(256), 0, st, b->d_jobs + j0);
-      hipLaunchKernelGGL(k_pair_emission<Job>, dim3(n, 16), dim3(256), 0, st, b->d_jobs + j0, tab);
+      hipLaunchKernelGGL((k_pair_clear<Job, NS>), dim3(n, 16), dim3(256), 0, st, b->device_jobs() + j0);
+      hipLaunchKernelGGL(k_pair_emission<Job>, dim3(n, 16), dim3(256), 0, st, b->device_jobs() + j0, tab);
     }
     if (hipEventRecord(b->ev[1], st) != hipSuccess) return api_fail(HX_ERR_HIP, "hipEventRecord failed");
     for (int j0 = 0; j0 < b->n_jobs; j0 += 65536) {
@@ -225,8 +190,8 @@ struct PairBatch {
       const bool yl = (size_t)b->max_y * 12 <= 96 * 1024;
       const size_t dyn = yl ? (size_t)b->max_y * 12 + 16 : 0;
       const int y_cap = yl ? (b->max_y + 1) & ~1 : 0;
-      if (yl) hipLaunchKernelGGL((k_pair_fill<L, true>), dim3(n), dim3(64 * waves), dyn, st, b->d_jobs + j0, tab, y_cap);
-      else hipLaunchKernelGGL((k_pair_fill<L, false>), dim3(n), dim3(64 * waves), 0, st, b->d_jobs + j0, tab, 0);
+      if (yl) hipLaunchKernelGGL((k_pair_fill<L, true>), dim3(n), dim3(64 * waves), dyn, st, b->device_jobs() + j0, tab, y_cap);
+      else hipLaunchKernelGGL((k_pair_fill<L, false>), dim3(n), dim3(64 * waves), 0, st, b->device_jobs() + j0, tab, 0);
     }
     if (hipEventRecord(b->ev[2], st) != hipSuccess || hipGetLastError() != hipSuccess) return fail(HX_ERR_HIP, "_run: launch failed");
     b->done = true;
@@ -238,7 +203,7 @@ struct PairBatch {
     if (!b || !lp_end) return api_fail(HX_ERR_INVALID_ARG, "bad arguments");
     if (!b->done) return fail(HX_ERR_STATE, "_run has not been launched");
     if (hipSetDevice(b->device) != hipSuccess || hipStreamSynchronize(b->last_stream) != hipSuccess ||
-        hipMemcpy(lp_end, b->d_arena + b->lp_off, sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(lp_end, b->d_arena.template as<char>() + b->lp_off, sizeof(double) * b->n_jobs, hipMemcpyDeviceToHost) != hipSuccess)
       return fail(HX_ERR_HIP, "_results: HIP call failed");
     return HX_OK;
   }
@@ -250,13 +215,13 @@ struct PairBatch {
     if (!b->done) return fail(HX_ERR_STATE, "_run has not been launched");
     const Job& J = b->jobs[job];
     const size_t bytes = sizeof(double) * NS * (size_t)J.X * J.Y;
-    double* dense = nullptr;
-    if (hipSetDevice(b->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dense), bytes) != hipSuccess)
+    DevBuf dense;
+    if (hipSetDevice(b->device) != hipSuccess || !dense.alloc(bytes))
       return fail(HX_ERR_OUT_OF_MEMORY, "_read_matrix: device allocation failed");
-    hipLaunchKernelGGL((k_pair_dense<Job, NS>), dim3(256), dim3(256), 0, b->last_stream, b->d_jobs, job, dense);
-    const bool ok = hipStreamSynchronize(b->last_stream) == hipSuccess && hipMemcpy(out, dense, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(dense);
-    return ok ? HX_OK : fail(HX_ERR_HIP, "_read_matrix: HIP call failed");
+    hipLaunchKernelGGL((k_pair_dense<Job, NS>), dim3(256), dim3(256), 0, b->last_stream, b->device_jobs(), job, dense.as<double>());
+    if (hipStreamSynchronize(b->last_stream) != hipSuccess || hipMemcpy(out, dense.as<double>(), bytes, hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(HX_ERR_HIP, "_read_matrix: HIP call failed");
+    return HX_OK;
   }
 
   static int64_t total_cells(const PairBatch* b) {
@@ -278,17 +243,10 @@ struct PairBatch {
   }
 };
 
-// device buffers of one call, freed when it returns
-struct PairScratch {
-  std::vector<void*> p;
-  ~PairScratch() { for (void* q : p) (void)hipFree(q); }
-  template <class T> T* get(const size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, sizeof(T) * (n ? n : 1)) != hipSuccess) return nullptr;
-    p.push_back(q);
-    return static_cast<T*>(q);
-  }
-};
+// a device buffer of n elements (at least one byte: an address also for none), or null
+template <class T> T* scratch(DevBuf& b, const size_t n) {
+  return b.alloc(sizeof(T) * (n ? n : 1)) ? b.as<T>() : nullptr;
+}
 
 // hx_*_batch_best_paths / hx_*_batch_sample_paths
 template <class L, bool BEST, class Batch>
@@ -307,14 +265,14 @@ int pair_walk_paths(Batch* b, const uint32_t* words, const int64_t* word_off, ui
     if (n_words > 0 && !words) return api_fail(HX_ERR_INVALID_ARG, "pair walk: words is null");
   }
   if (hipSetDevice(b->device) != hipSuccess) return api_fail(HX_ERR_HIP, "hipSetDevice failed");
-  PairScratch sc;
+  DevBuf b_states, b_steps, b_words, b_off, b_used;
   PairWalkIO o{};
   o.cap = cap;
-  o.states = sc.get<uint8_t>((size_t)n * cap);
-  o.n_steps = sc.get<int32_t>(n);
-  uint32_t* d_words = BEST ? nullptr : sc.get<uint32_t>((size_t)n_words);
-  int64_t* d_off = BEST ? nullptr : sc.get<int64_t>((size_t)n + 1);
-  o.words_used = BEST ? nullptr : sc.get<int32_t>(n);
+  o.states = scratch<uint8_t>(b_states, (size_t)n * cap);
+  o.n_steps = scratch<int32_t>(b_steps, n);
+  uint32_t* d_words = BEST ? nullptr : scratch<uint32_t>(b_words, (size_t)n_words);
+  int64_t* d_off = BEST ? nullptr : scratch<int64_t>(b_off, (size_t)n + 1);
+  o.words_used = BEST ? nullptr : scratch<int32_t>(b_used, n);
   o.words = d_words;
   o.word_off = d_off;
   if (!o.states || !o.n_steps || (!BEST && (!d_words || !d_off || !o.words_used)))
@@ -322,18 +280,15 @@ int pair_walk_paths(Batch* b, const uint32_t* words, const int64_t* word_off, ui
   if (!BEST && ((n_words && hipMemcpy(d_words, words, sizeof(uint32_t) * (size_t)n_words, hipMemcpyHostToDevice) != hipSuccess) ||
                 hipMemcpy(d_off, word_off, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice) != hipSuccess))
     return api_fail(HX_ERR_HIP, "pair walk: copy to the device failed");
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess &&
-                     hipEventRecord(ev[0], b->last_stream) == hipSuccess;
+  DevEvents<2> ev;
+  const bool timed = ev.create() && hipEventRecord(ev[0], b->last_stream) == hipSuccess;
   for (int j0 = 0; j0 < n; j0 += 65536) {
     const int m = n - j0 < 65536 ? n - j0 : 65536;
-    hipLaunchKernelGGL((k_pair_walk<L, BEST>), dim3(m), dim3(64), 0, b->last_stream, b->d_jobs, j0, o);
+    hipLaunchKernelGGL((k_pair_walk<L, BEST>), dim3(m), dim3(64), 0, b->last_stream, b->device_jobs(), j0, o);
   }
   b->walk_ms = -1.f;
   if (timed && hipEventRecord(ev[1], b->last_stream) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess)
     (void)hipEventElapsedTime(&b->walk_ms, ev[0], ev[1]);
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->last_stream) != hipSuccess ||
       hipMemcpy(states, o.states, (size_t)n * cap, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(n_steps, o.n_steps, sizeof(int32_t) * n, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -357,22 +312,23 @@ int pair_read_cells(Batch* b, const int32_t job, const int64_t n, const hx_pair_
   if (!b || n < 0 || (n && (!at || !cells))) return api_fail(HX_ERR_INVALID_ARG, "read_cells: bad arguments");
   if (job < 0 || job >= b->n_jobs) return api_fail(HX_ERR_RANGE, "job out of range");
   if (!b->done) return api_fail(HX_ERR_STATE, "read_cells: the batch has not been run");
-  const auto& J = b->jobs[job];
+  using Job = std::remove_cv_t<std::remove_reference_t<decltype(b->jobs[job])>>;
+  const Job& J = b->jobs[job];
   for (int64_t q = 0; q < n; ++q)
     if (at[q].xpos < 0 || at[q].xpos >= J.X || at[q].ypos < 0 || at[q].ypos >= J.Y || at[q].state < 0 || at[q].state >= NS)
       return api_fail(HX_ERR_RANGE, "read_cells: a coordinate outside the matrix");
   if (n == 0) return HX_OK;
   if (hipSetDevice(b->device) != hipSuccess) return api_fail(HX_ERR_HIP, "hipSetDevice failed");
-  PairScratch sc;
-  hx_pair_cell* d_at = sc.get<hx_pair_cell>((size_t)n);
-  double* d_cells = sc.get<double>((size_t)n);
-  double* d_lm = log_match ? sc.get<double>((size_t)n) : nullptr;
+  DevBuf b_at, b_cells, b_lm;
+  hx_pair_cell* d_at = scratch<hx_pair_cell>(b_at, (size_t)n);
+  double* d_cells = scratch<double>(b_cells, (size_t)n);
+  double* d_lm = log_match ? scratch<double>(b_lm, (size_t)n) : nullptr;
   if (!d_at || !d_cells || (log_match && !d_lm)) return api_fail(HX_ERR_OUT_OF_MEMORY, "read_cells: device allocation failed");
   if (hipMemcpy(d_at, at, sizeof(hx_pair_cell) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
     return api_fail(HX_ERR_HIP, "read_cells: copy to the device failed");
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 1024);
-  hipLaunchKernelGGL(k_pair_gather<std::remove_cv_t<std::remove_reference_t<decltype(J)>>>, dim3(blocks), dim3(256), 0, b->last_stream,
-                     b->d_jobs, job, n, d_at, d_cells, d_lm);
+  hipLaunchKernelGGL(k_pair_gather<Job>, dim3(blocks), dim3(256), 0, b->last_stream, b->device_jobs(), job, n, d_at, d_cells,
+                     d_lm);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(b->last_stream) != hipSuccess ||
       hipMemcpy(cells, d_cells, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
       (log_match && hipMemcpy(log_match, d_lm, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess))

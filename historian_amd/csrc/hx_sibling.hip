@@ -126,7 +126,7 @@ struct SiblingCell {
 };
 
 // one job of the ABI -> its device job and its arrays in the arena
-int fill_job(DevSibling& J, const hx_sibling_job& j, PairArena& a) {
+int fill_job(DevSibling& J, const hx_sibling_job& j, Arena& a) {
   if (j.l_len >= 64 * HXBR_MAX_STRIPS)
     return api_fail(HX_ERR_RANGE, "hx_sibling_batch_create: a left child profile of more than 65535 positions");
   if (j.l_len < 0 || j.r_len < 0 || j.components < 1 || j.alphabet < 1 || (j.l_len && (!j.l_sub || !j.l_emit || !j.log_root)) ||
@@ -146,7 +146,7 @@ int fill_job(DevSibling& J, const hx_sibling_job& j, PairArena& a) {
   a.put(J.y_sub, j.r_sub, (size_t)j.r_len * J.CA);
   a.put(J.x_emit, j.l_emit, (size_t)j.l_len);
   a.put(J.y_emit, j.r_emit, (size_t)j.r_len);
-  a.put_env(J, j.l_env, j.r_env, true);
+  put_env(a, J, j.l_env, j.r_env, true);
   return HX_OK;
 }
 

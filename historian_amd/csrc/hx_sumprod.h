@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "../../include/historian_hip.h"
+#include "hx_devmem.h"
 #include "hx_lse.h"
 #include "hx_policy.h"
 
@@ -218,18 +219,6 @@ __device__ __forceinline__ double combine_components(const double* sh_ll, const 
 }
 
 // ---- the launchers' prologue ----
-// a device allocation that is freed on every way out of a launcher
-struct SpBuf {
-  void* p = nullptr;
-  ~SpBuf() { if (p) (void)hipFree(p); }
-};
-// the events around a call's kernels, destroyed on every way out
-struct SpEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~SpEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  bool create() { return hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess; }
-};
-
 extern thread_local float g_sp_ms;             // hx_sumprod.hip: what hx_sumprod_last_kernel_ms reports
 const double* device_lse_table(int device);    // hx_api.hip: the 8-byte log_sum_exp table of an initialised device, or null
 int api_fail(int code, const char* what);       // hx_api.hip: sets hx_last_error()
@@ -274,11 +263,11 @@ inline int sp_check_tokens(const char* fn, const int8_t* tokens, const int64_t n
 
 // The model on the device: one allocation, filled front to back (every piece 16-byte aligned).
 struct SpUpload {
-  SpBuf buf;
+  DevBuf buf;
   char* q = nullptr;
   bool copied = true;
   static size_t room(const size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-  bool alloc(const size_t bytes) { return hipMalloc(&buf.p, bytes) == hipSuccess && (q = static_cast<char*>(buf.p)); }
+  bool alloc(const size_t bytes) { return buf.alloc(bytes) && (q = buf.as<char>()); }
   template <class T> T* reserve(const size_t n) {
     T* at = reinterpret_cast<T*>(q);
     q += room(n * sizeof(T));

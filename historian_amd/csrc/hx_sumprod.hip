@@ -472,10 +472,10 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
   const int parts = real_basis ? 2 : 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
   SpUpload up;
-  SpBuf b_tok, b_w, b_scr, b_out;
+  DevBuf b_tok, b_w, b_scr, b_out;
   const size_t eig = SpUpload::room((size_t)C * AA * sizeof(double)), esc = SpUpload::room((size_t)C * N * AA * sizeof(double));
-  if (!up.alloc(sp_tree_room(A, C, N, true) + 4 * eig + 2 * esc) || hipMalloc(&b_tok.p, (size_t)n_cols * N) != hipSuccess ||
-      (weight && hipMalloc(&b_w.p, n_cols * sizeof(double)) != hipSuccess))
+  if (!up.alloc(sp_tree_room(A, C, N, true) + 4 * eig + 2 * esc) || !b_tok.alloc((size_t)n_cols * N) ||
+      (weight && !b_w.alloc(n_cols * sizeof(double))))
     return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
   const SpTree tr = sp_put_tree(up, A, C, N, hm->parent, child, hm->ins_prob, hm->log_cpt_weight, hm->branch_sub);
   SpModel m;
@@ -487,16 +487,16 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
   m.einv_im = up.put(hm->evec_inv_im, (size_t)C * AA);
   m.esc_re = up.put(hm->esc_re, (size_t)C * N * AA);
   m.esc_im = up.put(hm->esc_im, (size_t)C * N * AA);
-  if (!up.copied || hipMemcpy(b_tok.p, tokens, (size_t)n_cols * N, hipMemcpyHostToDevice) != hipSuccess ||
-      (weight && hipMemcpy(b_w.p, weight, n_cols * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
+  if (!up.copied || hipMemcpy(b_tok.as<void>(), tokens, (size_t)n_cols * N, hipMemcpyHostToDevice) != hipSuccess ||
+      (weight && hipMemcpy(b_w.as<void>(), weight, n_cols * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
     return sp_fail(HX_ERR_HIP, fn, "copy failed");
   const int AP = (A + 1) & ~1;                     // message vectors are stored in pairs of entries
   const size_t per_col = (2 + (size_t)parts) * C * N * AP + 4 * (size_t)C * N + 2 * (size_t)C * A;
   const long long chunk = sp_chunk(per_col, n_cols);
   const size_t n_out = (size_t)n_cols * (1 + (root_post ? A : 0)) + (size_t)C * A + 2 * (size_t)C * AA;
-  if (hipMalloc(&b_scr.p, per_col * (((size_t)chunk + 63) & ~(size_t)63) * sizeof(double)) != hipSuccess || hipMalloc(&b_out.p, n_out * sizeof(double)) != hipSuccess)
+  if (!b_scr.alloc(per_col * (((size_t)chunk + 63) & ~(size_t)63) * sizeof(double)) || !b_out.alloc(n_out * sizeof(double)))
     return sp_fail(HX_ERR_OUT_OF_MEMORY, fn, "device allocation failed");
-  double* out = static_cast<double*>(b_out.p);
+  double* out = b_out.as<double>();
   double* d_cll = out;
   double* d_post = root_post ? out + n_cols : nullptr;
   double* d_root = out + (size_t)n_cols * (1 + (root_post ? A : 0));
@@ -507,12 +507,12 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
   const size_t lds = sizeof(double) * (size_t)parts * A * (HX_SP_TILE + 1);
   if (lds > HX_LDS_LIMIT) return sp_fail(HX_ERR_INVALID_ARG, fn, "basis tile exceeds the LDS of a CU");
   const SpPlan plan = sp_column_plan(A, C, 3, false);           // exp(R t), evecInv, evec
-  SpEvents ev;
+  DevEvents<2> ev;
   if (!ev.create()) return sp_fail(HX_ERR_HIP, fn, "HIP call failed");
-  (void)hipEventRecord(ev.a, st);
+  (void)hipEventRecord(ev[0], st);
   for (long long first = 0; first < n_cols; first += chunk) {
     const long long nc = n_cols - first < chunk ? n_cols - first : chunk;
-    double* scr = static_cast<double*>(b_scr.p);
+    double* scr = b_scr.as<double>();
     SpScratch s;
     const size_t nc64 = ((size_t)nc + 63) & ~(size_t)63;         // the scratch holds whole blocks of 64 columns
     const size_t msg = (size_t)C * N * AP * nc64, lg = (size_t)C * N * nc64;
@@ -523,8 +523,8 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
     s.basis = s.rootc + (size_t)C * A * nc64;
     long long blocks = (nc + 63) / 64;
     if (blocks > 65535) blocks = 65535;
-    const signed char* d_tok = static_cast<const signed char*>(b_tok.p) + first * N;
-    const double* d_w = b_w.p ? static_cast<const double*>(b_w.p) + first : nullptr;
+    const signed char* d_tok = b_tok.as<const signed char>() + first * N;
+    const double* d_w = b_w ? b_w.as<const double>() + first : nullptr;
     double* d_p = d_post ? d_post + first * A : nullptr;
 #define HX_SP_GO(TA_, LM_) hipLaunchKernelGGL((k_sumprod_columns<TA_, LM_>), dim3((unsigned)blocks), dim3(64 * plan.waves), plan.lds, st, m, d_tok, d_w, nc, s, lse_tab, d_cll + first, d_p)
     // (A = 4 has its matrices in LDS whatever C <= 128: 512 C + 24 * 16 * min(C, 8) <= 65536 + 3072 < 98304 - no <4, false> form)
@@ -559,9 +559,9 @@ int hx_sumprod_columns(const hx_sumprod_model* hm, const int8_t* tokens, const d
       hipLaunchKernelGGL(k_row_sums, dim3((unsigned)(C * A), (unsigned)rs), dim3(256), 0, st, s.rootc, nc, d_root);
     }
   }
-  (void)hipEventRecord(ev.b, st);
+  (void)hipEventRecord(ev[1], st);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return sp_fail(HX_ERR_HIP, fn, "kernel launch or execution failed");
-  (void)hipEventElapsedTime(&g_sp_ms, ev.a, ev.b);
+  (void)hipEventElapsedTime(&g_sp_ms, ev[0], ev[1]);
   auto down = [](double* dst, const double* src, const size_t n) { return hipMemcpy(dst, src, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess; };
   if (!down(col_log_like, d_cll, (size_t)n_cols) || (root_post && !down(root_post, d_post, (size_t)n_cols * A)) || !down(root_counts, d_root, (size_t)C * A) ||
       !down(eigen_re, d_re, (size_t)C * AA) || !down(eigen_im, d_im, (size_t)C * AA))

@@ -568,6 +568,11 @@ int hx_distance_last_products(int64_t* products);
 int hx_host_alloc(size_t bytes, void** out);
 int hx_host_free(void* p);
 
+/* Device and page-locked allocations the library holds at this moment, over all devices and objects of the process (events
+ * and streams are not counted, nor is what hx_host_alloc handed out).  An object's destroy call gives back what its create
+ * call and its readers' kept buffers took: a test of lifetimes compares the count before and after.  Never fails. */
+int64_t hx_live_allocations(void);
+
 /* ---- next row N4: per-branch pair DPs -----------------------------------------------------------
  * The three-state (Match / Insert / Delete) alignment of a parent sequence profile x with a child sequence profile y
  * across one tree branch inside a GuideAlignmentEnvelope: Refiner::BranchMatrix (reference src/refiner.cpp:10-60, Viterbi;
